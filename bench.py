@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Benchmark of the two BPMF hot paths on MI355X (contract: see the task brief / DESIGN.md s6).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]            (N = 1)
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]     (N = 1)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 A "step" is one pass of the hot path over one batch of synthetic input that is already
@@ -17,8 +17,15 @@ N > 1 is weak scaling: every rank owns its own shard of templates (MF) / of the 
 the packed (max, arg-max) all-reduce over RCCL.
 
 The JSON line also carries ``roofline`` (dominant kernel, HIP events recorded on the launch
-stream inside the timed region) and ``cpu_baseline`` (the CPU oracle timed on this box's host
-cores on a bounded sample of the same workload; rank 0, N = 1 only).
+stream inside the timed region).  A plain run stops there: set-up, warm-up, the timed steps, the
+outputs (--dump-outputs) and the line.  Everything else the bench measures or checks runs only
+with --full: the ``bp`` object, ``cpu_baseline`` (the CPU oracle timed on this box's host cores on a
+bounded sample of the same workload; rank 0), the detection stage, end-to-end and off-shape
+extras, the per-GPU shares for N > 1 and the rocprofv3 traffic passes.
+
+--dump-outputs DIR writes what the timed matched-filter path returned in its last step (the CC
+matrix, or a fixed seeded sample of it when it exceeds 64 MB) as float32 DIR/<name>.npy; the inputs
+are seeded, so two builds run with the same arguments can be compared output for output.
 """
 import argparse
 import json
@@ -62,6 +69,12 @@ def parse():
     ap.add_argument("--cpu-seconds", type=float, default=15.0,
                     help="target duration of the cpu_baseline sample")
     ap.add_argument("--templates", type=int, default=0, help="override T (debug)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write the CC matrix of the last timed step (a fixed seeded sample if larger than 64 MB) "
+                         "as float32 DIR/<name>.npy")
+    ap.add_argument("--full", action="store_true",
+                    help="also run everything beyond the headline: BP, CPU baselines, detection stage, end-to-end and "
+                         "off-shape extras, shares (N > 1), rocprofv3 traffic passes (the --skip-* options apply here)")
     return ap.parse_args()
 
 
@@ -460,6 +473,39 @@ def detection_stage(cc, planted, mv, w, local_rank, dist, device, t_offset=0):
     return out
 
 
+# ------------------------------------------------------------------- --dump-outputs ---
+DUMP_BYTES = 64 * 10**6          # at most this much in all
+DUMP_ROWS = 512                  # templates kept when T is larger (a seeded sample)
+DUMP_EDGE_LAGS = 4096            # the first and the last lags of every kept row
+DUMP_SAMPLED_LAGS = 16384        # lags between them, a seeded sample
+DUMP_SEED = 20261016
+
+
+def dump_outputs(out_dir, cc):
+    """The (T, n_corr) CC matrix the last timed step wrote, as float32 .npy files under out_dir: whole when it
+    fits DUMP_BYTES, else the kept rows at the first / last DUMP_EDGE_LAGS lags (where tiles of the day begin and
+    end) and at DUMP_SAMPLED_LAGS lags drawn with a fixed seed -- the same samples in every run of the same
+    arguments."""
+    os.makedirs(out_dir, exist_ok=True)
+    T, n = cc.shape
+    if T * n * 4 <= DUMP_BYTES:
+        parts = {"cc_sums": cc}
+    else:
+        rng = np.random.default_rng(DUMP_SEED)
+        if T > DUMP_ROWS:
+            rows = torch.as_tensor(np.sort(rng.choice(T, DUMP_ROWS, replace=False)), device=cc.device)
+            cc = cc.index_select(0, rows)
+        edge = min(DUMP_EDGE_LAGS, n // 2)
+        inner = n - 2 * edge
+        k = min(DUMP_SAMPLED_LAGS, inner)
+        lags = torch.as_tensor(edge + np.sort(rng.choice(inner, k, replace=False)), device=cc.device)
+        parts = {"cc_sums_first_lags": cc[:, :edge], "cc_sums_last_lags": cc[:, n - edge:],
+                 "cc_sums_sampled_lags": cc.index_select(1, lags)}
+    assert sum(v.numel() * 4 for v in parts.values()) <= DUMP_BYTES
+    for name, v in parts.items():
+        np.save(os.path.join(out_dir, name + ".npy"), v.contiguous().cpu().numpy().astype(np.float32, copy=False))
+
+
 # --------------------------------------------------------------------- the JSON line ---
 # keys the driver's contract names (+ the two objects of the hot-path tier); tests/test_bench_cli.py holds every
 # N to them
@@ -533,10 +579,12 @@ def self_launch(args):
 
     The driver's documented N > 1 command wraps bench.py in `python -m torch.distributed.run`; a bare
     `python bench.py --gpus 8` (the shape of the N = 1 command) used to run ONE rank and report n_gpus 1
-    without a word (round-4 review).  Now it re-executes itself under torch.distributed.run with
-    --nproc-per-node N on 127.0.0.1 and a free port, or fails loudly when fewer than N devices are visible.
-    BPMF_BENCH_FORCE_DIST=1 takes the same route for N = 1 (RCCL initialised with one rank)."""
+    without a word (round-4 review).  Now it runs itself under torch.distributed.run with
+    --nproc-per-node N on 127.0.0.1 and a free port, as a child process whose exit status it returns (the
+    device count above may have initialised HIP in this process), or fails loudly when fewer than N devices
+    are visible.  BPMF_BENCH_FORCE_DIST=1 takes the same route for N = 1 (RCCL initialised with one rank)."""
     import socket
+    import subprocess
     n_dev = torch.cuda.device_count() if torch.cuda.is_available() else 0
     if n_dev < args.gpus:
         raise SystemExit(f"bench.py --gpus {args.gpus}: only {n_dev} HIP device(s) visible "
@@ -553,17 +601,18 @@ def self_launch(args):
     sys.stdout.flush()
     sys.stderr.write(f"[bench] launching {args.gpus} rank(s): {' '.join(cmd)}\n")
     sys.stderr.flush()
-    os.execve(sys.executable, cmd, env)
+    raise SystemExit(subprocess.run(cmd, env=env).returncode)
 
 
 def main():
     args = parse()
+    full = args.full                            # everything beyond the headline (module docstring)
     force_dist = os.environ.get("BPMF_BENCH_FORCE_DIST") == "1"
     launched = "RANK" in os.environ and "WORLD_SIZE" in os.environ
     if args.gpus < 1:
         raise SystemExit("--gpus must be >= 1")
     if not launched and (args.gpus > 1 or force_dist):
-        self_launch(args)                       # does not return
+        self_launch(args)                       # does not return: exits with the ranks' status
     rank = int(os.environ.get("RANK", 0))
     local_rank = int(os.environ.get("LOCAL_RANK", 0))
     world = int(os.environ.get("WORLD_SIZE", 1))
@@ -657,6 +706,8 @@ def main():
 
     mf_dt = timed(mf_step, args.steps, args.warmup)
     mf_own_dt = own_dt[-1]
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, cc)
     mf_kernel_ms = _lib.profile_times_ms(_lib.KERNEL_MF_MAIN)
     mf_value = world * T * n_corr * args.steps / mf_dt / 1e6
     flop_per_launch = 2.0 * L * S * C * T * n_corr          # direct-form, all channels weighted
@@ -685,11 +736,11 @@ def main():
     rank_stats = {"rank": rank, "mf_ms_per_step": round(mf_own_dt / args.steps * 1e3, 3), "mf_kernel_ms": round(k_ms, 3),
                   "mf_frac": round(achieved / FP32_PEAK_TFLOPS, 4)}
     peak = float(cc[0].max().item())
-    detect = detection_stage(cc, planted, mv, w, local_rank, dist, device, t_offset=rank * T)
+    detect = detection_stage(cc, planted, mv, w, local_rank, dist, device, t_offset=rank * T) if full else None
     # untimed extra: the same step under option mf.compat_sqrt_norm (cc = num / sqrtf(E_t * E_d) in the
     # epilogue of the MFMA kernel: an IEEE square root and divide per channel and lag)
     compat = None
-    if rank == 0 and world == 1 and dist is None and not args.skip_e2e:
+    if full and rank == 0 and world == 1 and dist is None and not args.skip_e2e:
         with _lib.options(**{"mf.compat_sqrt_norm": 1}):
             mf_step()
             torch.cuda.synchronize()
@@ -712,7 +763,7 @@ def main():
     # over all T x n_corr CC sums (bar 2e-5: SURVEY App. C MF-5) and whether every planted event is still detected
     # at exactly its index by the product's detection stage.
     split16 = None
-    if rank == 0 and world == 1 and dist is None and not args.skip_e2e:
+    if full and rank == 0 and world == 1 and dist is None and not args.skip_e2e:
         try:
             cc2 = torch.empty_like(cc)
             with _lib.options(**{"mf.split16": 1}):
@@ -769,7 +820,7 @@ def main():
     # Untimed extra, N = 1 only; two calls, the faster one is reported (each call allocates and
     # first-touches its own 17 GB result array).  Never `value`.
     e2e = None
-    if world == 1 and dist is None and not args.skip_e2e and T * n_corr * 4 < 40e9:
+    if full and world == 1 and dist is None and not args.skip_e2e and T * n_corr * 4 < 40e9:
         h_t, h_mv, h_w, h_d = (x.cpu().numpy() for x in (tmpl, mv, w, data))
         e2e_ms, mf_thr = [], []
         h_cc = None
@@ -812,7 +863,7 @@ def main():
     # configs[0] (the reference's own CPU-runnable case: one hour, 4 templates, L = 128) and a day with
     # 128-sample templates; kernel time from the library's events, the whole call from the host clock
     mf_shapes = None
-    if rank == 0 and world == 1 and dist is None and not args.skip_e2e:
+    if full and rank == 0 and world == 1 and dist is None and not args.skip_e2e:
         mf_shapes = {}
         # ("tutorial": the shape of the reference's own tutorial, /root/reference/tutorial/notebooks/BPMF_parameters.cfg:7-16 --
         # 10 templates of 8 s at 25 Hz on 8 stations x 3 components, one day at 25 Hz)
@@ -914,7 +965,7 @@ def main():
 
     # ---------------------------------------------------------------- backprojection
     bp_obj = None
-    if not args.skip_bp:
+    if full and not args.skip_bp:
         bcfg = dict(syn.BP_CONFIGS[args.bp_config])
         geo, feat, wp = bp_inputs(bcfg, device, 20260928, rank, world)
         K_all = geo["moveouts"].shape[0]
@@ -1184,7 +1235,7 @@ def main():
     # weighted) followed by the packed-key all-reduce.  One warm-up and one timed step each, same barrier and
     # max-over-ranks timing as the headline.
     shares = None
-    if (world > 1 or dist is not None) and not args.skip_shares:
+    if full and (world > 1 or dist is not None) and not args.skip_shares:
         shares = {}
         try:
             del data, tmpl, mv, w
@@ -1275,7 +1326,7 @@ def main():
             torch.cuda.empty_cache()
 
     cpu = None
-    if rank == 0 and dist is None and not args.skip_cpu:
+    if full and rank == 0 and dist is None and not args.skip_cpu:
         cpu = cpu_baseline(cfg, args.cpu_seconds)
     # every rank's own step time, kernel time and roofline fraction into `ranks` (a straggler GPU -- the boxes of
     # one pool differ by +-5 % -- is then visible in a weak-scaling ratio)
@@ -1286,7 +1337,7 @@ def main():
 
     # roofline.traffic measured in this run (separate PMC passes in child processes, after everything
     # else, with this process's device memory released); headline workloads only
-    if rank == 0 and world == 1 and dist is None and not args.skip_traffic:
+    if full and rank == 0 and world == 1 and dist is None and not args.skip_traffic:
         try:
             del data, tmpl, mv, w
         except Exception:
@@ -1320,7 +1371,7 @@ def main():
     # N > 1: the CPU baseline AFTER the process group is gone -- the other ranks have exited (a rank waiting in a
     # collective spins on a host core, and the cgroup grants 16), rank 0 times the oracle alone, exactly as at N = 1
     # (taken whenever a process group was initialised -- BPMF_BENCH_FORCE_DIST=1 runs it with one rank on a one-GPU box)
-    if line is not None and dist is not None and not args.skip_cpu:
+    if full and line is not None and dist is not None and not args.skip_cpu:
         try:
             del data, tmpl, mv, w
         except Exception:

@@ -26,6 +26,8 @@ import numpy as np
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(os.path.dirname(HERE))
+sys.path.insert(0, os.path.dirname(HERE))
+import golden_npz  # noqa: E402  (fixtures larger than a committed file are written in parts)
 REF = "/root/reference"
 
 
@@ -143,9 +145,9 @@ def main():
         thr = clib.time_dependent_threshold(x, window, 8.0, overlap=overlap, white_noise=wn,
                                             num_threads=1)
         cases.append(dict(x=x, white_noise=wn, window=window, overlap=overlap, num_dev=8.0, thr=thr))
-    np.savez_compressed(os.path.join(HERE, "tdt_rms.npz"),
-                        **{f"{k}_{j}": np.asarray(v) for j, c in enumerate(cases) for k, v in c.items()},
-                        n_cases=len(cases))
+    golden_npz.save(os.path.join(HERE, "tdt_rms.npz"),
+                    **{f"{k}_{j}": np.asarray(v) for j, c in enumerate(cases) for k, v in c.items()},
+                    n_cases=len(cases))
 
     # ---- libc.c: select_cc_indexes ---------------------------------------------------
     cases = []
@@ -280,7 +282,7 @@ def main():
         env.update({f"traces_{j}": tr, f"features_{j}": np.asarray(feat, dtype=np.float32),
                     f"availability_{j}": np.asarray(avail, dtype=np.int32),
                     f"envelope_{j}": np.float32([template_search.envelope(x_) for x_ in tr.reshape(-1, n)]).reshape(tr.shape)})
-    np.savez_compressed(os.path.join(HERE, "saturated_envelopes.npz"), n_cases=2, **env)
+    golden_npz.save(os.path.join(HERE, "saturated_envelopes.npz"), n_cases=2, **env)
     # ---- BP-4: Beamformer source-weight builders (template_search.py:779-895) ---------------
     # and MF-6: MatchedFilter channel-weight builders / set_data / TemplateGroup.normalize
     # (similarity_search.py:163-185, 288-474; dataset.py:4152-4166, 4996-5001), through fake
@@ -431,7 +433,7 @@ def main():
         tg._remember = lambda name: None
         tg.normalize(method=method)
         wts[f"tg_norm_{method}"] = np.asarray(tg._waveforms_arr)
-    np.savez_compressed(os.path.join(HERE, "weights.npz"), **wts)
+    golden_npz.save(os.path.join(HERE, "weights.npz"), **wts)
     relocation_goldens(BPMF)
 
     print("goldens written to", HERE)

@@ -88,3 +88,47 @@ def test_the_n8_line_has_every_key_of_the_n1_line():
     assert l8["ranks"]["mf_kernel_ms_spread"] == {"min": 985.0, "max": 992.0, "slowest_over_fastest": round(992.0 / 985.0, 4)}
     assert l1["ranks"] is None
     json.loads(json.dumps(l8))
+
+
+def _bench_module():
+    import importlib.util
+    spec = importlib.util.spec_from_file_location("bench_module", os.path.join(ROOT, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    return bench
+
+
+def test_plain_and_full_runs_are_both_offered():
+    res = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--help"], capture_output=True, text=True,
+                         timeout=300)
+    assert res.returncode == 0 and "--full" in res.stdout and "--dump-outputs" in res.stdout
+
+
+def test_dump_outputs_is_bounded_float32_and_the_same_every_run(tmp_path):
+    """--dump-outputs on a CC matrix of the headline's row count: at most 64 MB of float32 .npy files, the first and
+    last lags of every row exactly, and the same sampled lags in every run; a small matrix is written whole."""
+    import numpy as np
+    import torch
+    bench = _bench_module()
+    cc = torch.randn((500, 40_000), generator=torch.Generator().manual_seed(1))
+    for run in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / run), cc)
+    names = sorted(os.listdir(tmp_path / "a"))
+    assert names == sorted(os.listdir(tmp_path / "b")) and all(n.endswith(".npy") for n in names)
+    total = 0
+    for n in names:
+        a, b = np.load(tmp_path / "a" / n), np.load(tmp_path / "b" / n)
+        assert a.dtype == np.float32 and np.array_equal(a, b)
+        total += a.nbytes
+    assert total <= 64 * 10**6
+    assert np.array_equal(np.load(tmp_path / "a" / "cc_sums_first_lags.npy"), cc[:, :4096].numpy())
+    assert np.array_equal(np.load(tmp_path / "a" / "cc_sums_last_lags.npy"), cc[:, -4096:].numpy())
+    sampled = np.load(tmp_path / "a" / "cc_sums_sampled_lags.npy")
+    assert sampled.shape == (500, 16384)
+    inner = cc.numpy()[:, 4096:-4096]
+    for k in (0, 8191, 16383):                   # every sampled lag is one lag between the two edges
+        assert np.flatnonzero((inner == sampled[:, k:k + 1]).all(axis=0)).size == 1
+    small = torch.randn((4, 1000))
+    bench.dump_outputs(str(tmp_path / "small"), small)
+    assert os.listdir(tmp_path / "small") == ["cc_sums.npy"]
+    assert np.array_equal(np.load(tmp_path / "small" / "cc_sums.npy"), small.numpy())

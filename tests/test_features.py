@@ -5,12 +5,14 @@ import os
 import numpy as np
 import pytest
 
+import golden_npz
+
 GOLD = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "saturated_envelopes.npz")
 
 
 def test_host_restatement_equals_the_reference():
     from oracle.features_host import envelope_host, saturated_envelopes_host
-    g = np.load(GOLD)
+    g = golden_npz.load(GOLD)
     for j in range(int(g["n_cases"])):
         tr = g[f"traces_{j}"]
         env = np.float32([envelope_host(x) for x in tr.reshape(-1, tr.shape[-1])]).reshape(tr.shape)
@@ -44,7 +46,7 @@ def test_reference_fft_is_single_precision():
     FFT: its envelopes carry round-off of a few float32 ulp OF THE CHANNEL'S LARGEST VALUE
     everywhere (a 3e6 spike puts +-0.5 on every sample).  This bounds how closely any other
     implementation can agree with the golden file, and is the tolerance of the device test."""
-    g = np.load(GOLD)
+    g = golden_npz.load(GOLD)
     for j in range(int(g["n_cases"])):
         tr, gold = g[f"traces_{j}"], g[f"envelope_{j}"]
         exact = _envelope_f64(tr)
@@ -63,7 +65,7 @@ def test_device_envelopes_against_float64_and_the_reference_output():
     divided by the channel's MAD.  Availability and the dropped channels match exactly."""
     from scipy.stats import median_abs_deviation as scimad
     from seismic_bpmf_amd.features import envelope, saturated_envelopes
-    g = np.load(GOLD)
+    g = golden_npz.load(GOLD)
     for j in range(int(g["n_cases"])):
         tr = g[f"traces_{j}"]
         env = envelope(tr).cpu().numpy()

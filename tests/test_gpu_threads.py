@@ -79,7 +79,7 @@ def test_hot_paths_from_concurrent_threads(oracle_lib):
             assert np.array_equal(pk[0], wpk[0]) and np.array_equal(pk[1], wpk[1]), j
 
 
-def test_multi_device_calls_from_competing_processes():
+def test_multi_device_calls_from_competing_processes(tmp_path):
     """4 processes x 40 iterations of ~16 host-pointer calls each with the same GPU listed 2-6 times
     (tools/stress/stress_multi.py: every result compared bit for bit with the single-device call of the same
     inputs).  Rounds 2-3 ran every listed device on its own host thread, each creating streams, events
@@ -89,7 +89,7 @@ def test_multi_device_calls_from_competing_processes():
     import subprocess
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    out = os.path.join(root, "gpurun_out", "stress_test")
+    out = str(tmp_path / "stress_test")
     res = subprocess.run([sys.executable, os.path.join(root, "tools", "stress", "stress_multi.py"), "--procs", "4",
                           "--threads", "1", "--calls", "40", "--out", out, "--timeout", "600"],
                          capture_output=True, text=True, timeout=700)

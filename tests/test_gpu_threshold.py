@@ -5,6 +5,8 @@ import os
 import numpy as np
 import pytest
 
+import golden_npz
+
 pytestmark = pytest.mark.gpu
 GOLD = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 
@@ -12,7 +14,7 @@ GOLD = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 def test_tdt_rms_matches_reference_goldens():
     import torch
     from seismic_bpmf_amd.threshold import ThresholdGPU
-    g = np.load(os.path.join(GOLD, "tdt_rms.npz"))
+    g = golden_npz.load(os.path.join(GOLD, "tdt_rms.npz"))
     th = ThresholdGPU()
     for j in range(int(g["n_cases"])):
         x = torch.as_tensor(g[f"x_{j}"], device="cuda")

@@ -5,11 +5,13 @@ import os
 import numpy as np
 import pytest
 
+import golden_npz
+
 GOLD = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 
 
 def load(name):
-    return np.load(os.path.join(GOLD, name))
+    return golden_npz.load(os.path.join(GOLD, name))
 
 
 def test_time_dependent_threshold_rms(oracle_lib):

@@ -5,6 +5,7 @@ import os
 import numpy as np
 import pytest
 
+import golden_npz
 from seismic_bpmf_amd import postprocess as pp
 from seismic_bpmf_amd import synthetic as syn
 
@@ -12,7 +13,7 @@ GOLD = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 
 
 def load(name):
-    return np.load(os.path.join(GOLD, name))
+    return golden_npz.load(os.path.join(GOLD, name))
 
 
 def test_sec_to_samp():

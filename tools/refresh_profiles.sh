@@ -8,10 +8,10 @@ OUT=$R/gpurun_out/prof_$TAG
 mkdir -p $OUT $R/profiles
 cd /tmp && export TMPDIR=/tmp
 # 1. the bench line, un-profiled
-(cd $R && python bench.py) > $OUT/bench.log 2>&1
+(cd $R && python bench.py --full) > $OUT/bench.log 2>&1
 grep '^{' $OUT/bench.log | tail -1 > $R/profiles/${TAG}_bench.json
 # 2. the same command under rocprofv3 --kernel-trace --stats
-rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats -- python $R/bench.py > $OUT/bench_rocprof.log 2>&1
+rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats -- python $R/bench.py --full > $OUT/bench_rocprof.log 2>&1
 grep '^{' $OUT/bench_rocprof.log | tail -1 > $R/profiles/${TAG}_bench_under_rocprof.json
 # 3. PMC passes, counters only (no other trace domains), small targets
 for c in "SQ_LDS_IDX_ACTIVE SQ_LDS_BANK_CONFLICT SQ_INSTS_LDS" "SQ_INSTS_VALU SQ_ACTIVE_INST_VALU SQ_INSTS_MFMA" \
@@ -24,7 +24,7 @@ for c in "SQ_LDS_IDX_ACTIVE SQ_LDS_BANK_CONFLICT SQ_INSTS_LDS" "SQ_INSTS_VALU SQ
 done
 # 4. the one-rank RCCL record on the current kernels: process group initialised, BP steps end with the
 #    packed-key all-reduce, detections all-gathered, the per-GPU shares of configs[3] / [4] as extras
-(cd $R && BPMF_BENCH_FORCE_DIST=1 timeout 900 python bench.py --gpus 1 --steps 2 --warmup 1 --skip-cpu --skip-traffic --skip-dense) > $OUT/bench_force_dist.log 2>&1
+(cd $R && BPMF_BENCH_FORCE_DIST=1 timeout 900 python bench.py --full --gpus 1 --steps 2 --warmup 1 --skip-cpu --skip-traffic --skip-dense) > $OUT/bench_force_dist.log 2>&1
 grep '^{' $OUT/bench_force_dist.log | tail -1 > $R/profiles/${TAG}_bench_force_dist_1rank.json
 # 5. spread of the BP FETCH_SIZE figure: the same pass five times
 for i in 1 2 3 4 5; do

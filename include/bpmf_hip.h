@@ -87,8 +87,8 @@ int bpmf_host_call_stats(double *out, int n);
  * the host-pointer calls, group ranges per tile): the GPU tests use them to drive every kernel
  * family through the same parity cases, tools/ to measure alternatives.  Process-wide, thread
  * safe; plans already built keep the variant they were built with.  Names:
- *   bp.lds_kb bp.max_group bp.tpt bp.reorder bp.dual bp.packed bp.wps bp.uvgpr bp.fast
- *   bp.fast_uniform bp.fast_tile bp.halves bp.direct bp.split bp.wpb bp.smeta bp.slot_prio bp.verbose
+ *   bp.lds_kb bp.max_group bp.tpt (1 or 2) bp.reorder bp.dual bp.fast
+ *   bp.fast_uniform bp.fast_tile bp.halves bp.direct bp.split bp.slot_prio bp.verbose
  *   mf.wave_kernel mf.tiles_per_wave mf.boundary_prio mf.fused_prologue mf.channel_split mf.max_mfma_step mf.host_batch_kb mf.host_piece_kb mf.verbose
  *   stats.bucketed_median (MAD threshold, window medians: 2 one pass each, 1 two passes, 0 radix select only)
  *   stats.row_grid_min_n (row median / MAD: rows at least this long are read twice by the whole chip; -1 never)

@@ -240,13 +240,13 @@ __global__ __launch_bounds__(BP_THREADS) void bp_beam_kernel(
     }
 }
 
-// ------------------------------------------------ beam, uniform-VGPR metadata ---
-// Fast path for sources with at most NTV (station, phase) terms (NTV <= 32).  The per-term
-// metadata {LDS byte offset, weight} is loaded with VECTOR loads from a wave-uniform address
-// (every lane receives the same value), two sources ahead, so that the gather loop is three
-// instructions per term: v_add (address) / ds_read2st64_b32 (TPT = 2 gathers) / v_pk_fma.
-// (Round 1 ruled scalar loads out here -- SMEM shares the lgkm counter with the LDS gathers -- see the
-// note above bp_beam_kernel; v_readlane broadcasting costs two more VALU issues per term.)
+// ------------------------------------------------ beam, one wave per source ---
+// For sources with at most NTV (station, phase) terms (NTV <= 32).  The per-term metadata
+// {LDS byte offset, weight} is loaded with VECTOR loads from a wave-uniform address (every lane
+// receives the same value), ahead of its use, so that a term costs one address add, its gathers
+// and their fmas.  (Round 1 ruled scalar loads out here -- SMEM shares the lgkm counter with the
+// LDS gathers -- see the note above bp_beam_kernel; v_readlane broadcasting costs two more VALU
+// issues per term.)
 struct BpTermV {
     int off_bytes;  // LDS byte offset of the term's window origin (+ moveout)
     float beta;     // source weight of the term's station
@@ -268,133 +268,13 @@ struct BpMetaV {
     }
 };
 
-template <int TPT, int NTV, int OOB, int REDUCE>
-__global__ __launch_bounds__(BP_THREADS) void bp_beam_uvgpr_kernel(
-    const float* __restrict__ U, long long N, const BpGroup* __restrict__ groups, int n_groups,
-    const int4* __restrict__ chunks, const int4* __restrict__ srcs4,
-    const int4* __restrict__ terms, int id_offset, float* __restrict__ out_beam,
-    int* __restrict__ out_arg, long long tile_base, float best0)
-{
-    extern __shared__ float lds[];
-    const int tid = threadIdx.x;
-    const int lane = tid & 63;
-    constexpr int TILE = BP_THREADS * TPT;
-    const long long t0 = (tile_base + (long long)blockIdx.x) * TILE;
-    int vzero;
-    asm volatile("v_mov_b32 %0, 0" : "=v"(vzero));
-    const char* lds_t = (const char*)lds + tid * 4;
-
-    float best[TPT];
-    int arg[TPT];
-#pragma unroll
-    for (int j = 0; j < TPT; ++j) {
-        best[j] = best0;
-        arg[j] = id_offset;
-        lds[tid + j * BP_THREADS] = 0.0f;  // the zero slab (never overwritten)
-    }
-
-    for (int g = 0; g < n_groups; ++g) {
-        const BpGroup grp = groups[g];
-        const int k_last = grp.first_src + grp.n_src - 1;
-        BpMetaV<NTV> m0, m1, m2;
-        m0.load(srcs4, terms, grp.first_src, vzero);
-        m1.load(srcs4, terms, min(grp.first_src + 1, k_last), vzero);
-        __syncthreads();  // previous group's gathers are done
-        for (int cb = 0; cb < grp.n_chunk; cb += 64) {
-            const int nb = min(64, grp.n_chunk - cb);
-            int4 d = make_int4(0, 0, 0, 0);
-            if (lane < nb) d = chunks[grp.first_chunk + cb + lane];
-            for (int c = 0; c < nb; c += 4) {
-                int row[4], dd[4], n[4];
-                long long gi[4];
-#pragma unroll
-                for (int u = 0; u < 4; ++u) {
-                    const int cc = min(c + u, nb - 1);
-                    row[u] = lane_bcast(d.x, cc);
-                    gi[u] = t0 + lane_bcast(d.y, cc) + tid;
-                    dd[u] = lane_bcast(d.z, cc);
-                    n[u] = c + u < nb ? lane_bcast(d.w, cc) : 0;
-                }
-                float v[4];
-#pragma unroll
-                for (int u = 0; u < 4; ++u) {
-                    const long long gc = gi[u] < 0 ? 0 : (gi[u] >= N ? N - 1 : gi[u]);
-                    v[u] = U[(size_t)row[u] * (size_t)N + gc];
-                }
-#pragma unroll
-                for (int u = 0; u < 4; ++u)
-                    if (tid < n[u]) lds[dd[u] + tid] = (gi[u] >= 0 && gi[u] < N) ? v[u] : 0.0f;
-            }
-        }
-        __syncthreads();
-
-        auto process = [&](const BpMetaV<NTV>& m) {
-            const int nterm = __builtin_amdgcn_readfirstlane(m.hd.w);
-            float acc[TPT];
-#pragma unroll
-            for (int j = 0; j < TPT; ++j) acc[j] = 0.0f;
-#pragma unroll
-            for (int c = 0; c < NTV / 4; ++c) {
-                if (c * 4 < nterm) {  // wave-uniform
-                    float x[4][TPT];
-#pragma unroll
-                    for (int i = 0; i < 4; ++i) {
-                        const int4 tt = m.t[(c * 4 + i) / 2];
-                        const int ob = (i & 1) ? tt.z : tt.x;
-                        const float* lp = (const float*)(lds_t + ob);
-#pragma unroll
-                        for (int j = 0; j < TPT; ++j) x[i][j] = lp[j * BP_THREADS];
-                    }
-#pragma unroll
-                    for (int i = 0; i < 4; ++i) {
-                        const int4 tt = m.t[(c * 4 + i) / 2];
-                        const float beta = __int_as_float((i & 1) ? tt.w : tt.y);
-#pragma unroll
-                        for (int j = 0; j < TPT; ++j) acc[j] = __fmaf_rn(beta, x[i][j], acc[j]);
-                    }
-                }
-            }
-            const int sid = m.hd.x;
-#pragma unroll
-            for (int j = 0; j < TPT; ++j) {
-                const long long t = t0 + tid + j * BP_THREADS;
-                bool computed = nterm > 0;
-                if (OOB == BPMF_BP_STRICT) computed = computed && (t + m.hd.y >= 0) && (t + m.hd.z < N);
-                if (REDUCE == BPMF_BP_REDUCE_MAX) {
-                    const bool better = acc[j] > best[j] || (acc[j] == best[j] && sid < arg[j]);
-                    if (computed && better) { best[j] = acc[j]; arg[j] = sid; }
-                } else {
-                    if (t < N)
-                        out_beam[(size_t)(sid - id_offset) * (size_t)N + t] = computed ? acc[j] : 0.0f;
-                }
-            }
-        };
-        for (int k = grp.first_src; k <= k_last; k += 3) {
-            m2.load(srcs4, terms, min(k + 2, k_last), vzero);
-            process(m0);
-            m0.load(srcs4, terms, min(k + 3, k_last), vzero);
-            process(m1);
-            m1.load(srcs4, terms, min(k + 4, k_last), vzero);
-            process(m2);
-        }
-    }
-    if (REDUCE == BPMF_BP_REDUCE_MAX) {
-#pragma unroll
-        for (int j = 0; j < TPT; ++j) {
-            const long long t = t0 + tid + j * BP_THREADS;
-            if (t < N) { out_beam[t] = best[j]; out_arg[t] = arg[j]; }
-        }
-    }
-}
-
-// ------------------------------------------------ beam, one wave per source ---
-// Same data flow as bp_beam_uvgpr_kernel, but inside a workgroup the four waves take
-// DIFFERENT sources (k, k+1, k+2, k+3, then +4 ...) and each wave covers the whole time tile
-// (TPW samples per lane, tile = 64 * TPW).  The wave-uniform metadata of a source is then
-// fetched by one wave only, which divides the vector-memory return traffic of the metadata
-// broadcast (the limiter of the time-split kernel: 13 x 1 KiB per source per wave) by four,
-// and one address add serves TPW gathers.  Every wave keeps its own running (max, arg-max)
-// for the tile; they are merged through LDS at the end with the same (value, lowest id) order.
+// Inside a workgroup the four waves take DIFFERENT sources (k, k+1, k+2, k+3, then +4 ...) and
+// each wave covers the whole time tile (TPW samples per lane, tile = 64 * TPW).  The wave-uniform
+// metadata of a source is then fetched by one wave only, which divides the vector-memory return
+// traffic of the metadata broadcast (the limiter of the earlier time-split layout: 13 x 1 KiB per
+// source per wave) by four, and one address add serves TPW gathers.  Every wave keeps its own
+// running (max, arg-max) for the tile; they are merged through LDS at the end with the same
+// (value, lowest id) order.
 template <int TPW, int NTV, int OOB, int REDUCE>
 __global__ __launch_bounds__(BP_THREADS) void bp_beam_wps_kernel(
     const float* __restrict__ U, long long N, const BpGroup* __restrict__ groups, int n_groups,
@@ -537,27 +417,8 @@ __global__ __launch_bounds__(BP_THREADS) void bp_beam_wps_kernel(
 // sources).  Measured on cfg3 with the metadata in VGPRs: WPB 4 (8 waves/CU) 0.342 s, more waves
 // spill; with the metadata in SGPRs (BpMetaS, <= 80 VGPRs): WPB 4 0.280 s, WPB 8 (16 waves/CU)
 // 0.241 s, WPB 12 (24 waves/CU) 0.236 s.
-template <int NSV>
-struct BpMetaP {
-    int4 hd;            // id, tmin, tmax, stations (padded to 2; 0 = unused source)
-    int4 st[NSV / 2];   // two stations per int4: {offs, weight, offs, weight}
-    __device__ __forceinline__ void load(const int4* __restrict__ srcs4,
-                                         const int4* __restrict__ recs, int k, int vzero)
-    {
-        const size_t kk = (size_t)(k + vzero);  // vzero: see BpMetaV
-        hd = srcs4[kk];
-#pragma unroll
-        for (int i = 0; i < NSV / 2; ++i) st[i] = recs[kk * (NSV / 2) + i];
-    }
-    __device__ __forceinline__ unsigned offs(int s) const { return (unsigned)((s & 1) ? st[s >> 1].z : st[s >> 1].x); }
-    __device__ __forceinline__ float beta(int s) const { return __int_as_float((s & 1) ? st[s >> 1].w : st[s >> 1].y); }
-    __device__ __forceinline__ int id() const { return hd.x; }
-    __device__ __forceinline__ int tmin() const { return hd.y; }
-    __device__ __forceinline__ int tmax() const { return hd.z; }
-    __device__ __forceinline__ int nsta() const { return hd.w; }
-};
-
-// Scalar-register variant of the metadata (NSV <= 16): ONE set of 4 + 2 NSV SGPRs, filled by
+//
+// The metadata of a source in scalar registers: ONE set of 4 + 2 NSV SGPRs (NSV <= 16), filled by
 // inline-asm s_load_dwordx4/x8 for the NEXT source right after the last gather of the current
 // one, so the scalar-cache latency hides behind the max/arg-max epilogue.  SMEM shares lgkmcnt
 // with the LDS gathers and returns out of order, hence the placement: nothing else is in flight
@@ -612,7 +473,6 @@ struct BpMetaS {
         __builtin_amdgcn_sched_barrier(0);
     }
     __device__ __forceinline__ unsigned offs(int s) const { return (unsigned)r[(2 * s) >> 3][(2 * s) & 7]; }
-    __device__ __forceinline__ float beta(int s) const { return __int_as_float(r[(2 * s + 1) >> 3][(2 * s + 1) & 7]); }
     // {offs, weight} as one aligned SGPR pair: v_pk_fma_f32 takes the weight from its high half
     __device__ __forceinline__ i32x2 pair(int s) const
     {
@@ -630,7 +490,7 @@ struct BpMetaS {
 // B64 (plans with dual windows, see build_plan): every LDS offset is even, a lane owns the
 // sample PAIRS 128 j + 2 lane + {0, 1} and gathers them with ds_read_b64 -- 256 B/clk/CU instead of
 // the 128 B/clk/CU of the 4-byte gathers.
-template <int WPB, int NSV, int OOB, int REDUCE, bool SMETA = false, bool B64 = false>
+template <int WPB, int NSV, int OOB, int REDUCE, bool B64 = false>
 __global__ __launch_bounds__(64 * WPB, WPB >= 16 ? WPB / 4 : (WPB * 2 + 3) / 4) void bp_beam_wps2_kernel(
     const float* __restrict__ U, long long N, const BpGroup* __restrict__ groups, int n_groups,
     const int4* __restrict__ chunks, const int4* __restrict__ srcs4,
@@ -653,7 +513,6 @@ __global__ __launch_bounds__(64 * WPB, WPB >= 16 ? WPB / 4 : (WPB * 2 + 3) / 4) 
         out_arg += (size_t)blockIdx.y * (size_t)split_stride;
     }
     constexpr bool GLOCAL = B64 && REDUCE == BPMF_BP_REDUCE_MAX;
-    constexpr bool SPAIR = SMETA;
     const int tid = threadIdx.x;
     const int lane = tid & 63;
     const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -681,8 +540,8 @@ __global__ __launch_bounds__(64 * WPB, WPB >= 16 ? WPB / 4 : (WPB * 2 + 3) / 4) 
         const BpGroup grp = groups[g];
         const int k_last = grp.first_src + grp.n_src - 1;
         const int k_first = grp.first_src + wv;
-        using Meta = typename std::conditional<SMETA, BpMetaS<NSV>, BpMetaP<NSV>>::type;
-        Meta m0, m1;
+        using Meta = BpMetaS<NSV>;
+        Meta meta;
         // GLOCAL: the plan lists a group's sources by ascending id, so inside a group a plain
         // strict > keeps the lowest id on ties; the full tie rule runs once per group.
         float bestg[GLOCAL ? TPW : 1];
@@ -691,12 +550,11 @@ __global__ __launch_bounds__(64 * WPB, WPB >= 16 ? WPB / 4 : (WPB * 2 + 3) / 4) 
 #pragma unroll
             for (int j = 0; j < TPW; ++j) { bestg[j] = -INFINITY; argg[j] = 0x7fffffff; }
         }
-        if constexpr (!SMETA) m0.load(srcs4, recs, min(k_first, k_last), vzero);
         __syncthreads();  // previous group's gathers are done
         // the first source's metadata travels while the windows are staged (the staging uses no
         // scalar registers of its own, so nothing tempts the compiler to spill this set in flight:
         // tools/check_inflight.py)
-        if constexpr (SMETA) { if (k_first <= k_last) m0.issue(srcs4, recs, k_first); }
+        if (k_first <= k_last) meta.issue(srcs4, recs, k_first);
         // Staging, one chunk per wave and 16 bytes per lane: a chunk is <= 256 consecutive floats
         // of one prestacked row (the plan cuts windows to multiples of 4 floats at 16-byte
         // aligned LDS offsets), so it is one unaligned global_load_dwordx4 + one ds_write_b128
@@ -744,7 +602,7 @@ __global__ __launch_bounds__(64 * WPB, WPB >= 16 ? WPB / 4 : (WPB * 2 + 3) / 4) 
                     if (4 * lane < dsc[r].w) *(f32x4v*)(lds + dsc[r].z + 4 * lane) = v[r];
             }
         }
-        if constexpr (SMETA) { if (k_first <= k_last) m0.wait(); }
+        if (k_first <= k_last) meta.wait();
         __syncthreads();
 
         // Gathers of one station (2 phases x 8 samples = 8 ds_read2st64_b32) are inline asm with
@@ -757,8 +615,6 @@ __global__ __launch_bounds__(64 * WPB, WPB >= 16 ? WPB / 4 : (WPB * 2 + 3) / 4) 
         const unsigned lds_lu = (unsigned)(size_t)lds_l;
 #define BP_RD2(dst, addr, o0, o1) \
     asm volatile("ds_read2st64_b32 %0, %1 offset0:" #o0 " offset1:" #o1 : "=v"(dst) : "v"(addr))
-#define BP_PKFMA(acc2, b2, x2) \
-    asm volatile("v_pk_fma_f32 %0, %1, %2, %0" : "+v"(acc2) : "v"(b2), "v"(x2))
 #define BP_PKFMA_S(acc2, sp2, x2)                                                      \
     asm volatile("v_pk_fma_f32 %0, %1, %2, %0 op_sel:[1,0,0] op_sel_hi:[1,1,1]"        \
                  : "+v"(acc2) : "s"(sp2), "v"(x2))
@@ -799,10 +655,7 @@ __global__ __launch_bounds__(64 * WPB, WPB >= 16 ? WPB / 4 : (WPB * 2 + 3) / 4) 
             for (int u = 0; u < AH; ++u) BP_ISSUE_U(u)
 #pragma unroll
             for (int u = 0; u < NU; ++u) {
-                f32x2 bb;
-                i32x2 sp;
-                if constexpr (SPAIR) { sp = m.pair(u >> 1); }
-                else { const float beta = m.beta(u >> 1); bb[0] = beta; bb[1] = beta; }
+                const i32x2 sp = m.pair(u >> 1);
                 if (u + AH < NU) BP_ISSUE_U(u + AH)
                 const int left = NU - 1 - u < AH ? NU - 1 - u : AH;  // units that may stay in flight
                 if (left == 3) asm volatile("s_waitcnt lgkmcnt(12)" ::: "memory");
@@ -810,19 +663,17 @@ __global__ __launch_bounds__(64 * WPB, WPB >= 16 ? WPB / 4 : (WPB * 2 + 3) / 4) 
                 else if (left == 1) asm volatile("s_waitcnt lgkmcnt(4)" ::: "memory");
                 else asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
 #pragma unroll
-                for (int jj = 0; jj < 4; ++jj) {  // phase P then phase S of a station, as the oracle
-                    if constexpr (SPAIR) BP_PKFMA_S(ac[jj], sp, X[u & 3][jj]);
-                    else BP_PKFMA(ac[jj], bb, X[u & 3][jj]);
-                }
+                for (int jj = 0; jj < 4; ++jj)  // phase P then phase S of a station, as the oracle
+                    BP_PKFMA_S(ac[jj], sp, X[u & 3][jj]);
             }
 #undef BP_ISSUE_U
 #pragma unroll
             for (int jj = 0; jj < 4; ++jj) { acc[2 * jj] = ac[jj][0]; acc[2 * jj + 1] = ac[jj][1]; }
         };
-        // k_next >= 0 (SMETA): refill m with that source once its own gathers are done
-        constexpr int NS = SMETA ? (NSV < 16 ? NSV : 16) : NSV;  // stations per gather() call
-        auto process = [&](Meta& m, bool live, int k_cur, int k_next) {
-            const int nsta = live ? __builtin_amdgcn_readfirstlane(m.nsta()) : 0;
+        // k_next: refill m with that source once its own gathers are done
+        constexpr int NS = Meta::NS;  // stations per gather() call
+        auto process = [&](Meta& m, int k_cur, int k_next) {
+            const int nsta = __builtin_amdgcn_readfirstlane(m.nsta());
             const int sid = m.id(), tmin = m.tmin(), tmax = m.tmax();
             float acc[TPW];
 #pragma unroll
@@ -839,7 +690,7 @@ __global__ __launch_bounds__(64 * WPB, WPB >= 16 ? WPB / 4 : (WPB * 2 + 3) / 4) 
                 constexpr std::true_type first_c{};
                 BP_SWITCH((nsta < NS ? nsta : NS) >> 1)
             }
-            if constexpr (SMETA && NSV > NS) {  // more than 16 stations: refill the set, keep summing
+            if constexpr (NSV > NS) {  // more than 16 stations: refill the set, keep summing
                 constexpr std::false_type first_c{};
                 for (int part = 1; part * NS < nsta; ++part) {
                     m.issue_part(recs, k_cur, part);
@@ -850,7 +701,7 @@ __global__ __launch_bounds__(64 * WPB, WPB >= 16 ? WPB / 4 : (WPB * 2 + 3) / 4) 
             }
 #undef BP_SWITCH
 #undef BP_CASE
-            if constexpr (SMETA) m.issue(srcs4, recs, k_next);
+            m.issue(srcs4, recs, k_next);
             // strict bounds as a wave-uniform window [lo, hi) of the tile: 0 <= t + tmin and
             // t + tmax < N with t = t0 + x
             int lo = 0, hi = TILE;
@@ -884,23 +735,14 @@ __global__ __launch_bounds__(64 * WPB, WPB >= 16 ? WPB / 4 : (WPB * 2 + 3) / 4) 
                         arg[j] = take ? sid : arg[j];
                     } else {
                         const long long t = t0 + x;
-                        if (live && t < N)
+                        if (t < N)
                             out_beam[(size_t)(sid - id_offset) * (size_t)N + t] = computed ? acc[j] : 0.0f;
                     }
                 }
             }
-            if constexpr (SMETA) m.wait();
+            m.wait();
         };
-        if constexpr (SMETA) {
-            for (int k = k_first; k <= k_last; k += WPB) process(m0, true, k, min(k + WPB, k_last));
-        } else {
-            for (int k = k_first; k <= k_last; k += 2 * WPB) {
-                m1.load(srcs4, recs, min(k + WPB, k_last), vzero);
-                process(m0, true, k, -1);
-                m0.load(srcs4, recs, min(k + 2 * WPB, k_last), vzero);
-                process(m1, k + WPB <= k_last, k + WPB, -1);
-            }
-        }
+        for (int k = k_first; k <= k_last; k += WPB) process(meta, k, min(k + WPB, k_last));
         if constexpr (GLOCAL) {
 #pragma unroll
             for (int j = 0; j < TPW; ++j) {
@@ -912,7 +754,6 @@ __global__ __launch_bounds__(64 * WPB, WPB >= 16 ? WPB / 4 : (WPB * 2 + 3) / 4) 
 #undef BP_RD2
 #undef BP_PKFMA_S
 #undef BP_RD64
-#undef BP_PKFMA
     }
     if (REDUCE == BPMF_BP_REDUCE_MAX) {
         __syncthreads();
@@ -1693,8 +1534,7 @@ extern "C" int bpmf_bp_plan_create(const int32_t* moveouts, const float* w_sourc
     // groups fit the LDS with the lowest modelled cost; one 17-station source no longer moves a
     // whole grid off the fast path, and dense 20- or 40-station weights run it on the small tiles.
     std::vector<ClassHost> classes;
-    const bool want_dual = P == 2 && option(OPT_BP_DUAL) && option(OPT_BP_PACKED) &&
-                           option(OPT_BP_WPS) && tpt_first == 2;
+    const bool want_dual = P == 2 && option(OPT_BP_DUAL) && tpt_first == 2;
     if (want_dual && any_src && max_sta <= 64) {
         static const int bound[4] = {0, 16, 32, 64};
         static const int cand[3][3] = {{512, 256, 128}, {256, 128, 0}, {128, 0, 0}};
@@ -1780,10 +1620,7 @@ extern "C" int bpmf_bp_plan_create(const int32_t* moveouts, const float* w_sourc
         tpt = 2;
         dual = true;
     } else {
-        const int candidates[3] = {tpt_first, 2, 1};
-        for (int c = 0; c < 3 && !tpt; ++c) {
-            const int cnd = candidates[c];
-            if (cnd != 1 && cnd != 2 && cnd != 4) continue;
+        for (int cnd = tpt_first; cnd >= 1 && !tpt; --cnd) {   // tile 256 x bp.tpt, then 256
             ph_own = PlanHost();
             if (build_plan(moveouts, w_sources, order, S, P, BP_THREADS * cnd, chunk, soft, hard,
                            max_group, source_id_offset, false, ph_own))
@@ -1824,7 +1661,6 @@ extern "C" int bpmf_bp_plan_create(const int32_t* moveouts, const float* w_sourc
         pl->id_offset = source_id_offset;
         pl->tmin_all = tmin_all;
         pl->tmax_all = tmax_all;
-        pl->wps = 0;
         if (verbose)
             fprintf(stderr, "[bpmf] bp plan: K=%zu, no LDS plan (%s): global-memory gathers over %zu terms\n", K,
                     !tpt ? "windows exceed the LDS" : (ph.NT > 256 ? "> 256 terms per source" : "bp.direct"),
@@ -1853,22 +1689,8 @@ extern "C" int bpmf_bp_plan_create(const int32_t* moveouts, const float* w_sourc
                 K, pl->n_groups, pl->mean_group, BP_THREADS * tpt, pl->NT, chunk, pl->lds_bytes, (int)dual,
                 classes.size());
     int rc = 0;
-    // fast-path copy of the term table: {byte offset, weight} pairs padded to ntv per source
-    const int ntv_opts[4] = {8, 16, 24, 32};
-    const bool want_uv = option(OPT_BP_UVGPR) != 0;
-    pl->wps = (int)option(OPT_BP_WPS);
-    std::vector<BpTermV> tv;
-    for (int o = 0; o < 4 && want_uv && !pl->ntv; ++o)
-        if (ph.NT <= ntv_opts[o]) pl->ntv = ntv_opts[o];
-    if (pl->ntv) {
-        tv.assign(K * (size_t)pl->ntv, BpTermV{0, 0.0f});
-        for (size_t q = 0; q < K; ++q)
-            for (int j = 0; j < ph.NT; ++j)
-                tv[q * pl->ntv + j] = BpTermV{ph.off[q * ph.NT + j] * 4, ph.beta[q * ph.NT + j]};
-        if ((rc = upload(tv, (BpTermV**)&pl->d_termsv))) { bpmf_bp_plan_destroy(pl); return rc; }
-    }
     // packed per-station records for the two-phase kernel
-    if (P == 2 && ph.NT <= 64 && option(OPT_BP_PACKED)) {
+    if (P == 2 && ph.NT <= 64) {
         const int nsta_max = ph.NT / 2;   // NT is a multiple of 4
         const int opts[5] = {4, 8, 12, 16, 32};
         for (int o = 0; o < 5 && !pl->nsv; ++o)
@@ -1893,6 +1715,16 @@ extern "C" int bpmf_bp_plan_create(const int32_t* moveouts, const float* w_sourc
             bpmf_bp_plan_destroy(pl);
             return rc;
         }
+    }
+    // the per-term table of bp_beam_wps_kernel (tile 512 without packed records, <= 32 terms per
+    // source): {byte offset, weight} pairs padded to ntv per source
+    if (tpt == 2 && !pl->nsv && ph.NT <= 32) {
+        pl->ntv = (ph.NT + 7) / 8 * 8;
+        std::vector<BpTermV> tv(K * (size_t)pl->ntv, BpTermV{0, 0.0f});
+        for (size_t q = 0; q < K; ++q)
+            for (int j = 0; j < ph.NT; ++j)
+                tv[q * pl->ntv + j] = BpTermV{ph.off[q * ph.NT + j] * 4, ph.beta[q * ph.NT + j]};
+        if ((rc = upload(tv, (BpTermV**)&pl->d_termsv))) { bpmf_bp_plan_destroy(pl); return rc; }
     }
     // interior-tile classes
     if (use_fast) {
@@ -1980,8 +1812,8 @@ extern "C" int bpmf_bp_plan_info(const bpmf_bp_plan* pl, bpmf_bp_plan_stats* out
     out->tile = BP_THREADS * pl->tpt;
     out->lds_bytes = (int32_t)pl->lds_bytes;
     out->gather_bytes = pl->dual ? 8 : 4;
-    out->stations_max = pl->wps ? pl->nsv : 0;
-    const bool packed = pl->wps && pl->nsv && pl->tpt == 2;
+    out->stations_max = pl->nsv;
+    const bool packed = pl->nsv && pl->tpt == 2;
     out->waves_per_cu = !packed ? 8 : (pl->nsv > 16 ? 16 : (pl->dual ? 16 : 24));
     // reduce="max": the interior tiles run the classes of bp_fast.hip (8-byte gathers, 16 waves per CU);
     // tile / n_groups then describe the class that holds most sources
@@ -2015,8 +1847,7 @@ namespace {
 // option bp.split: 0/1 = off, n = force n ranges (tests), -1 = automatic.  Only the P = 2 packed kernels take it.
 bool generic_can_split(const bpmf_bp_plan* pl)
 {
-    if (pl->tpt != 2 || !pl->wps || pl->n_groups < 2) return false;
-    return pl->nsv == 4 || pl->nsv == 8 || pl->nsv == 12 || pl->nsv == 16 || pl->nsv == 32;   // dispatch_beam<2>'s packed kernels
+    return pl->tpt == 2 && pl->nsv && pl->n_groups >= 2;   // (dispatch_beam's packed kernels)
 }
 
 // `forced` = option bp.split as the CALLER read it (once per call: the size check of the workspace and the
@@ -2078,238 +1909,135 @@ extern "C" size_t bpmf_bp_workspace_bytes(const bpmf_bp_plan* pl, size_t N, size
 
 namespace {
 
-// The caller (interior / edge split of bpmf_bp_run_dev) may restrict a launch of the general kernels
-// to the samples [t_samp_lo, t_samp_hi) -- multiples of 1024, i.e. whole tiles of every kernel -- and
-// then places the profile marks itself.  t_samp_hi < 0: the whole series.
-thread_local long long t_samp_lo = 0, t_samp_hi = -1;
-thread_local int t_n_split = 1;                  // group ranges per tile (short series, see bp_split_count)
-thread_local long long t_split_stride = 0;       // elements between the partial outputs of reduce="max"
-// start value of the running maximum: 0 (the build's convention: a beam that is not > 0 never
-// becomes the maximum) or -inf (option bp.compat_first_computed: the maximum over the computed
-// beams whatever their sign; samples without any computed beam are set to (0, first id) at the end)
-thread_local float t_best0 = 0.0f;
-}  // namespace
-namespace bpmf { thread_local bool t_bp_defer_finish = false; }
-namespace {
+// Launch values of the general kernels.  The caller (interior / edge split of bp_run_dev) may restrict a
+// launch to the samples [samp_lo, samp_hi) -- multiples of 1024, i.e. whole tiles of every kernel -- and
+// then places the profile marks itself; samp_hi < 0: the whole series.
+struct BpLaunch {
+    long long samp_lo = 0, samp_hi = -1;
+    int n_split = 1;                 // group ranges per tile (short series, see bp_split_count)
+    long long split_stride = 0;      // elements between the partial outputs of reduce="max"
+    // start value of the running maximum: 0 (the build's convention: a beam that is not > 0 never
+    // becomes the maximum) or -inf (option bp.compat_first_computed: the maximum over the computed
+    // beams whatever their sign; samples without any computed beam are set to (0, first id) at the end)
+    float best0 = 0.0f;
+};
 
 // tiles [base, base + count) of a kernel with `tile` samples per workgroup
-inline void tile_range(size_t N, size_t tile, long long& base, long long& count)
+void tile_range(size_t N, size_t tile, const BpLaunch& lc, long long& base, long long& count)
 {
     base = 0;
     count = (long long)((N + tile - 1) / tile);
-    if (t_samp_hi >= 0) {
-        const long long hi = std::min<long long>(t_samp_hi, (long long)N);
-        base = t_samp_lo / (long long)tile;
-        count = hi > t_samp_lo ? (hi + (long long)tile - 1) / (long long)tile - base : 0;
+    if (lc.samp_hi >= 0) {
+        const long long hi = std::min<long long>(lc.samp_hi, (long long)N);
+        base = lc.samp_lo / (long long)tile;
+        count = hi > lc.samp_lo ? (hi + (long long)tile - 1) / (long long)tile - base : 0;
     }
 }
 
-template <int TPT, int CHUNK, int NBLK, int OOB, int REDUCE>
-int launch_beam(const bpmf_bp_plan* pl, const float* U, size_t N, hipStream_t stream, float* beam,
-                int32_t* arg)
+// What every launch of a general kernel does around the kernel itself: more than 64 KB of dynamic LDS
+// where needed, the tiles of lc's samples, profile marks around a whole-series launch, the launch check.
+// enqueue(tile_base, n_tiles) launches the kernel.
+template <typename Kernel, typename Enqueue>
+int launch_general(Kernel kern, size_t lds, size_t tile, size_t N, const BpLaunch& lc, hipStream_t stream,
+                   Enqueue enqueue)
 {
-    auto kern = bp_beam_kernel<TPT, CHUNK, NBLK, OOB, REDUCE>;
-    if (pl->lds_bytes > 64 * 1024)
-        BPMF_HIP_CHECK(hipFuncSetAttribute((const void*)kern,
-                                           hipFuncAttributeMaxDynamicSharedMemorySize,
-                                           (int)BP_LDS_MAX));
-    long long tile_base, n_tiles;
-    tile_range(N, (size_t)BP_THREADS * TPT, tile_base, n_tiles);
-    if (n_tiles <= 0) return 0;
-    dim3 grid((unsigned)n_tiles);
-    if (t_samp_hi < 0) profile_mark(BPMF_KERNEL_BP_BEAM, 0, stream);
-    kern<<<grid, dim3(BP_THREADS), pl->lds_bytes, stream>>>(
-        U, (long long)N, pl->d_groups, pl->n_groups, (const int4*)pl->d_chunks,
-        (const int*)pl->d_srcs, pl->d_off, pl->d_beta, pl->NT, pl->id_offset, beam, arg, tile_base, t_best0);
-    BPMF_LAUNCH_CHECK();
-    if (t_samp_hi < 0) profile_mark(BPMF_KERNEL_BP_BEAM, 1, stream);
-    return 0;
-}
-
-template <int TPT, int CHUNK, int NBLK>
-int dispatch_beam3(const bpmf_bp_plan* pl, const float* U, size_t N, int oob, int reduce,
-                   hipStream_t stream, float* beam, int32_t* arg)
-{
-    if (oob == BPMF_BP_STRICT && reduce == BPMF_BP_REDUCE_MAX)
-        return launch_beam<TPT, CHUNK, NBLK, BPMF_BP_STRICT, BPMF_BP_REDUCE_MAX>(pl, U, N, stream, beam, arg);
-    if (oob == BPMF_BP_FLEXIBLE && reduce == BPMF_BP_REDUCE_MAX)
-        return launch_beam<TPT, CHUNK, NBLK, BPMF_BP_FLEXIBLE, BPMF_BP_REDUCE_MAX>(pl, U, N, stream, beam, arg);
-    if (oob == BPMF_BP_STRICT)
-        return launch_beam<TPT, CHUNK, NBLK, BPMF_BP_STRICT, BPMF_BP_REDUCE_NONE>(pl, U, N, stream, beam, arg);
-    return launch_beam<TPT, CHUNK, NBLK, BPMF_BP_FLEXIBLE, BPMF_BP_REDUCE_NONE>(pl, U, N, stream, beam, arg);
-}
-
-template <int TPT, int CHUNK>
-int dispatch_beam2(const bpmf_bp_plan* pl, const float* U, size_t N, int oob, int reduce,
-                   hipStream_t stream, float* beam, int32_t* arg)
-{
-    if (pl->NT <= 64) return dispatch_beam3<TPT, CHUNK, 1>(pl, U, N, oob, reduce, stream, beam, arg);
-    if (pl->NT <= 128) return dispatch_beam3<TPT, CHUNK, 2>(pl, U, N, oob, reduce, stream, beam, arg);
-    return dispatch_beam3<TPT, CHUNK, 4>(pl, U, N, oob, reduce, stream, beam, arg);
-}
-
-template <int TPT, int NTV, int OOB, int REDUCE>
-int launch_beam_uv(const bpmf_bp_plan* pl, const float* U, size_t N, hipStream_t stream,
-                   float* beam, int32_t* arg)
-{
-    auto kern = bp_beam_uvgpr_kernel<TPT, NTV, OOB, REDUCE>;
-    if (pl->lds_bytes > 64 * 1024)
-        BPMF_HIP_CHECK(hipFuncSetAttribute((const void*)kern,
-                                           hipFuncAttributeMaxDynamicSharedMemorySize,
-                                           (int)BP_LDS_MAX));
-    long long tile_base, n_tiles;
-    tile_range(N, (size_t)BP_THREADS * TPT, tile_base, n_tiles);
-    if (n_tiles <= 0) return 0;
-    dim3 grid((unsigned)n_tiles);
-    if (t_samp_hi < 0) profile_mark(BPMF_KERNEL_BP_BEAM, 0, stream);
-    kern<<<grid, dim3(BP_THREADS), pl->lds_bytes, stream>>>(
-        U, (long long)N, pl->d_groups, pl->n_groups, (const int4*)pl->d_chunks,
-        (const int4*)pl->d_srcs, (const int4*)pl->d_termsv, pl->id_offset, beam, arg, tile_base, t_best0);
-    BPMF_LAUNCH_CHECK();
-    if (t_samp_hi < 0) profile_mark(BPMF_KERNEL_BP_BEAM, 1, stream);
-    return 0;
-}
-
-template <int TPT, int NTV>
-int dispatch_beam_uv(const bpmf_bp_plan* pl, const float* U, size_t N, int oob, int reduce,
-                     hipStream_t stream, float* beam, int32_t* arg)
-{
-    if (oob == BPMF_BP_STRICT && reduce == BPMF_BP_REDUCE_MAX)
-        return launch_beam_uv<TPT, NTV, BPMF_BP_STRICT, BPMF_BP_REDUCE_MAX>(pl, U, N, stream, beam, arg);
-    if (oob == BPMF_BP_FLEXIBLE && reduce == BPMF_BP_REDUCE_MAX)
-        return launch_beam_uv<TPT, NTV, BPMF_BP_FLEXIBLE, BPMF_BP_REDUCE_MAX>(pl, U, N, stream, beam, arg);
-    if (oob == BPMF_BP_STRICT)
-        return launch_beam_uv<TPT, NTV, BPMF_BP_STRICT, BPMF_BP_REDUCE_NONE>(pl, U, N, stream, beam, arg);
-    return launch_beam_uv<TPT, NTV, BPMF_BP_FLEXIBLE, BPMF_BP_REDUCE_NONE>(pl, U, N, stream, beam, arg);
-}
-
-template <int TPW, int NTV, int OOB, int REDUCE>
-int launch_beam_wps(const bpmf_bp_plan* pl, const float* U, size_t N, hipStream_t stream,
-                    float* beam, int32_t* arg)
-{
-    auto kern = bp_beam_wps_kernel<TPW, NTV, OOB, REDUCE>;
-    // the end-of-kernel merge needs 2 * 4 * tile floats of LDS
-    const size_t lds = std::max(pl->lds_bytes, (size_t)8 * 64 * TPW * sizeof(float));
     if (lds > 64 * 1024)
-        BPMF_HIP_CHECK(hipFuncSetAttribute((const void*)kern,
-                                           hipFuncAttributeMaxDynamicSharedMemorySize,
+        BPMF_HIP_CHECK(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize,
                                            (int)BP_LDS_MAX));
     long long tile_base, n_tiles;
-    tile_range(N, (size_t)64 * TPW, tile_base, n_tiles);
+    tile_range(N, tile, lc, tile_base, n_tiles);
     if (n_tiles <= 0) return 0;
-    dim3 grid((unsigned)n_tiles);
-    if (t_samp_hi < 0) profile_mark(BPMF_KERNEL_BP_BEAM, 0, stream);
-    kern<<<grid, dim3(BP_THREADS), lds, stream>>>(
-        U, (long long)N, pl->d_groups, pl->n_groups, (const int4*)pl->d_chunks,
-        (const int4*)pl->d_srcs, (const int4*)pl->d_termsv, pl->id_offset, beam, arg, tile_base, t_best0);
+    if (lc.samp_hi < 0) profile_mark(BPMF_KERNEL_BP_BEAM, 0, stream);
+    enqueue(tile_base, n_tiles);
     BPMF_LAUNCH_CHECK();
-    if (t_samp_hi < 0) profile_mark(BPMF_KERNEL_BP_BEAM, 1, stream);
+    if (lc.samp_hi < 0) profile_mark(BPMF_KERNEL_BP_BEAM, 1, stream);
     return 0;
 }
 
-template <int TPW, int NTV>
-int dispatch_beam_wps(const bpmf_bp_plan* pl, const float* U, size_t N, int oob, int reduce,
-                      hipStream_t stream, float* beam, int32_t* arg)
+template <int V>
+using IntC = std::integral_constant<int, V>;
+
+// f(oob, reduce) with both codes as IntC: the one place where they become template arguments
+template <typename F>
+int with_oob_reduce(int oob, int reduce, F f)
 {
-    if (oob == BPMF_BP_STRICT && reduce == BPMF_BP_REDUCE_MAX)
-        return launch_beam_wps<TPW, NTV, BPMF_BP_STRICT, BPMF_BP_REDUCE_MAX>(pl, U, N, stream, beam, arg);
-    if (oob == BPMF_BP_FLEXIBLE && reduce == BPMF_BP_REDUCE_MAX)
-        return launch_beam_wps<TPW, NTV, BPMF_BP_FLEXIBLE, BPMF_BP_REDUCE_MAX>(pl, U, N, stream, beam, arg);
-    if (oob == BPMF_BP_STRICT)
-        return launch_beam_wps<TPW, NTV, BPMF_BP_STRICT, BPMF_BP_REDUCE_NONE>(pl, U, N, stream, beam, arg);
-    return launch_beam_wps<TPW, NTV, BPMF_BP_FLEXIBLE, BPMF_BP_REDUCE_NONE>(pl, U, N, stream, beam, arg);
+    if (reduce == BPMF_BP_REDUCE_MAX)
+        return oob == BPMF_BP_STRICT ? f(IntC<BPMF_BP_STRICT>{}, IntC<BPMF_BP_REDUCE_MAX>{})
+                                     : f(IntC<BPMF_BP_FLEXIBLE>{}, IntC<BPMF_BP_REDUCE_MAX>{});
+    return oob == BPMF_BP_STRICT ? f(IntC<BPMF_BP_STRICT>{}, IntC<BPMF_BP_REDUCE_NONE>{})
+                                 : f(IntC<BPMF_BP_FLEXIBLE>{}, IntC<BPMF_BP_REDUCE_NONE>{});
 }
 
-template <int WPB, int NSV, int OOB, int REDUCE, bool SMETA, bool B64>
-int launch_beam_wps2(const bpmf_bp_plan* pl, const float* U, size_t N, hipStream_t stream,
-                     float* beam, int32_t* arg)
-{
-    auto kern = bp_beam_wps2_kernel<WPB, NSV, OOB, REDUCE, SMETA, B64>;
-    const size_t lds = std::max(pl->lds_bytes, (size_t)2 * WPB * 512 * sizeof(float));
-    if (lds > 64 * 1024)
-        BPMF_HIP_CHECK(hipFuncSetAttribute((const void*)kern,
-                                           hipFuncAttributeMaxDynamicSharedMemorySize,
-                                           (int)BP_LDS_MAX));
-    long long tile_base, n_tiles;
-    tile_range(N, 512, tile_base, n_tiles);
-    if (n_tiles <= 0) return 0;
-    dim3 grid((unsigned)((n_tiles + 7) / 8 * 8), (unsigned)t_n_split);  // x: multiple of 8 (XCD-aware tile order)
-    if (t_samp_hi < 0) profile_mark(BPMF_KERNEL_BP_BEAM, 0, stream);
-    kern<<<grid, dim3(64 * WPB), lds, stream>>>(U, (long long)N, pl->d_groups, pl->n_groups,
-                                                (const int4*)pl->d_chunks, pl->d_hdr2, pl->d_recs,
-                                                pl->id_offset, beam, arg, tile_base, n_tiles,
-                                                t_split_stride, t_best0);
-    BPMF_LAUNCH_CHECK();
-    if (t_samp_hi < 0) profile_mark(BPMF_KERNEL_BP_BEAM, 1, stream);
-    return 0;
-}
-
-template <int WPB, int NSV, bool SMETA, bool B64 = false>
-int dispatch_beam_wps2b(const bpmf_bp_plan* pl, const float* U, size_t N, int oob, int reduce,
-                        hipStream_t stream, float* beam, int32_t* arg)
-{
-    if (oob == BPMF_BP_STRICT && reduce == BPMF_BP_REDUCE_MAX)
-        return launch_beam_wps2<WPB, NSV, BPMF_BP_STRICT, BPMF_BP_REDUCE_MAX, SMETA, B64>(pl, U, N, stream, beam, arg);
-    if (oob == BPMF_BP_FLEXIBLE && reduce == BPMF_BP_REDUCE_MAX)
-        return launch_beam_wps2<WPB, NSV, BPMF_BP_FLEXIBLE, BPMF_BP_REDUCE_MAX, SMETA, B64>(pl, U, N, stream, beam, arg);
-    if (oob == BPMF_BP_STRICT)
-        return launch_beam_wps2<WPB, NSV, BPMF_BP_STRICT, BPMF_BP_REDUCE_NONE, SMETA, B64>(pl, U, N, stream, beam, arg);
-    return launch_beam_wps2<WPB, NSV, BPMF_BP_FLEXIBLE, BPMF_BP_REDUCE_NONE, SMETA, B64>(pl, U, N, stream, beam, arg);
-}
-
-template <int NSV>
-int dispatch_beam_wps2(const bpmf_bp_plan* pl, const float* U, size_t N, int oob, int reduce,
-                       hipStream_t stream, float* beam, int32_t* arg)
-{
-    // NSV <= 16: metadata in SGPRs, 12 waves per workgroup, 2 workgroups (24 waves) per CU --
-    // ds_read_b32-class gathers need >= 4 waves/SIMD to reach the LDS rate.  Above 16 stations
-    // the SGPR set no longer fits and the VGPR-metadata variant (8 waves/CU) runs.
-    const int wpb = (int)option(OPT_BP_WPB);
-    if constexpr (NSV <= 16) {
-        if (pl->dual) return dispatch_beam_wps2b<16, NSV, true, true>(pl, U, N, oob, reduce, stream, beam, arg);
-        if (wpb == 8) return dispatch_beam_wps2b<8, NSV, true>(pl, U, N, oob, reduce, stream, beam, arg);
-        return dispatch_beam_wps2b<12, NSV, true>(pl, U, N, oob, reduce, stream, beam, arg);
-    }
-    const int smeta = (int)option(OPT_BP_SMETA);
-    if constexpr (NSV % 16 == 0) {
-        if (smeta) return dispatch_beam_wps2b<16, NSV, true>(pl, U, N, oob, reduce, stream, beam, arg);
-    }
-    return dispatch_beam_wps2b<4, NSV, false>(pl, U, N, oob, reduce, stream, beam, arg);
-}
-
-template <int TPT>
-int dispatch_beam(const bpmf_bp_plan* pl, const float* U, size_t N, int oob, int reduce,
+// The general kernel of a plan over lc's samples: packed per-station records (P = 2, tile 512), else the
+// per-term table (<= 32 terms per source, tile 512), else the readlane kernel (any plan, tile 256 x tpt).
+int dispatch_beam(const bpmf_bp_plan* pl, const float* U, size_t N, int oob, int reduce, const BpLaunch& lc,
                   hipStream_t stream, float* beam, int32_t* arg)
 {
-    if (pl->wps && pl->nsv && TPT == 2) {  // packed two-phase kernel, 16 waves/CU
-        switch (pl->nsv) {
-            case 4: return dispatch_beam_wps2<4>(pl, U, N, oob, reduce, stream, beam, arg);
-            case 8: return dispatch_beam_wps2<8>(pl, U, N, oob, reduce, stream, beam, arg);
-            case 12: return dispatch_beam_wps2<12>(pl, U, N, oob, reduce, stream, beam, arg);
-            case 16: return dispatch_beam_wps2<16>(pl, U, N, oob, reduce, stream, beam, arg);
-            case 32: return dispatch_beam_wps2<32>(pl, U, N, oob, reduce, stream, beam, arg);
-            default: break;
+    return with_oob_reduce(oob, reduce, [&](auto oob_c, auto reduce_c) -> int {
+        constexpr int OOB = decltype(oob_c)::value, REDUCE = decltype(reduce_c)::value;
+        auto wps2 = [&](auto wpb_c, auto nsv_c, auto b64_c) -> int {
+            constexpr int WPB = decltype(wpb_c)::value;
+            auto kern = bp_beam_wps2_kernel<WPB, decltype(nsv_c)::value, OOB, REDUCE, decltype(b64_c)::value>;
+            const size_t lds = std::max(pl->lds_bytes, (size_t)2 * WPB * 512 * sizeof(float));
+            return launch_general(kern, lds, 512, N, lc, stream, [&](long long tile_base, long long n_tiles) {
+                // x: a multiple of 8 (XCD-aware tile order), y: group ranges
+                kern<<<dim3((unsigned)((n_tiles + 7) / 8 * 8), (unsigned)lc.n_split), dim3(64 * WPB), lds, stream>>>(
+                    U, (long long)N, pl->d_groups, pl->n_groups, (const int4*)pl->d_chunks, pl->d_hdr2, pl->d_recs,
+                    pl->id_offset, beam, arg, tile_base, n_tiles, lc.split_stride, lc.best0);
+            });
+        };
+        auto wps = [&](auto ntv_c) -> int {
+            auto kern = bp_beam_wps_kernel<8, decltype(ntv_c)::value, OOB, REDUCE>;
+            // the end-of-kernel merge needs 2 * 4 * tile floats of LDS
+            const size_t lds = std::max(pl->lds_bytes, (size_t)8 * 512 * sizeof(float));
+            return launch_general(kern, lds, 512, N, lc, stream, [&](long long tile_base, long long n_tiles) {
+                kern<<<dim3((unsigned)n_tiles), dim3(BP_THREADS), lds, stream>>>(
+                    U, (long long)N, pl->d_groups, pl->n_groups, (const int4*)pl->d_chunks, (const int4*)pl->d_srcs,
+                    (const int4*)pl->d_termsv, pl->id_offset, beam, arg, tile_base, lc.best0);
+            });
+        };
+        auto readlane = [&](auto tpt_c, auto nblk_c) -> int {
+            constexpr int TPT = decltype(tpt_c)::value;
+            auto kern = bp_beam_kernel<TPT, 4, decltype(nblk_c)::value, OOB, REDUCE>;
+            return launch_general(kern, pl->lds_bytes, (size_t)BP_THREADS * TPT, N, lc, stream,
+                                  [&](long long tile_base, long long n_tiles) {
+                kern<<<dim3((unsigned)n_tiles), dim3(BP_THREADS), pl->lds_bytes, stream>>>(
+                    U, (long long)N, pl->d_groups, pl->n_groups, (const int4*)pl->d_chunks, (const int*)pl->d_srcs,
+                    pl->d_off, pl->d_beta, pl->NT, pl->id_offset, beam, arg, tile_base, lc.best0);
+            });
+        };
+        if (pl->tpt == 2) {
+            // Packed records of <= 16 stations keep a source's metadata in SGPRs: 16 waves per workgroup with
+            // the 8-byte gathers of a dual plan, 12 (2 workgroups, 24 waves per CU) with 4-byte gathers, which
+            // need >= 4 waves/SIMD to reach the LDS rate.  32 stations: one 16-wave workgroup per CU, the
+            // records gathered in two parts.
+            switch (pl->nsv) {
+                case 4: return pl->dual ? wps2(IntC<16>{}, IntC<4>{}, std::true_type{})
+                                        : wps2(IntC<12>{}, IntC<4>{}, std::false_type{});
+                case 8: return pl->dual ? wps2(IntC<16>{}, IntC<8>{}, std::true_type{})
+                                        : wps2(IntC<12>{}, IntC<8>{}, std::false_type{});
+                case 12: return pl->dual ? wps2(IntC<16>{}, IntC<12>{}, std::true_type{})
+                                         : wps2(IntC<12>{}, IntC<12>{}, std::false_type{});
+                case 16: return pl->dual ? wps2(IntC<16>{}, IntC<16>{}, std::true_type{})
+                                         : wps2(IntC<12>{}, IntC<16>{}, std::false_type{});
+                case 32: return wps2(IntC<16>{}, IntC<32>{}, std::false_type{});
+                default: break;
+            }
+            switch (pl->ntv) {
+                case 8: return wps(IntC<8>{});
+                case 16: return wps(IntC<16>{});
+                case 24: return wps(IntC<24>{});
+                case 32: return wps(IntC<32>{});
+                default: break;
+            }
         }
-    }
-    if (pl->wps && pl->ntv && TPT == 2) {  // wave-per-source layout: tile 512 = 64 lanes x 8
-        switch (pl->ntv) {
-            case 8: return dispatch_beam_wps<8, 8>(pl, U, N, oob, reduce, stream, beam, arg);
-            case 16: return dispatch_beam_wps<8, 16>(pl, U, N, oob, reduce, stream, beam, arg);
-            case 24: return dispatch_beam_wps<8, 24>(pl, U, N, oob, reduce, stream, beam, arg);
-            case 32: return dispatch_beam_wps<8, 32>(pl, U, N, oob, reduce, stream, beam, arg);
-            default: break;
-        }
-    }
-    switch (pl->ntv) {  // uniform-VGPR fast path when every source has <= 32 terms
-        case 8: return dispatch_beam_uv<TPT, 8>(pl, U, N, oob, reduce, stream, beam, arg);
-        case 16: return dispatch_beam_uv<TPT, 16>(pl, U, N, oob, reduce, stream, beam, arg);
-        case 24: return dispatch_beam_uv<TPT, 24>(pl, U, N, oob, reduce, stream, beam, arg);
-        case 32: return dispatch_beam_uv<TPT, 32>(pl, U, N, oob, reduce, stream, beam, arg);
-        default: break;
-    }
-    return dispatch_beam2<TPT, 4>(pl, U, N, oob, reduce, stream, beam, arg);
+        // blocks of 64 terms per source: 1, 2 or 4
+        const bool t1 = pl->tpt == 1;
+        if (pl->NT <= 64) return t1 ? readlane(IntC<1>{}, IntC<1>{}) : readlane(IntC<2>{}, IntC<1>{});
+        if (pl->NT <= 128) return t1 ? readlane(IntC<1>{}, IntC<2>{}) : readlane(IntC<2>{}, IntC<2>{});
+        return t1 ? readlane(IntC<1>{}, IntC<4>{}) : readlane(IntC<2>{}, IntC<4>{});
+    });
 }
-
 
 // prestack of the samples [t_lo, t_hi)
 int launch_prestack(const float* d_features, const float* d_w_phases, size_t N, size_t C, int S, int P, float* U,
@@ -2337,16 +2065,14 @@ struct BpFeed {
     virtual int need(long long samp_end, hipStream_t stream) = 0;
     virtual ~BpFeed() {}
 };
-thread_local BpFeed* t_bp_feed = nullptr;
 
-}  // namespace
-
-extern "C" int bpmf_bp_run_dev(const bpmf_bp_plan* pl, const float* d_features,
-                               const float* d_w_phases, size_t N, size_t C, int out_of_bounds,
-                               int reduce, void* d_workspace, size_t workspace_bytes,
-                               bpmf_stream_t stream_, float* d_beam_out, int32_t* d_arg_out)
+// bpmf_bp_run_dev, and a host-pointer call's run on the device: `feed` (not null: the day of features is still
+// arriving, see BpFeed) and `defer_finish` (option bp.compat_first_computed: samples without any computed beam
+// keep -inf; bpmf_bp_run_multi finishes them after the merge of all devices' shares)
+int bp_run_dev(const bpmf_bp_plan* pl, const float* d_features, const float* d_w_phases, size_t N, size_t C,
+               int out_of_bounds, int reduce, void* d_workspace, size_t workspace_bytes, hipStream_t stream,
+               float* d_beam_out, int32_t* d_arg_out, BpFeed* feed, bool defer_finish)
 {
-    hipStream_t stream = (hipStream_t)stream_;
     if (!pl || !d_features || !d_w_phases || !d_workspace || !d_beam_out || N == 0 || C == 0) {
         set_error("bpmf_bp_run_dev: bad argument");
         return -1;
@@ -2382,7 +2108,6 @@ extern "C" int bpmf_bp_run_dev(const bpmf_bp_plan* pl, const float* d_features,
     // A host-pointer call may stream its day of features in while the kernels run (BpFeed, bpmf_bp_run):
     // the feed uploads AND prestacks piece by piece; only the interior-tile path below consumes it in
     // pieces, every other path asks for the whole series first.
-    BpFeed* feed = t_bp_feed;
     // option bp.host_piece_samples: samples of the first piece (default 131 072 = one round of the chip at tile
     // 512; the tests shrink it), 0 = the whole day in front of the first kernel
     const long long piece0 = (long long)align_up((size_t)option(OPT_BP_HOST_PIECE_SAMPLES), 1024);
@@ -2391,17 +2116,10 @@ extern "C" int bpmf_bp_run_dev(const bpmf_bp_plan* pl, const float* d_features,
         if (int rc = feed->need((long long)N, stream)) return rc;
     if (!feed)
         if (int rc = launch_prestack(d_features, d_w_phases, N, C, S, P, U, 0, (long long)N, stream)) return rc;
-    struct SplitScope {          // the launchers read the thread-local pair; always reset on the way out
-        SplitScope(int n, long long stride) { t_n_split = n; t_split_stride = stride; }
-        ~SplitScope() { t_n_split = 1; t_split_stride = 0; t_samp_hi = -1; t_samp_lo = 0; }
-    };
     const bool first_computed = reduce == BPMF_BP_REDUCE_MAX && option(OPT_BP_COMPAT_FIRST_COMPUTED) != 0;
-    struct Best0Scope {
-        explicit Best0Scope(float v) { t_best0 = v; }
-        ~Best0Scope() { t_best0 = 0.0f; }
-    } best0_scope(first_computed ? -INFINITY : 0.0f);
+    const float best0 = first_computed ? -INFINITY : 0.0f;      // (BpLaunch::best0)
     auto finish = [&](float* beam, int32_t* arg) -> int {
-        if (first_computed && !t_bp_defer_finish) {
+        if (first_computed && !defer_finish) {
             bp_finish_first_computed_kernel<<<dim3((unsigned)((N + 255) / 256)), dim3(256), 0, stream>>>(
                 beam, arg, N, pl->id_offset);
             BPMF_LAUNCH_CHECK();
@@ -2417,7 +2135,7 @@ extern "C" int bpmf_bp_run_dev(const bpmf_bp_plan* pl, const float* d_features,
         float* pbeam = rows > 1 ? (float*)part : beam_final;
         int32_t* parg = rows > 1 ? (int32_t*)(part + (size_t)rows * N * sizeof(float)) : arg_final;
         profile_mark(BPMF_KERNEL_BP_BEAM, 0, stream);
-        int rc = launch_beam_direct(pl, U, N, out_of_bounds, reduce, stream, pbeam, parg, rows, (long long)N, t_best0);
+        int rc = launch_beam_direct(pl, U, N, out_of_bounds, reduce, stream, pbeam, parg, rows, (long long)N, best0);
         if (!rc && rows > 1) {
             bp_merge_splits_kernel<<<dim3((unsigned)((N + 255) / 256)), dim3(256), 0, stream>>>(
                 pbeam, parg, rows, rows, 0, (long long)N, N, beam_final, arg_final);
@@ -2461,18 +2179,12 @@ extern "C" int bpmf_bp_run_dev(const bpmf_bp_plan* pl, const float* d_features,
             BPMF_HIP_CHECK(hipStreamWaitEvent(pl->side_stream, pl->ev_fork, 0));
             es = pl->side_stream;
         }
+        auto edge = [&](long long from, long long to) {
+            if (to > from && !rc)
+                rc = dispatch_beam(pl, U, N, out_of_bounds, reduce,
+                                   BpLaunch{from, to, n_split_edge, rows > 1 ? (long long)N : 0, best0}, es, pbeam, parg);
+        };
         auto run_edges = [&]() {
-            SplitScope scope(n_split_edge, rows > 1 ? (long long)N : 0);
-            auto edge = [&](long long from, long long to) {
-                if (to <= from || rc) return;
-                t_samp_lo = from; t_samp_hi = to;
-                switch (pl->tpt) {
-                    case 1: rc = dispatch_beam<1>(pl, U, N, out_of_bounds, reduce, es, pbeam, parg); break;
-                    case 2: rc = dispatch_beam<2>(pl, U, N, out_of_bounds, reduce, es, pbeam, parg); break;
-                    default: rc = dispatch_beam<4>(pl, U, N, out_of_bounds, reduce, es, pbeam, parg); break;
-                }
-                t_samp_hi = -1;
-            };
             edge(0, lo_s);
             edge(hi_s, (long long)N);
         };
@@ -2515,7 +2227,7 @@ extern "C" int bpmf_bp_run_dev(const bpmf_bp_plan* pl, const float* d_features,
                 const BpFastClass& fc = pl->cls[c];
                 rc = launch_beam_fast(fc, pl->id_offset, U, N, a / fc.tile, b / fc.tile, stream,
                                       pbeam + (size_t)c * n_split * N, parg + (size_t)c * n_split * N, n_split,
-                                      rows > 1 ? (long long)N : 0, t_best0);
+                                      rows > 1 ? (long long)N : 0, best0);
             }
             a = b;
         }
@@ -2533,28 +2245,31 @@ extern "C" int bpmf_bp_run_dev(const bpmf_bp_plan* pl, const float* d_features,
     // the general kernels over the whole series.  Short series: several group ranges per tile
     // (bp_split_count); reduce="max" goes through partial rows and one merge launch
     const int n_split = bp_split_count(pl, N, forced_split);
-    SplitScope split_scope(n_split, n_split > 1 && reduce == BPMF_BP_REDUCE_MAX ? (long long)N : 0);
-    if (n_split > 1 && reduce == BPMF_BP_REDUCE_MAX) {
+    const bool merge = n_split > 1 && reduce == BPMF_BP_REDUCE_MAX;
+    if (merge) {
         d_beam_out = (float*)part;
         d_arg_out = (int32_t*)(part + (size_t)n_split * N * sizeof(float));
     }
-    auto merge_splits = [&]() -> int {
-        if (n_split > 1 && reduce == BPMF_BP_REDUCE_MAX) {
-            bp_merge_splits_kernel<<<dim3((unsigned)((N + 255) / 256)), dim3(256), 0, stream>>>(
-                d_beam_out, d_arg_out, n_split, n_split, 0, (long long)N, N, beam_final, arg_final);
-            BPMF_LAUNCH_CHECK();
-        }
-        return 0;
-    };
-    int rc;
-    switch (pl->tpt) {
-        case 1: rc = dispatch_beam<1>(pl, U, N, out_of_bounds, reduce, stream, d_beam_out, d_arg_out); break;
-        case 2: rc = dispatch_beam<2>(pl, U, N, out_of_bounds, reduce, stream, d_beam_out, d_arg_out); break;
-        default: rc = dispatch_beam<4>(pl, U, N, out_of_bounds, reduce, stream, d_beam_out, d_arg_out); break;
+    int rc = dispatch_beam(pl, U, N, out_of_bounds, reduce, BpLaunch{0, -1, n_split, merge ? (long long)N : 0, best0},
+                           stream, d_beam_out, d_arg_out);
+    if (!rc && merge) {
+        bp_merge_splits_kernel<<<dim3((unsigned)((N + 255) / 256)), dim3(256), 0, stream>>>(
+            d_beam_out, d_arg_out, n_split, n_split, 0, (long long)N, N, beam_final, arg_final);
+        BPMF_LAUNCH_CHECK();
     }
-    if (!rc) rc = merge_splits();
     if (!rc && reduce == BPMF_BP_REDUCE_MAX) rc = finish(beam_final, arg_final);
     return rc;
+}
+
+}  // namespace
+
+extern "C" int bpmf_bp_run_dev(const bpmf_bp_plan* pl, const float* d_features,
+                               const float* d_w_phases, size_t N, size_t C, int out_of_bounds,
+                               int reduce, void* d_workspace, size_t workspace_bytes,
+                               bpmf_stream_t stream, float* d_beam_out, int32_t* d_arg_out)
+{
+    return bp_run_dev(pl, d_features, d_w_phases, N, C, out_of_bounds, reduce, d_workspace, workspace_bytes,
+                      (hipStream_t)stream, d_beam_out, d_arg_out, nullptr, false);
 }
 
 namespace {
@@ -2603,7 +2318,7 @@ size_t plan_cache_capacity()
 static int bpmf_bp_run_impl(const float* features, const int32_t* moveouts, const float* w_phases,
                            const float* w_sources, size_t N, size_t K, size_t S, size_t C, size_t P,
                            int out_of_bounds, int reduce, int device, float* beam_out,
-                           int32_t* arg_out)
+                           int32_t* arg_out, bool defer_finish)
 {
     if (!features || !moveouts || !w_phases || !w_sources || !beam_out) {
         set_error("bpmf_bp_run: null pointer");
@@ -2783,13 +2498,9 @@ static int bpmf_bp_run_impl(const float* features, const int32_t* moveouts, cons
         host_feed.d_wp = (const float*)(base + o_wp); host_feed.U = (float*)(base + o_ws);
         host_feed.N = N; host_feed.C = C; host_feed.S = (int)S; host_feed.P = (int)P; host_feed.t_call0 = t_call0;
         if (from_peer) t_call_stats.first_kernel_ms = host_now_ms() - t_call0;
-        struct FeedScope {
-            explicit FeedScope(BpFeed* f) { t_bp_feed = f; }
-            ~FeedScope() { t_bp_feed = nullptr; }
-        } feed_scope(from_peer ? nullptr : &host_feed);
-        rc = bpmf_bp_run_dev(pl, (const float*)(base + o_f), (const float*)(base + o_wp), N, C,
-                             out_of_bounds, reduce, base + o_ws, b_ws, stream,
-                             (float*)(base + o_beam), (int32_t*)(base + o_arg));
+        rc = bp_run_dev(pl, (const float*)(base + o_f), (const float*)(base + o_wp), N, C, out_of_bounds, reduce,
+                        base + o_ws, b_ws, stream, (float*)(base + o_beam), (int32_t*)(base + o_arg),
+                        from_peer ? nullptr : &host_feed, defer_finish);
     }
     // The results' way back, through the pinned pieces (staged_download: the runtime's pageable path page-locks a
     // destination it has not seen before, and a result array is a new allocation on every call)
@@ -2811,15 +2522,15 @@ static int bpmf_bp_run_impl(const float* features, const int32_t* moveouts, cons
     return rc;
 }
 
-extern "C" int bpmf_bp_run(const float* features, const int32_t* moveouts, const float* w_phases,
-                           const float* w_sources, size_t N, size_t K, size_t S, size_t C, size_t P,
-                           int out_of_bounds, int reduce, int device, float* beam_out,
-                           int32_t* arg_out)
+int bpmf::bp_run_host(const float* features, const int32_t* moveouts, const float* w_phases,
+                      const float* w_sources, size_t N, size_t K, size_t S, size_t C, size_t P, int out_of_bounds,
+                      int reduce, int device, float* beam_out, int32_t* arg_out, bool defer_finish)
 {
     // nothing may cross the C boundary as an exception (std::bad_alloc from the host-side planning, a
     // std::system_error): it becomes status -3 with its text
     try {
-        return bpmf_bp_run_impl(features, moveouts, w_phases, w_sources, N, K, S, C, P, out_of_bounds, reduce, device, beam_out, arg_out);
+        return bpmf_bp_run_impl(features, moveouts, w_phases, w_sources, N, K, S, C, P, out_of_bounds, reduce, device,
+                                beam_out, arg_out, defer_finish);
     } catch (const std::exception& e) {
         copy_pool_quiesce();      // (no pool thread may still read the caller's arrays)
         set_error("bpmf_bp_run: exception: %s", e.what());
@@ -2829,6 +2540,15 @@ extern "C" int bpmf_bp_run(const float* features, const int32_t* moveouts, const
         set_error("bpmf_bp_run: unknown exception");
         return -3;
     }
+}
+
+extern "C" int bpmf_bp_run(const float* features, const int32_t* moveouts, const float* w_phases,
+                           const float* w_sources, size_t N, size_t K, size_t S, size_t C, size_t P,
+                           int out_of_bounds, int reduce, int device, float* beam_out,
+                           int32_t* arg_out)
+{
+    return bp_run_host(features, moveouts, w_phases, w_sources, N, K, S, C, P, out_of_bounds, reduce, device,
+                       beam_out, arg_out, false);
 }
 
 extern "C" int bpmf_bp_pack_max_dev(const float* d_beam, const int32_t* d_arg, size_t N,

@@ -83,11 +83,10 @@ struct bpmf_bp_plan {
     bpmf::BpSource* d_srcs = nullptr;
     int* d_off = nullptr;
     float* d_beta = nullptr;
-    int ntv = 0;                 // > 0: uniform-VGPR fast path with NTV padded terms
-    int wps = 1;                 // wave-per-source kernel (needs ntv > 0 and tile 512)
     int nsv = 0;                 // > 0: packed per-station records (P == 2), NSV stations padded
     int4* d_recs = nullptr;      // [K, nsv/2]
     int4* d_hdr2 = nullptr;      // [K] headers with the station count in .w
+    int ntv = 0;                 // > 0: per-term table of NTV padded terms (tile 512 without packed records)
     void* d_termsv = nullptr;    // [K, ntv] BpTermV (bp.hip)
     // interior-tile fast path: 1-3 station-count classes of sources, each with its own tile
     bool fast = false;
@@ -116,10 +115,12 @@ struct bpmf_bp_plan {
 };
 
 namespace bpmf {
-// bp.hip, option bp.compat_first_computed: set by bpmf_bp_run_multi on the thread that runs a device's
-// share -- the share keeps -inf where it computed no beam, and the host finishes (0, first id) after
-// the merge of all shares (a finished share could not be told from a real 0)
-extern thread_local bool t_bp_defer_finish;
+// bp.hip: bpmf_bp_run, and with `defer_finish` one device's share of bpmf_bp_run_multi under option
+// bp.compat_first_computed -- the share keeps -inf where it computed no beam, and the host finishes
+// (0, first id) after the merge of all shares (a finished share could not be told from a real 0)
+int bp_run_host(const float* features, const int32_t* moveouts, const float* w_phases, const float* w_sources,
+                size_t N, size_t K, size_t S, size_t C, size_t P, int out_of_bounds, int reduce, int device,
+                float* beam_out, int32_t* arg_out, bool defer_finish);
 // bp_fast.hip: running (max, arg-max) over the sources of one class for its tiles [tile_lo, tile_hi)
 // (units of fc.tile samples), every one of which lies inside [-tmin_all, N - tmax_all) (no bounds
 // test per source).

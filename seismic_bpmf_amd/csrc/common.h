@@ -29,9 +29,8 @@ inline size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
 // alternative the upstream packages may implement.  The defaults are the tuned production values; the GPU tests use
 // the options to force every kernel family through the same parity cases.
 enum Option {
-    OPT_BP_LDS_KB, OPT_BP_MAX_GROUP, OPT_BP_TPT, OPT_BP_REORDER, OPT_BP_DUAL, OPT_BP_PACKED,
-    OPT_BP_WPS, OPT_BP_UVGPR, OPT_BP_FAST, OPT_BP_FAST_UNIFORM, OPT_BP_SPLIT, OPT_BP_WPB,
-    OPT_BP_SMETA, OPT_BP_VERBOSE, OPT_BP_FAST_TILE, OPT_BP_HALVES, OPT_BP_DIRECT, OPT_MF_WAVE_KERNEL, OPT_MF_MAX_MFMA_STEP, OPT_MF_HOST_BATCH_KB,
+    OPT_BP_LDS_KB, OPT_BP_MAX_GROUP, OPT_BP_TPT, OPT_BP_REORDER, OPT_BP_DUAL,
+    OPT_BP_FAST, OPT_BP_FAST_UNIFORM, OPT_BP_SPLIT, OPT_BP_VERBOSE, OPT_BP_FAST_TILE, OPT_BP_HALVES, OPT_BP_DIRECT, OPT_MF_WAVE_KERNEL, OPT_MF_MAX_MFMA_STEP, OPT_MF_HOST_BATCH_KB,
     OPT_MF_HOST_PIECE_KB, OPT_MF_VERBOSE, OPT_MF_TILES_PER_WAVE, OPT_MF_BOUNDARY_PRIO, OPT_MF_FUSED_PROLOGUE, OPT_DEBUG_POISON_OUTPUT,
     OPT_DEBUG_VIRTUAL_DEVICES, OPT_MULTI_PEER_FANOUT, OPT_MF_HOST_PIECE_LAGS, OPT_BP_HOST_PIECE_SAMPLES,
     OPT_HOST_CACHE_LIMIT_MB, OPT_BP_SLOT_PRIO, OPT_MF_CHANNEL_SPLIT, OPT_STATS_BUCKETED_MEDIAN, OPT_STATS_ROW_GRID_MIN_N, OPT_STATS_KURT_FULL_CHUNKS, OPT_MF_SPLIT16, OPT_DEBUG_FAIL_PEER_COPY,

@@ -263,13 +263,9 @@ extern "C" int bpmf_bp_run_multi(const float* features, const int32_t* moveouts,
     int rc = run_blocks(dev, [&](size_t i) -> int {
         const size_t k0 = b[i], nk = b[i + 1] - b[i];
         if (nk == 0) return 0;
-        struct Defer {
-            explicit Defer(bool on) { bpmf::t_bp_defer_finish = on; }
-            ~Defer() { bpmf::t_bp_defer_finish = false; }
-        } defer(first_computed);
-        return bpmf_bp_run(features, moveouts + k0 * S * P, w_phases, w_sources + k0 * S, N, nk, S, C,
-                           P, out_of_bounds, reduce, dev[i], i ? pb[i].data() : beam_out,
-                           i ? pa[i].data() : arg_out);
+        return bpmf::bp_run_host(features, moveouts + k0 * S * P, w_phases, w_sources + k0 * S, N, nk, S, C,
+                                 P, out_of_bounds, reduce, dev[i], i ? pb[i].data() : beam_out,
+                                 i ? pa[i].data() : arg_out, first_computed);
     }, true);
     if (rc) return rc;
     // Ascending source blocks and a strict >: block 0 carries the (0, source 0) starting point of

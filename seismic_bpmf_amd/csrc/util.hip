@@ -33,17 +33,12 @@ struct OptionDef { const char* name; long dflt; long lo, hi; bool plan; };
 const OptionDef OPTION_DEFS[OPT_COUNT] = {
     {"bp.lds_kb", 80, 8, 160, true},          // soft LDS budget of a group (single-window plans)
     {"bp.max_group", 4096, 1, 1 << 20, true}, // sources per group at most
-    {"bp.tpt", 2, 1, 4, true},                // samples per thread of the generic kernels (tile = 256 x tpt)
+    {"bp.tpt", 2, 1, 2, true},                // samples per thread of the generic kernels (tile = 256 x tpt)
     {"bp.reorder", 1, 0, 1, true},            // kd-tree processing order of the sources
     {"bp.dual", 1, 0, 1, true},               // dual (shifted) windows + 8-byte gathers where they fit
-    {"bp.packed", 1, 0, 1, true},             // packed per-station records (P = 2)
-    {"bp.wps", 1, 0, 1, true},                // wave-per-source kernels
-    {"bp.uvgpr", 1, 0, 1, true},              // uniform-VGPR metadata kernels
     {"bp.fast", 1, 0, 1, true},               // interior-tile kernel of bp_fast.hip
     {"bp.fast_uniform", 1, 0, 1, true},       // ready-made addresses when a source's weights are uniform
     {"bp.split", -1, -1, 1 << 16, false},      // group ranges per tile: -1 = automatic (short series)
-    {"bp.wpb", 12, 8, 12, false},              // waves per workgroup of the 4-byte-gather kernel
-    {"bp.smeta", 1, 0, 1, false},              // SGPR metadata for 32-station records
     {"bp.verbose", 0, 0, 1, false},
     {"bp.fast_tile", 0, 0, 512, true},        // 0: the cost model picks each class's tile; 512 / 256 / 128: only that one
     {"bp.halves", 1, 0, 1, true},             // 33-64 stations: two LDS residencies per group at tile 256 where cheaper

@@ -1,7 +1,7 @@
 """GPU: every kernel variant the dispatchers can pick, each bit-exact against the oracle.
 
 MF: staging-register variants (L <= 273 / 1041 / 2065), the generic kernel beyond, step > 1.
-BP: wave-per-source (<= 32 terms/source), uniform-VGPR time-split, readlane kernels with 1 / 2 / 4
+BP: packed two-phase records, wave-per-source (<= 32 terms/source), readlane kernels with 1 / 2 / 4
 metadata blocks (up to 256 terms/source), tile fall-backs, P = 1 / 3 / 5.
 """
 import os
@@ -276,11 +276,13 @@ def test_bp_term_count_variants(oracle_lib, S, P, density, label):
     _bp_check(oracle_lib, f, tau, wp, ws, label)
 
 
-@pytest.mark.parametrize("env", [{"bp.wps": 0}, {"bp.uvgpr": 0}, {"bp.packed": 0},
-                                 {"bp.tpt": 1, "bp.wps": 0}, {"bp.tpt": 4, "bp.wps": 0},
+# (explicit ids: every case keeps the id it had when the list also held the retired bp.wps / bp.uvgpr /
+# bp.packed / bp.wpb cases and bp.tpt = 4)
+@pytest.mark.parametrize("env", [{"bp.tpt": 1},
                                  {"bp.reorder": 0}, {"bp.lds_kb": 24}, {"bp.max_group": 5},
-                                 {"bp.dual": 0}, {"bp.dual": 0, "bp.wpb": 8},
-                                 {"bp.dual": 0, "bp.lds_kb": 24}, {"bp.max_group": 3}])
+                                 {"bp.dual": 0},
+                                 {"bp.dual": 0, "bp.lds_kb": 24}, {"bp.max_group": 3}],
+                         ids=["tpt1", "env5", "env6", "env7", "env8", "env10", "env11"])
 def test_bp_kernel_and_plan_knobs(oracle_lib, env, hip_opts):
     for k, v in env.items():
         hip_opts(k, v)
@@ -345,8 +347,9 @@ def test_bad_arguments_raise_with_a_message():
         sb.matched_filter(tp, np.zeros((1, 1, 1)), np.ones((1, 1, 1)), np.zeros((1, 1, 50), np.float32), 1)
     with pytest.raises(ValueError, match="step"):
         sb.matched_filter(tp, np.zeros((1, 1, 1)), np.ones((1, 1, 1)), np.zeros((1, 1, 500), np.float32), 0)
-    with pytest.raises(_lib.BpmfHipError, match="unknown option"):
-        _lib.set_option("bp.no_such_option", 1)
+    for name in ("bp.no_such_option", "bp.wps", "bp.uvgpr", "bp.packed", "bp.wpb", "bp.smeta"):
+        with pytest.raises(_lib.BpmfHipError, match="unknown option"):
+            _lib.set_option(name, 1)
 
 
 # ------------------------------------------ grids without an LDS plan (bp_direct.hip) ---

@@ -77,7 +77,10 @@ int bpmf_device_memory_held(int device, size_t *device_bytes, size_t *pinned_byt
  *   the last launch was enqueued (kernels still running + the results' way back); out[4] pieces the day arrived
  *   in; out[5] host threads that filled them; out[6] waiting for a pinned piece to be free again (its previous
  *   copy still in flight); out[7] inside the runtime's asynchronous-copy calls of the pieces;
- *   out[8] finding (or building) the backprojection plan; out[9] reserving the device working set and the pinned pieces.  Returns the number of values written (<= n).  The reference has no
+ *   out[8] finding (or building) the backprojection plan; out[9] reserving the device working set and the pinned pieces;
+ *   out[10] stragglers: blocks of a pinned piece's fill that the calling thread copied itself while a copy-pool thread
+ *   still held them (that thread writes the same bytes later; nothing else writes into the piece before it is done).
+ *   Returns the number of values written (<= n).  The reference has no
  *   counterpart (its back-ends' calls are opaque, BPMF/template_search.py:549-558); bench.py reports these beside
  *   the end-to-end times. */
 int bpmf_host_call_stats(double *out, int n);
@@ -104,6 +107,9 @@ int bpmf_host_call_stats(double *out, int n);
  *     uploads from the host itself, which is what the upstream back-ends do)
  *     a device-to-device copy the platform refuses falls back to host uploads for that device, status 0, with a
  *     "note: ..." in bpmf_last_error; debug.fail_peer_copy (tests) makes every copy be refused
+ *   debug.copy_stall_ms (tests, 0 .. 2000: k > 0 = in every multi-block fill of a pinned piece by the copy pool, the
+ *     pool thread that draws the first block sleeps k ms before copying it, and the fill returns without waiting for
+ *     it: a straggler that writes the start of the piece k ms later, every time; out[10] of bpmf_host_call_stats)
  *   mf.split16 (off by default; CHANGES RESULTS within a stated tolerance: matched-filter numerators on the fp16
  *     matrix pipe from hi/lo splits of data and templates, three products, fp32 accumulation -- csrc/mf_split.h;
  *     |d cc_sum| <= 3e-7 * sum|w| measured, 2e-5 allowed by the north star; x 2.3-2.4 at configs[1]; templates of up

@@ -136,12 +136,12 @@ def last_error():
 
 def host_call_stats():
     """Where the time of this thread's last host-pointer call went (bpmf_host_call_stats), milliseconds."""
-    buf = (C.c_double * 10)()
-    k = lib().bpmf_host_call_stats(buf, 10)
+    buf = (C.c_double * 11)()
+    k = lib().bpmf_host_call_stats(buf, 11)
     names = ("total_ms", "first_kernel_start_ms", "host_copy_ms", "device_wait_ms", "pieces", "fill_threads",
-             "pinned_wait_ms", "copy_enqueue_ms", "plan_ms", "reserve_ms")
+             "pinned_wait_ms", "copy_enqueue_ms", "plan_ms", "reserve_ms", "stragglers")
     out = {n: float(buf[i]) for i, n in enumerate(names[:k])}
-    for n in ("pieces", "fill_threads"):
+    for n in ("pieces", "fill_threads", "stragglers"):
         if n in out:
             out[n] = int(out[n])
     return out

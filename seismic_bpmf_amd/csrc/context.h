@@ -70,6 +70,7 @@ struct DeviceContext {
 struct HostCallStats {
     double total_ms = 0, first_kernel_ms = 0, host_copy_ms = 0, device_wait_ms = 0, pinned_wait_ms = 0, enqueue_ms = 0, plan_ms = 0, reserve_ms = 0;
     int pieces = 0, fill_threads = 0;
+    int stragglers = 0;               // blocks of idempotent fills the caller finished while a pool thread still held them
 };
 extern thread_local HostCallStats t_call_stats;
 inline double host_now_ms()

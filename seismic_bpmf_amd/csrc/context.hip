@@ -3,6 +3,7 @@
 #include "../../include/bpmf_hip.h"
 
 #include <algorithm>
+#include <chrono>
 #include <condition_variable>
 #include <cstdlib>
 #include <functional>
@@ -72,7 +73,7 @@ int DeviceContext::reserve_pinned(size_t bytes)
     bytes = std::max<size_t>(bytes, 4096);
     if (pinned[0] && pinned[1] && bytes <= pinned_cap) return 0;
     drain(this);
-    copy_pool_quiesce();          // no host thread is still writing into a piece
+    copy_pool_quiesce();          // no host thread is still writing into a piece (a straggler of an idempotent fill)
     upload_inflight[0] = upload_inflight[1] = false;
     for (int i = 0; i < 2; ++i) {
         if (pinned[i]) (void)hipHostFree(pinned[i]);
@@ -152,6 +153,12 @@ public:
     // writing when the buffer is filled with the NEXT piece that goes through it: a job into `token` first waits for
     // the stragglers of the earlier jobs into the same token (two pieces ago: it has normally long finished), and
     // quiesce() waits for all of them (before a pinned piece is freed or used for the way down).
+    // The rule that follows: NOTHING writes into a pinned piece -- a fill, a plain memcpy, a D2H -- before the
+    // stragglers of the earlier fills into it are done.  Each such straggler counts in HostCallStats::stragglers.
+    //
+    // Option debug.copy_stall_ms = k > 0 (tests) makes one on every idempotent fill with more than one block: the
+    // caller starts drawing only once a worker has drawn block 0 (at most ~1 s), and that worker sleeps k ms
+    // before its copy -- the caller finishes block 0 itself and returns, the worker writes offset 0 k ms later.
     void run(size_t n, const std::function<void(size_t)>& fn, const void* token = nullptr)
     {
         if (n == 0) return;
@@ -166,6 +173,7 @@ public:
         job->token = token;
         job->state.reset(new std::atomic<unsigned char>[n]);
         for (size_t i = 0; i < n; ++i) job->state[i].store(0, std::memory_order_relaxed);
+        job->stall_ms = token ? option(OPT_DEBUG_COPY_STALL_MS) : 0;
         {
             std::unique_lock<std::mutex> g(m);
             if (token) cv_done.wait(g, [&] { return stragglers_of(token) == 0; });
@@ -174,13 +182,19 @@ public:
             ++generation;
         }
         cv.notify_all();
-        draw(*job);
+        if (job->stall_ms > 0) {
+            const auto until = std::chrono::steady_clock::now() + std::chrono::seconds(1);
+            while (job->next.load() == 0 && std::chrono::steady_clock::now() < until)
+                std::this_thread::sleep_for(std::chrono::microseconds(50));
+        }
+        draw(*job, false);
         if (token) {
             // nothing left to draw: finish what others hold, without waiting for them
             for (size_t i = 0; i < n; ++i)
                 if (job->state[i].load(std::memory_order_acquire) != 2) {
                     job->fn(i);
                     job->state[i].store(2, std::memory_order_release);
+                    ++t_call_stats.stragglers;
                 }
             std::lock_guard<std::mutex> g(m);
             current.reset();
@@ -197,11 +211,18 @@ public:
         std::unique_lock<std::mutex> g(m);
         cv_done.wait(g, [&] { return straggling.empty(); });
     }
+    // every straggler of the earlier jobs into `token` has finished
+    void settle(const void* token)
+    {
+        std::unique_lock<std::mutex> g(m);
+        cv_done.wait(g, [&] { return stragglers_of(token) == 0; });
+    }
 private:
     struct Job {
         std::function<void(size_t)> fn;
         size_t n = 0;
         const void* token = nullptr;
+        long stall_ms = 0;                                        // option debug.copy_stall_ms (idempotent fills only)
         std::atomic<size_t> next{0};
         std::unique_ptr<std::atomic<unsigned char>[]> state;      // 0 not drawn, 1 drawn, 2 done
         int inside = 0;                                           // workers inside draw() (under m)
@@ -225,12 +246,13 @@ private:
         for (auto& j : straggling) k += j->token == token;
         return k;
     }
-    static void draw(Job& job)
+    static void draw(Job& job, bool worker)
     {
         for (;;) {
             const size_t i = job.next.fetch_add(1, std::memory_order_relaxed);
             if (i >= job.n) return;
             job.state[i].store(1, std::memory_order_relaxed);
+            if (i == 0 && worker && job.stall_ms > 0) std::this_thread::sleep_for(std::chrono::milliseconds(job.stall_ms));
             job.fn(i);
             job.state[i].store(2, std::memory_order_release);
         }
@@ -247,7 +269,7 @@ private:
                 job = current;
                 ++job->inside;
             }
-            draw(*job);
+            draw(*job, true);
             {
                 std::lock_guard<std::mutex> g(m);
                 if (--job->inside == 0)
@@ -357,6 +379,7 @@ hipError_t staged_upload_rows(DeviceContext* ctx, float* d_dst, const float* hos
         // row segments -> the piece, packed: blocks of at most 1 MB of a row, drawn by whoever is free
         const size_t row_bytes = len * sizeof(float);
         if (rows * row_bytes < (4u << 20) || pool.team() == 1) {
+            pool.settle(pin);                  // (a straggler of an earlier fill into this piece writes other bytes)
             for (size_t r = 0; r < rows; ++r) memcpy(pin + r * row_bytes, host + r * N + a, row_bytes);
         } else {
             const size_t blk = (size_t)1 << 20, per_row = (row_bytes + blk - 1) / blk;
@@ -387,7 +410,7 @@ void DeviceContext::trim_after_call()
 void DeviceContext::release_memory()
 {
     drain(this);
-    copy_pool_quiesce();
+    copy_pool_quiesce();          // no host thread is still writing into a piece that is about to be freed
     if (dev_buf) (void)hipFree(dev_buf);
     dev_buf = nullptr;
     dev_cap = 0;
@@ -595,10 +618,11 @@ extern "C" int bpmf_release_device_memory(int device)
 extern "C" int bpmf_host_call_stats(double* out, int n)
 {
     const bpmf::HostCallStats& st = bpmf::t_call_stats;
-    const double v[10] = {st.total_ms, st.first_kernel_ms, st.host_copy_ms, st.device_wait_ms, (double)st.pieces,
-                          (double)st.fill_threads, st.pinned_wait_ms, st.enqueue_ms, st.plan_ms, st.reserve_ms};
+    const double v[11] = {st.total_ms, st.first_kernel_ms, st.host_copy_ms, st.device_wait_ms, (double)st.pieces,
+                          (double)st.fill_threads, st.pinned_wait_ms, st.enqueue_ms, st.plan_ms, st.reserve_ms,
+                          (double)st.stragglers};
     int k = 0;
-    for (; out && k < n && k < 10; ++k) out[k] = v[k];
+    for (; out && k < n && k < 11; ++k) out[k] = v[k];
     return k;
 }
 

@@ -1713,6 +1713,11 @@ static int bpmf_mf_run_impl(const float* templates, const int32_t* moveouts, con
     double t_wait = 0.0, t_copy = 0.0;
     if (!rc) rc = launch(0);
     if (t_call_stats.first_kernel_ms == 0.0) t_call_stats.first_kernel_ms = host_now_ms() - t_call0;
+    // The CC matrix comes down through the pieces the day went up through: a copy-pool thread still finishing a
+    // block of one of the day's last fills (the fill returned without it, context.hip: CopyPool::run) would write
+    // day bytes over CC bytes that have already landed.  Every such straggler is done before the first D2H (as in
+    // staged_download).
+    copy_pool_quiesce();
     for (size_t b = 0; b < n_batch && !rc; ++b) {
         if (b + 1 < n_batch) rc = launch(b + 1);   // its buffer was drained one iteration ago
         if (rc) break;

@@ -63,17 +63,23 @@ def matched_filter(full):
     T, S, L, N = (500, 20, 256, 8_640_000) if full else (16, 8, 128, 400_000)
     mf = syn.make_mf_inputs(T, S, 3, L, N, n_events=3)
     t0 = tic()
-    det, cc = workflow.matched_filter_detections(
+    det, cc, amp = workflow.matched_filter_detections(
         mf["templates"], mf["moveouts"], mf["weights"], mf["data"], step=1, sr=sr,
         threshold_window_dur=1800.0 if full else 600.0, minimum_interevent_time=5.0, n_dev=8.0,
         remove_edges=False,
-        white_noise=np.random.default_rng(5).standard_normal(500).astype(np.float32))
+        white_noise=np.random.default_rng(5).standard_normal(500).astype(np.float32), extract_peak_amplitudes=True)
     t1 = tic()
     n_det = sum(len(v) for v in det.values())
     hit = sum(int(i0 in set(np.asarray(det[t]).tolist())) for t, i0 in mf["planted"])
     print(f"matched filter: {T} templates x {S * 3} channels x {N} samples | {t1 - t0:.3f} s | "
           f"{n_det} detections, {hit}/{len(mf['planted'])} planted events at their exact CC index | "
           f"CC matrix {tuple(cc.shape)} stayed in HBM")
+    t_first, i_first = mf["planted"][0]
+    where = np.flatnonzero(np.asarray(det[t_first]) == i_first)
+    if where.size:
+        a = amp[t_first][where[0]]                                    # (S, 3): max of the 3 s behind the arrival - 1 s
+        print(f"peak amplitudes of the first planted event (template {t_first}, sample {i_first}): "
+              f"{a.min():.2f} .. {a.max():.2f} over {a.size} channels, gathered on the device")
 
 
 if __name__ == "__main__":

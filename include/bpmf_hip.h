@@ -353,6 +353,26 @@ int bpmf_count_below_dev(const float *d_series, size_t n_rows, size_t n, size_t 
                          const int32_t *d_len_right, const float *d_level, bpmf_stream_t stream,
                          int32_t *d_below);
 
+/* The peak amplitudes MatchedFilter._find_detections_t attaches to its events (BPMF/similarity_search.py:695-714,
+ * `extract_peak_amplitudes`, the reference's default; the input of the magnitude step), gathered from the day of data
+ * in HBM (peak_amp.hip): for detection q = (template row d_rows[q], DATA sample d_samples[q] = cc index x step) and
+ * channel (s, c)
+ *     i1 = d_samples[q] + d_moveouts[row, s, c] - offset;   i2 = i1 + duration;
+ *     d_out[q, s, c] = max(data[s, c, i1:i2]) * d_norm[s, c]      (0.0 for an empty slice)
+ * with the slice taken as NumPy takes it -- the reference does not guard it: i1 and i2 each get N added when
+ * negative and are then clipped to [0, N], so a window that straddles sample 0 is empty, a window wholly before
+ * sample 0 wraps to the end of the day, and a window past N is clipped.  A window that holds a NaN gives NaN
+ * (np.max); the product is one float32 multiply, and without d_norm the maximum is stored as it is.
+ *   d_data (S, C, N) f32; d_rows (n) i32; d_samples (n) i64; d_moveouts (T, S, C) i32 samples (any sign);
+ *   d_norm_or_null (S, C) f32; d_out (n, S, C) f32 -- every element is written.
+ * Returns -1 for a null pointer, S * C == 0, N, |offset| or |duration| above 2^40, or a row outside [0, T): the rows
+ * are checked on the host (a copy of 4 n bytes and one synchronisation of `stream`) before anything is launched.
+ * n_detections == 0 launches nothing and returns 0. */
+int bpmf_peak_amplitudes_dev(const float *d_data, size_t S, size_t C, size_t N, size_t n_detections,
+                             const int32_t *d_rows, const int64_t *d_samples, const int32_t *d_moveouts, size_t T,
+                             int64_t offset, int64_t duration, const float *d_norm_or_null, bpmf_stream_t stream,
+                             float *d_out);
+
 /* ------------------------------------------------- robust statistics (stats.hip) --- */
 /* np.median and MAD (median of |x - median|, float32 like NumPy) of every row of a (rows, n)
  * device array; skip_zeros != 0: over the samples != 0 only (`a[a != 0]`).  NaN for an empty

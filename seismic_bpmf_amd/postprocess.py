@@ -32,13 +32,44 @@ def moveouts_to_samples(travel_times_sec, sr, relative_to_first=True):
 
 
 # ------------------------------------------------------------------- input conditioning ---
-def normalize_data(data_arr):
+def normalize_data(data_arr, return_norm=False):
     """MatchedFilter.set_data conditioning, BPMF/similarity_search.py:181-185: each channel is
-    divided by its standard deviation (channels with zero std are left untouched)."""
+    divided by its standard deviation (channels with zero std are left untouched).  With `return_norm`:
+    (data / std, std.squeeze()) -- the second is the reference's `self.data_norm`, which turns the peak
+    amplitudes of the normalised day back into those of the recorded one (:713)."""
     d = np.array(data_arr, dtype=np.float32, copy=True)
     std = d.std(axis=-1, keepdims=True)
     std[std == 0.0] = 1.0
+    if return_norm:
+        return d / std, std.squeeze()
     return d / std
+
+
+def peak_amplitudes_host(data, rows, samples, moveouts, offset, duration, data_norm=None):
+    """Host mirror of bpmf_peak_amplitudes_dev: the loop of MatchedFilter._find_detections_t
+    (BPMF/similarity_search.py:695-714) over the detections (template row rows[q], DATA sample samples[q]), with the
+    reference's own unguarded NumPy slice -- a window that straddles sample 0 is empty, one wholly before it wraps to
+    the end of the day, one past the end is clipped.  data (S, C, N) float32, moveouts (T, S, C) in samples,
+    `offset` / `duration` in samples, data_norm (S, C) or None (the maximum is then stored as it is).
+    Returns (D, S, C) float32."""
+    data = np.asarray(data, dtype=np.float32)
+    S, C = data.shape[:2]
+    rows = np.asarray(rows).reshape(-1)
+    samples = np.asarray(samples).reshape(-1)
+    moveouts = np.asarray(moveouts)
+    moveouts = np.broadcast_to(moveouts.reshape(moveouts.shape[0], S, -1), (moveouts.shape[0], S, C))
+    norm = None if data_norm is None else np.asarray(data_norm, dtype=np.float32).reshape(S, C)
+    out = np.zeros((len(rows), S, C), dtype=np.float32)
+    for q in range(len(rows)):
+        mv = moveouts[int(rows[q])]
+        for s in range(S):
+            for c in range(C):
+                time_idx1 = int(samples[q]) + int(mv[s, c]) - int(offset)
+                time_idx2 = time_idx1 + int(duration)
+                win_peak_amp = data[s, c, time_idx1:time_idx2]
+                if len(win_peak_amp) > 0:
+                    out[q, s, c] = win_peak_amp.max() if norm is None else win_peak_amp.max() * norm[s, c]
+    return out
 
 
 def normalize_weights(weights):

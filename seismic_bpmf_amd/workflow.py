@@ -8,6 +8,8 @@
   (BPMF/template_search.py:508-572, 574-627).
 * :func:`intertemplate_cc` = the core of ``TemplateGroup.compute_intertemplate_cc``
   (BPMF/dataset.py:4775-4830).
+* :func:`peak_amplitudes` / :func:`detection_aux_data` = the peak amplitudes and the ``aux_data`` that
+  ``_find_detections_t`` attaches to every detection (BPMF/similarity_search.py:695-722).
 """
 import numpy as np
 
@@ -148,13 +150,112 @@ def validate_detections(cc, merged, bounds, c_index, c_thr, *, n_dev, threshold_
     return out
 
 
+def peak_amplitudes(data_dev, rows, samples, moveouts, *, offset, duration, data_norm=None):
+    """The peak amplitudes of ``MatchedFilter._find_detections_t`` (BPMF/similarity_search.py:695-714) for the
+    detections of ALL templates in one launch (bpmf_peak_amplitudes_dev, csrc/peak_amp.hip): out[q, s, c] is the
+    maximum of data[s, c, i1:i2], i1 = samples[q] + moveouts[rows[q], s, c] - offset, i2 = i1 + duration -- the
+    reference's own NumPy slice, see postprocess.peak_amplitudes_host -- times data_norm[s, c]; 0.0 for an empty
+    window.
+
+    `data_dev`: the (S, C, N) float32 day as a tensor on the GPU (what MatchedFilterGPU.data holds); `rows` (D,)
+    template rows; `samples` (D,) DATA samples (cc index x step); `moveouts` (T, S[, C]) in samples -- per component
+    the moveout of the phase the reference's `phase_on_comp_peak_amp` names; `offset` / `duration` in samples;
+    `data_norm` (S, C) or None.  Uploads the detection records and the moveout table, downloads D * S * C floats.
+    Returns a (D, S, C) float32 NumPy array."""
+    import ctypes as C
+    import torch
+    from . import _lib
+    if not isinstance(data_dev, torch.Tensor) or not data_dev.is_cuda:
+        raise ValueError("peak_amplitudes: data_dev must be a tensor on the GPU (there is no CPU path; the host mirror "
+                         "is postprocess.peak_amplitudes_host)")
+    if data_dev.dim() != 3:
+        raise ValueError("peak_amplitudes: data_dev must be (S, C, N)")
+    dev = data_dev.device
+    x = data_dev.to(dtype=torch.float32).contiguous()
+    S, Cc, N = (int(v) for v in x.shape)
+    rows = np.ascontiguousarray(np.asarray(rows).reshape(-1), dtype=np.int32)
+    samples = np.ascontiguousarray(np.asarray(samples).reshape(-1), dtype=np.int64)
+    if rows.shape != samples.shape:
+        raise ValueError("peak_amplitudes: rows and samples must have one entry per detection")
+    mv = moveouts.detach().cpu().numpy() if isinstance(moveouts, torch.Tensor) else np.asarray(moveouts)
+    if mv.ndim not in (2, 3) or mv.shape[1] != S or (mv.ndim == 3 and mv.shape[2] not in (1, Cc)):
+        raise ValueError(f"peak_amplitudes: moveouts must be (T, {S}) or (T, {S}, {Cc}); got {mv.shape}")
+    T = int(mv.shape[0])
+    mv = np.array(np.broadcast_to(mv.reshape(T, S, -1), (T, S, Cc)), dtype=np.int32, order="C")
+    norm = None
+    if data_norm is not None:
+        norm = np.ascontiguousarray(data_norm, dtype=np.float32)
+        if norm.shape != (S, Cc):
+            raise ValueError(f"peak_amplitudes: data_norm must be ({S}, {Cc}); got {norm.shape}")
+    D = len(rows)
+    if D == 0:
+        return np.zeros((0, S, Cc), dtype=np.float32)
+    d_rows = torch.as_tensor(rows, device=dev)
+    d_samples = torch.as_tensor(samples, device=dev)
+    d_mv = torch.as_tensor(mv, device=dev)
+    d_norm = None if norm is None else torch.as_tensor(norm, device=dev)
+    out = torch.empty((D, S, Cc), dtype=torch.float32, device=dev)
+    with torch.cuda.device(dev):
+        rc = _lib.lib().bpmf_peak_amplitudes_dev(
+            C.c_void_p(x.data_ptr()), S, Cc, N, D, C.c_void_p(d_rows.data_ptr()), C.c_void_p(d_samples.data_ptr()),
+            C.c_void_p(d_mv.data_ptr()), T, int(offset), int(duration),
+            None if d_norm is None else C.c_void_p(d_norm.data_ptr()),
+            C.c_void_p(torch.cuda.current_stream(dev).cuda_stream), C.c_void_p(out.data_ptr()))
+    _lib.check(rc, "bpmf_peak_amplitudes_dev")
+    return out.cpu().numpy()
+
+
+def _peak_amplitude_window(sr, offset_win_peak_amp_sec, duration_win_peak_amp_sec):
+    """(offset, duration) in samples, as MatchedFilter.set_data converts them (BPMF/similarity_search.py:175-180)."""
+    return (int(pp.sec_to_samp(offset_win_peak_amp_sec, sr)), int(pp.sec_to_samp(duration_win_peak_amp_sec, sr)))
+
+
+def _split_by_row(rows, values, n_rows):
+    """(D, ...) values of detections sorted by row -> {row: values of that row} for every row of range(n_rows)."""
+    bounds = np.searchsorted(rows, np.arange(n_rows + 1))
+    return {t: values[bounds[t]:bounds[t + 1]] for t in range(n_rows)}
+
+
+def detection_aux_data(detections_with_values, amplitudes, n_dev, tids=None):
+    """The ``aux_data`` dict the reference attaches to every detection (BPMF/similarity_search.py:715-722), per
+    template row: {row: [dict, ...]} in the order of the detections.  `detections_with_values`: {row: (cc indices,
+    cc float32, threshold float32)} (cc_detections(with_values=True), sharded_matched_filter_detections);
+    `amplitudes`: {row: (n_row, S, C)} (matched_filter_detections(extract_peak_amplitudes=True)) or None -- the
+    reference then stores no "peak_amplitudes"; `n_dev`: cfg.N_DEV_MF_THRESHOLD; `tids`: the template ids of the rows
+    (default: the row itself).  float32 arithmetic: n_threshold = cc / threshold, n_dev = n_threshold * n_dev."""
+    out = {}
+    for t, (idx, val, thr) in detections_with_values.items():
+        val = np.asarray(val, dtype=np.float32)
+        thr = np.asarray(thr, dtype=np.float32)
+        events = []
+        for i in range(len(idx)):
+            aux = {"cc": val[i], "n_threshold": val[i] / thr[i]}
+            aux["n_dev"] = aux["n_threshold"] * np.float32(n_dev)
+            aux["tid"] = t if tids is None else tids[t]
+            if amplitudes is not None:
+                aux["peak_amplitudes"] = amplitudes[t][i]
+            events.append(aux)
+        out[t] = events
+    return out
+
+
 def matched_filter_detections(templates, moveouts, weights, data, *, step=1, sr,
                               threshold_window_dur, minimum_interevent_time, n_dev=8.0,
                               overlap=0.25, max_cc_threshold=0.80, white_noise=None, device=None,
                               remove_edges=True, data_buffer_sec=None, data_duration_sec=None,
                               sanity_check=True, max_kurto=100.0, threshold_type="rms",
-                              anomalous_cdf_at_mean_plus_1sig=0.0, window_for_validation_Tmax=100.0, min_freq_hz=None):
+                              anomalous_cdf_at_mean_plus_1sig=0.0, window_for_validation_Tmax=100.0, min_freq_hz=None,
+                              extract_peak_amplitudes=False, offset_win_peak_amp_sec=1.0,
+                              duration_win_peak_amp_sec=3.0, moveouts_peak_amp=None, data_norm=None):
     """Matched-filter search of one day: returns ({template: cc indices}, cc device tensor).
+
+    `extract_peak_amplitudes` (the reference's default, BPMF/similarity_search.py:733, 695-714; off here, so that
+    the return value stays the pair): returns (detections, cc, amplitudes) with amplitudes = {row: (n_row, S, C)
+    float32} in the order of detections[row] -- per channel the maximum of the day in the `duration_win_peak_amp_sec`
+    window that starts `offset_win_peak_amp_sec` before the arrival, times `data_norm` (S, C) (normalize_data(...,
+    return_norm=True); None: the amplitudes of the day as given).  `moveouts_peak_amp` (T, S, C): the moveouts of the
+    phases of `phase_on_comp_peak_amp` in samples (default: `moveouts`).  Gathered on the device from the day the
+    matched filter holds there (peak_amplitudes): no second upload.
 
     `remove_edges` (the reference's default, BPMF/similarity_search.py:274-285) drops detections
     inside the `data_buffer_sec` margins the day was loaded with (`cfg.DATA_BUFFER_SEC`) and past
@@ -182,7 +283,15 @@ def matched_filter_detections(templates, moveouts, weights, data, *, step=1, sr,
                         data_duration_sec=data_duration_sec, sanity_check=sanity_check, max_kurto=max_kurto,
                         threshold_type=threshold_type, anomalous_cdf_at_mean_plus_1sig=anomalous_cdf_at_mean_plus_1sig,
                         window_for_validation_Tmax=window_for_validation_Tmax, min_freq_hz=min_freq_hz)
-    return out, cc
+    if not extract_peak_amplitudes:
+        return out, cc
+    offset, duration = _peak_amplitude_window(sr, offset_win_peak_amp_sec, duration_win_peak_amp_sec)
+    n_t = weights.shape[0]
+    rows = np.concatenate([np.full(len(out[t]), t, dtype=np.int32) for t in range(n_t)])
+    samples = np.concatenate([np.asarray(out[t], dtype=np.int64) * step for t in range(n_t)])
+    amp = peak_amplitudes(mf.data, rows, samples, moveouts if moveouts_peak_amp is None else moveouts_peak_amp,
+                          offset=offset, duration=duration, data_norm=data_norm)
+    return out, cc, _split_by_row(rows, amp, n_t)
 
 
 def cc_detections(cc, moveouts, weights, *, step=1, sr, threshold_window_dur, minimum_interevent_time,
@@ -325,6 +434,8 @@ def records_to_detections(records, n_templates):
 
 def sharded_matched_filter_detections(templates, moveouts, weights, data, *, group=None, device=None,
                                       engine=None, detector=None, data_src=None, balance=True, step=1,
+                                      extract_peak_amplitudes=False, offset_win_peak_amp_sec=1.0,
+                                      duration_win_peak_amp_sec=3.0, moveouts_peak_amp=None, data_norm=None,
                                       **detection_kwargs):
     """Matched-filter search of one day on ALL ranks of a torch.distributed group (one process per GPU):
     what ``MatchedFilter.run_matched_filter_search`` (BPMF/similarity_search.py:726-807) does with its
@@ -343,8 +454,16 @@ def sharded_matched_filter_detections(templates, moveouts, weights, data, *, gro
     finds in one process; info = {"templates": (t0, t1), "cc": this rank's CC tensor or None,
     "records_gathered": n, "broadcast_ms": float or None}.
 
+    `extract_peak_amplitudes` (with `offset_win_peak_amp_sec`, `duration_win_peak_amp_sec`, `moveouts_peak_amp`
+    (T, S, C), `data_norm`: matched_filter_detections'; needs `sr` among the detection_kwargs): every rank gathers
+    the peak amplitudes of ITS templates' detections from the day on its own GPU (peak_amplitudes) -- with
+    `data_src` the only place a rank other than the source can read the day from -- and a second all-gather of
+    (n, S * C) float32 rows brings them together: info["peak_amplitudes"] = {global template id: (n, S, C)},
+    identical on every rank and ordered like the returned detections.
+
     `engine` / `detector`: stand-ins for the per-rank MatchedFilterGPU and for cc_detections (the CPU tests
-    of the choreography over gloo pass oracle-backed ones); None = the HIP path.
+    of the choreography over gloo pass oracle-backed ones); None = the HIP path.  An engine whose day (`.data`) is not
+    on a GPU gets its amplitudes from the host mirror, postprocess.peak_amplitudes_host.
 
     threshold_type="mad" needs an explicit `white_noise` here: without one every rank would draw its own
     (np.random, as the reference does per call) and the ranks' detections would not be those of one process."""
@@ -378,6 +497,21 @@ def sharded_matched_filter_detections(templates, moveouts, weights, data, *, gro
     parts = parallel.allgather_varlen(torch.as_tensor(rec, device=rec_dev), group=group)
     everything = np.concatenate([p.cpu().numpy() for p in parts]) if parts else rec
     info = {"templates": (t0, t1), "cc": cc, "records_gathered": int(everything.shape[0]), "broadcast_ms": t_b}
+    if extract_peak_amplitudes:
+        if "sr" not in detection_kwargs:
+            raise ValueError("sharded_matched_filter_detections: extract_peak_amplitudes needs sr")
+        offset, duration = _peak_amplitude_window(detection_kwargs["sr"], offset_win_peak_amp_sec,
+                                                  duration_win_peak_amp_sec)
+        mv_amp = np.asarray(moveouts if moveouts_peak_amp is None else moveouts_peak_amp)
+        day = smf.local.data
+        # this rank's records carry global template ids, in the order they are gathered in
+        gather = peak_amplitudes if isinstance(day, torch.Tensor) and day.is_cuda else pp.peak_amplitudes_host
+        amp = gather(day, rec[:, 0], rec[:, 1] * step, mv_amp, offset=offset, duration=duration, data_norm=data_norm)
+        n_chan = int(np.prod(amp.shape[1:]))
+        parts = parallel.allgather_varlen(torch.as_tensor(amp.reshape(len(rec), n_chan), device=rec_dev), group=group)
+        amp_all = np.concatenate([p.cpu().numpy() for p in parts]).reshape((-1,) + amp.shape[1:])
+        order = np.lexsort((everything[:, 1], everything[:, 0]))              # records_to_detections' order
+        info["peak_amplitudes"] = _split_by_row(everything[order, 0], amp_all[order], T)
     return records_to_detections(everything, T), info
 
 

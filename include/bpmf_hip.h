@@ -241,6 +241,43 @@ int bpmf_bp_run_multi(const float *features, const int32_t *moveouts, const floa
                       int out_of_bounds, int reduce, int n_devices, const int *devices,
                       float *beam_out, int32_t *arg_out);
 
+/* The beamforming step of Event.relocate_beam (BPMF/dataset.py:2186-2245; tutorial notebook 6 loops it over every
+ * detected event) for a BATCH of E events on one resident plan (bp_relocate.hip).  Every event is a short feature
+ * array of N samples (60-120 s); per event the call finds the point of maximum focusing of its (K, N) beam volume --
+ * np.unravel_index(beam.argmax(), beam.shape): the first maximum in source-major order -- WITHOUT making the volume:
+ * prestack and max-beam of all events in shared launches (the general beam kernels over an event dimension), one
+ * focus launch, and for BPMF_BP_RELOCATE_SPATIAL the beam column beam[:, time_idx] of every event, gathered in the
+ * oracle's order, and Beamformer._likelihood of it (BPMF/template_search.py:498-506):
+ * ((col - min) / (max - min)).clip(0, 1) in float32, NaN for a constant column.  BPMF_BP_RELOCATE_TEMPORAL
+ * (reduce="max", dataset.py:2217-2231) returns the max-beam rows, time_idx = first maximum of a row.
+ *   element (e, s, c, t) of the features is d_features[e * event_stride + d_starts[e] + (s C + c) row_stride + t]:
+ *     one array per event   (E, S, C, N):  event_stride = S C N, row_stride = N, d_starts = NULL;
+ *     windows of a day      (S, C, N_day): event_stride = 0, row_stride = N_day, d_starts (E) i64 first samples.
+ *     A window must lie inside its row; samples outside read as 0 (the Python caller refuses such windows).
+ *   d_moveouts (K, S, P) i32, d_w_sources (K, S) f32: the tables the plan was created from, on the device (the plan
+ *     keeps them in its LDS-window form only; the column needs them as they are).  Unused (NULL) for TEMPORAL.
+ *   d_time_idx, d_src_idx (E) i32, d_max_beam (E) f32: sample, source id (plan's source_id_offset included) and
+ *     value of the maximum.  The result equals the per-event path (bpmf_bp_run_dev + arg-max) whenever
+ *     d_max_beam[e] > 0 or the event's volume is all zero; an event with d_max_beam[e] == 0 and any negative beam
+ *     is the caller's to redo one by one (seismic_bpmf_amd.workflow.relocate_events does).
+ *   SPATIAL: d_likelihood (E, K) f32; d_columns (E, K) f32 or NULL: the raw beam columns.
+ *   TEMPORAL: d_maxbeam (E, N) f32, d_maxbeam_sources (E, N) i32.  Unused pointers may be NULL.
+ * E <= 65535 per call: callers chunk (results do not depend on the chunking).  Refused (-1) while a bp.compat_*
+ * option is set: focus and column are written for the build's conventions.  A plan without LDS windows
+ * (bp_direct.hip) runs its events' max-beams one after the other inside the call; everything else is batched.
+ * Workspace: bpmf_bp_relocate_workspace_bytes(plan, E, N, C) bytes -- E prestacks (S P N floats each), the
+ * partial rows of the group-range split and, for SPATIAL, the (E, N) max-beam rows. */
+#define BPMF_BP_RELOCATE_SPATIAL 0
+#define BPMF_BP_RELOCATE_TEMPORAL 1
+size_t bpmf_bp_relocate_workspace_bytes(const bpmf_bp_plan *plan, size_t E, size_t N, size_t C);
+int bpmf_bp_relocate_batch_dev(const bpmf_bp_plan *plan, const float *d_features, size_t event_stride,
+                               size_t row_stride, const int64_t *d_starts, const float *d_w_phases,
+                               const int32_t *d_moveouts, const float *d_w_sources, size_t E, size_t N, size_t C,
+                               int out_of_bounds, int method, void *d_workspace, size_t workspace_bytes,
+                               bpmf_stream_t stream, int32_t *d_time_idx, int32_t *d_src_idx, float *d_max_beam,
+                               float *d_likelihood, float *d_columns, float *d_maxbeam,
+                               int32_t *d_maxbeam_sources);
+
 /* Multi-GPU exchange step of reduce="max": pack (beam, source id) into one uint64 whose
  * unsigned order is (beam ascending, then source id DEscending), so that an RCCL
  * all-reduce with ncclMax over uint64 (or int64 after the bias below) yields the global

@@ -59,6 +59,9 @@ SIGNATURES = {
     "bpmf_bp_run_dev": (C.c_int, [_vp, _vp, _vp, _sz, _sz, C.c_int, C.c_int, _vp, _sz, _vp, _vp, _vp]),
     "bpmf_bp_run": (C.c_int, [_f, _i, _f, _f, _sz, _sz, _sz, _sz, _sz, C.c_int, C.c_int, C.c_int,
                               _f, _i]),
+    "bpmf_bp_relocate_workspace_bytes": (_sz, [_vp, _sz, _sz, _sz]),
+    "bpmf_bp_relocate_batch_dev": (C.c_int, [_vp, _vp, _sz, _sz, _vp, _vp, _vp, _vp, _sz, _sz, _sz, C.c_int, C.c_int,
+                                             _vp, _sz, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "bpmf_bp_pack_max_dev": (C.c_int, [_vp, _vp, _sz, C.c_int, _vp, _vp]),
     "bpmf_bp_unpack_max_dev": (C.c_int, [_vp, _sz, C.c_int, _vp, _vp, _vp]),
     "bpmf_intertemplate_workspace_bytes": (_sz, [_sz, _sz, _sz, _sz]),

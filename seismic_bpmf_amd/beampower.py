@@ -99,6 +99,9 @@ class BeamformerGPU:
         if mv.ndim != 3 or ws.shape != mv.shape[:2]:
             raise ValueError("moveouts must be (K, S, P) and weights_sources (K, S)")
         self.K, self.S, self.P = mv.shape
+        self.source_id_offset = int(source_id_offset)
+        self._tables_host = (mv, ws)     # relocate_batch gathers beam columns from the tables as they are
+        self._tables_dev = None
         self._plan = C.c_void_p()
         rc = self.lib.bpmf_bp_plan_create(mv.ctypes.data_as(_lib._i), ws.ctypes.data_as(_lib._f),
                                           self.K, self.S, self.P, idx, int(source_id_offset),
@@ -164,6 +167,36 @@ class BeamformerGPU:
         _lib.check(rc, "bpmf_bp_run_dev")
         self._keepalive = (f, wp)
         return (beam, arg) if reduce == "max" else beam
+
+    _METHOD = {"spatial": 0, "temporal": 1}
+
+    def relocation_workspace_bytes(self, E, N, Cc):
+        return int(self.lib.bpmf_bp_relocate_workspace_bytes(self._plan, int(E), int(N), int(Cc)))
+
+    def relocate_batch(self, features, event_stride, row_stride, starts, weights_phases, E, N, Cc,
+                       out_of_bounds, method, workspace, time_idx, src_idx, max_beam, likelihood=None,
+                       columns=None, maxbeam=None, maxbeam_sources=None):
+        """bpmf_bp_relocate_batch_dev (include/bpmf_hip.h) on device tensors: the point of maximum focusing of E
+        events in shared launches, written to the caller's output tensors.  `features` / `starts`: see the
+        header for the two layouts.  workflow.relocate_events is the call with checks, chunks and results."""
+        t = self.torch
+        if method == "spatial" and self._tables_dev is None:
+            mv, ws = self._tables_host
+            self._tables_dev = (t.as_tensor(mv, device=self.device), t.as_tensor(ws, device=self.device))
+        mv_d, ws_d = self._tables_dev if method == "spatial" else (None, None)
+
+        def ptr(x):
+            return None if x is None else x.data_ptr()
+
+        stream = t.cuda.current_stream(self.device).cuda_stream
+        with t.cuda.device(self.device):
+            rc = self.lib.bpmf_bp_relocate_batch_dev(
+                self._plan, features.data_ptr(), int(event_stride), int(row_stride), ptr(starts),
+                weights_phases.data_ptr(), ptr(mv_d), ptr(ws_d), int(E), int(N), int(Cc), _OOB[out_of_bounds],
+                self._METHOD[method], workspace.data_ptr(), workspace.numel(), C.c_void_p(stream),
+                time_idx.data_ptr(), src_idx.data_ptr(), max_beam.data_ptr(), ptr(likelihood), ptr(columns),
+                ptr(maxbeam), ptr(maxbeam_sources))
+        _lib.check(rc, "bpmf_bp_relocate_batch_dev")
 
     # -- multi-GPU exchange step of reduce="max" (SURVEY.md section 8e) ----------------
     def pack_max(self, beam, arg):

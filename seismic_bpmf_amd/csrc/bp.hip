@@ -70,6 +70,19 @@ __global__ void bp_prestack_any_kernel(const float* __restrict__ feat,
 }
 
 // ----------------------------------------------------------------------- beam ---
+// A batch of short series (event relocation, bp_relocate.hip): gridDim.z = events, every one with its own
+// prestack `u_estride` floats and its own outputs `out_estride` elements behind the previous event's.  N
+// and all bounds stay those of ONE event, so a window never reads its neighbour's samples.  The kernels take
+// this as a template flag (BATCH, reduce="max" only): a day runs the instantiation without it, whose code is
+// what it was before batches existed -- the packed kernel sits at the edge of its scalar registers.
+__device__ __forceinline__ void bp_select_event(const float* __restrict__& U, float* __restrict__& out_beam,
+                                                int* __restrict__& out_arg, long long u_estride, long long out_estride)
+{
+    U += (size_t)blockIdx.z * (size_t)u_estride;
+    out_beam += (size_t)blockIdx.z * (size_t)out_estride;
+    out_arg += (size_t)blockIdx.z * (size_t)out_estride;
+}
+
 template <int NBLK>
 struct BpMeta {  // one source's wave-uniform metadata, spread over the lanes of a wave
     int hd;
@@ -105,14 +118,16 @@ __device__ __forceinline__ float lane_bcast(float v, int lane)
 // the lgkm counter; round 3 found that ONE lgkmcnt(0) per source is cheap with 16 waves per CU --
 // bp_fast.hip keeps its records in SGPRs -- but these general kernels predate that and only run the
 // edge tiles of a day, reduce="none" and the P != 2 grids).
-template <int TPT, int CHUNK, int NBLK, int OOB, int REDUCE>
+template <int TPT, int CHUNK, int NBLK, int OOB, int REDUCE, bool BATCH = false>
 __global__ __launch_bounds__(BP_THREADS) void bp_beam_kernel(
     const float* __restrict__ U, long long N, const BpGroup* __restrict__ groups, int n_groups,
     const int4* __restrict__ chunks, const int* __restrict__ srcs,
     const int* __restrict__ term_off, const float* __restrict__ term_beta, int NT,
-    int id_offset, float* __restrict__ out_beam, int* __restrict__ out_arg, long long tile_base, float best0)
+    int id_offset, float* __restrict__ out_beam, int* __restrict__ out_arg, long long tile_base, float best0,
+    long long u_estride, long long out_estride)
 {
     extern __shared__ float lds[];
+    if constexpr (BATCH) bp_select_event(U, out_beam, out_arg, u_estride, out_estride);
     const int tid = threadIdx.x;
     const int lane = tid & 63;
     constexpr int TILE = BP_THREADS * TPT;
@@ -275,14 +290,15 @@ struct BpMetaV {
 // source per wave) by four, and one address add serves TPW gathers.  Every wave keeps its own
 // running (max, arg-max) for the tile; they are merged through LDS at the end with the same
 // (value, lowest id) order.
-template <int TPW, int NTV, int OOB, int REDUCE>
+template <int TPW, int NTV, int OOB, int REDUCE, bool BATCH = false>
 __global__ __launch_bounds__(BP_THREADS) void bp_beam_wps_kernel(
     const float* __restrict__ U, long long N, const BpGroup* __restrict__ groups, int n_groups,
     const int4* __restrict__ chunks, const int4* __restrict__ srcs4,
     const int4* __restrict__ terms, int id_offset, float* __restrict__ out_beam,
-    int* __restrict__ out_arg, long long tile_base, float best0)
+    int* __restrict__ out_arg, long long tile_base, float best0, long long u_estride, long long out_estride)
 {
     extern __shared__ float lds[];
+    if constexpr (BATCH) bp_select_event(U, out_beam, out_arg, u_estride, out_estride);
     const int tid = threadIdx.x;
     const int lane = tid & 63;
     const int wv = tid >> 6;
@@ -490,14 +506,18 @@ struct BpMetaS {
 // B64 (plans with dual windows, see build_plan): every LDS offset is even, a lane owns the
 // sample PAIRS 128 j + 2 lane + {0, 1} and gathers them with ds_read_b64 -- 256 B/clk/CU instead of
 // the 128 B/clk/CU of the 4-byte gathers.
-template <int WPB, int NSV, int OOB, int REDUCE, bool B64 = false>
+template <int WPB, int NSV, int OOB, int REDUCE, bool B64 = false, bool BATCH = false>
 __global__ __launch_bounds__(64 * WPB, WPB >= 16 ? WPB / 4 : (WPB * 2 + 3) / 4) void bp_beam_wps2_kernel(
     const float* __restrict__ U, long long N, const BpGroup* __restrict__ groups, int n_groups,
     const int4* __restrict__ chunks, const int4* __restrict__ srcs4,
     const int4* __restrict__ recs, int id_offset, float* __restrict__ out_beam,
-    int* __restrict__ out_arg, long long tile_base, long long n_tiles, long long split_stride, float best0)
+    int* __restrict__ out_arg, long long tile_base, long long n_tiles, long long split_stride, float best0,
+    long long u_estride, long long out_estride)
 {
     extern __shared__ float lds[];
+    // BATCH: the event's prestack now; its outputs are selected where they are written (two more pointers alive
+    // through the source loop would crowd the scalar registers of the metadata set)
+    if constexpr (BATCH) U += (size_t)blockIdx.z * (size_t)u_estride;
     constexpr int TPW = 8;
     constexpr int TILE = 64 * TPW;
     constexpr int NTHREADS = 64 * WPB;
@@ -775,7 +795,8 @@ __global__ __launch_bounds__(64 * WPB, WPB >= 16 ? WPB / 4 : (WPB * 2 + 3) / 4) 
                 if (bw > b || (bw == b && aw < a)) { b = bw; a = aw; }
             }
             const long long t = t0 + x;
-            if (t < N) { out_beam[t] = b; out_arg[t] = a; }
+            const size_t eo = BATCH ? (size_t)blockIdx.z * (size_t)out_estride : 0;
+            if (t < N) { out_beam[eo + t] = b; out_arg[eo + t] = a; }
         }
     }
 }
@@ -795,12 +816,17 @@ __device__ __forceinline__ float ordered_to_f32(unsigned k)
 // (beam, arg) rows -- larger beam wins, lowest source id on equal beams, the rule of every other merge
 // Interior samples [lo_s, hi_s) hold `rows` partial rows (station-count classes x group ranges), the
 // edge samples around them -- computed by the general kernel over all sources -- `rows_edge`.
+// blockIdx.y: the event of a batch of series, its partial rows `pstride` elements behind the previous event's.
 __global__ void bp_merge_splits_kernel(const float* __restrict__ pbeam, const int* __restrict__ parg,
                                        int rows, int rows_edge, long long lo_s, long long hi_s,
-                                       size_t N, float* __restrict__ beam, int* __restrict__ arg)
+                                       size_t N, float* __restrict__ beam, int* __restrict__ arg, size_t pstride)
 {
     size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= N) return;
+    pbeam += (size_t)blockIdx.y * pstride;
+    parg += (size_t)blockIdx.y * pstride;
+    beam += (size_t)blockIdx.y * N;
+    arg += (size_t)blockIdx.y * N;
     const int n_split = ((long long)i >= lo_s && (long long)i < hi_s) ? rows : rows_edge;
     float b = pbeam[i];
     int a = parg[i];
@@ -1852,9 +1878,10 @@ bool generic_can_split(const bpmf_bp_plan* pl)
 
 // `forced` = option bp.split as the CALLER read it (once per call: the size check of the workspace and the
 // launches must see the same value even if another thread sets the option in between)
-long long split_wanted(size_t N, int forced)
+// `n_events`: series of N samples computed by one launch (a batch of events fills the chip with its events' tiles)
+long long split_wanted(size_t N, int forced, size_t n_events = 1)
 {
-    const long long n_tiles = (long long)((N + 511) / 512);
+    const long long n_tiles = (long long)((N + 511) / 512) * (long long)n_events;
     // enough workgroups for ~4 rounds over the 256 CUs (a split costs one merge pass and nothing else:
     // the ranges stage disjoint windows), none from 1024 tiles (N >= 524 288) on
     long long want = n_tiles >= 1024 ? 1 : (1024 + n_tiles - 1) / n_tiles;
@@ -1863,10 +1890,10 @@ long long split_wanted(size_t N, int forced)
 }
 
 // the general kernels alone (reduce="none", plans without interior classes)
-int bp_split_count(const bpmf_bp_plan* pl, size_t N, int forced)
+int bp_split_count(const bpmf_bp_plan* pl, size_t N, int forced, size_t n_events = 1)
 {
     if (!pl || !generic_can_split(pl)) return 1;
-    return (int)std::max<long long>(1, std::min<long long>(split_wanted(N, forced), pl->n_groups));
+    return (int)std::max<long long>(1, std::min<long long>(split_wanted(N, forced, n_events), pl->n_groups));
 }
 
 // reduce="max" on a plan with interior classes: group ranges per tile of every class kernel, and of
@@ -1920,6 +1947,9 @@ struct BpLaunch {
     // becomes the maximum) or -inf (option bp.compat_first_computed: the maximum over the computed
     // beams whatever their sign; samples without any computed beam are set to (0, first id) at the end)
     float best0 = 0.0f;
+    // a batch of series (bp_select_event): events, floats between their prestacks, elements between their outputs
+    int n_events = 1;
+    long long u_estride = 0, out_estride = 0;
 };
 
 // tiles [base, base + count) of a kernel with `tile` samples per workgroup
@@ -1975,37 +2005,46 @@ int dispatch_beam(const bpmf_bp_plan* pl, const float* U, size_t N, int oob, int
 {
     return with_oob_reduce(oob, reduce, [&](auto oob_c, auto reduce_c) -> int {
         constexpr int OOB = decltype(oob_c)::value, REDUCE = decltype(reduce_c)::value;
-        auto wps2 = [&](auto wpb_c, auto nsv_c, auto b64_c) -> int {
+        // a batch of series (lc.n_events > 1, reduce="max") runs the BATCH instantiation of the same kernel
+        auto batched = [&](auto launch) -> int {
+            if constexpr (REDUCE == BPMF_BP_REDUCE_MAX)
+                if (lc.n_events > 1) return launch(std::true_type{});
+            return launch(std::false_type{});
+        };
+        auto wps2 = [&](auto wpb_c, auto nsv_c, auto b64_c) -> int { return batched([&](auto batch_c) -> int {
             constexpr int WPB = decltype(wpb_c)::value;
-            auto kern = bp_beam_wps2_kernel<WPB, decltype(nsv_c)::value, OOB, REDUCE, decltype(b64_c)::value>;
+            auto kern = bp_beam_wps2_kernel<WPB, decltype(nsv_c)::value, OOB, REDUCE, decltype(b64_c)::value,
+                                            decltype(batch_c)::value>;
             const size_t lds = std::max(pl->lds_bytes, (size_t)2 * WPB * 512 * sizeof(float));
             return launch_general(kern, lds, 512, N, lc, stream, [&](long long tile_base, long long n_tiles) {
                 // x: a multiple of 8 (XCD-aware tile order), y: group ranges
-                kern<<<dim3((unsigned)((n_tiles + 7) / 8 * 8), (unsigned)lc.n_split), dim3(64 * WPB), lds, stream>>>(
+                kern<<<dim3((unsigned)((n_tiles + 7) / 8 * 8), (unsigned)lc.n_split, (unsigned)lc.n_events), dim3(64 * WPB), lds,
+                       stream>>>(
                     U, (long long)N, pl->d_groups, pl->n_groups, (const int4*)pl->d_chunks, pl->d_hdr2, pl->d_recs,
-                    pl->id_offset, beam, arg, tile_base, n_tiles, lc.split_stride, lc.best0);
+                    pl->id_offset, beam, arg, tile_base, n_tiles, lc.split_stride, lc.best0, lc.u_estride, lc.out_estride);
             });
-        };
-        auto wps = [&](auto ntv_c) -> int {
-            auto kern = bp_beam_wps_kernel<8, decltype(ntv_c)::value, OOB, REDUCE>;
+        }); };
+        auto wps = [&](auto ntv_c) -> int { return batched([&](auto batch_c) -> int {
+            auto kern = bp_beam_wps_kernel<8, decltype(ntv_c)::value, OOB, REDUCE, decltype(batch_c)::value>;
             // the end-of-kernel merge needs 2 * 4 * tile floats of LDS
             const size_t lds = std::max(pl->lds_bytes, (size_t)8 * 512 * sizeof(float));
             return launch_general(kern, lds, 512, N, lc, stream, [&](long long tile_base, long long n_tiles) {
-                kern<<<dim3((unsigned)n_tiles), dim3(BP_THREADS), lds, stream>>>(
+                kern<<<dim3((unsigned)n_tiles, 1, (unsigned)lc.n_events), dim3(BP_THREADS), lds, stream>>>(
                     U, (long long)N, pl->d_groups, pl->n_groups, (const int4*)pl->d_chunks, (const int4*)pl->d_srcs,
-                    (const int4*)pl->d_termsv, pl->id_offset, beam, arg, tile_base, lc.best0);
+                    (const int4*)pl->d_termsv, pl->id_offset, beam, arg, tile_base, lc.best0, lc.u_estride, lc.out_estride);
             });
-        };
-        auto readlane = [&](auto tpt_c, auto nblk_c) -> int {
+        }); };
+        auto readlane = [&](auto tpt_c, auto nblk_c) -> int { return batched([&](auto batch_c) -> int {
             constexpr int TPT = decltype(tpt_c)::value;
-            auto kern = bp_beam_kernel<TPT, 4, decltype(nblk_c)::value, OOB, REDUCE>;
+            auto kern = bp_beam_kernel<TPT, 4, decltype(nblk_c)::value, OOB, REDUCE, decltype(batch_c)::value>;
             return launch_general(kern, pl->lds_bytes, (size_t)BP_THREADS * TPT, N, lc, stream,
                                   [&](long long tile_base, long long n_tiles) {
-                kern<<<dim3((unsigned)n_tiles), dim3(BP_THREADS), pl->lds_bytes, stream>>>(
+                kern<<<dim3((unsigned)n_tiles, 1, (unsigned)lc.n_events), dim3(BP_THREADS), pl->lds_bytes, stream>>>(
                     U, (long long)N, pl->d_groups, pl->n_groups, (const int4*)pl->d_chunks, (const int*)pl->d_srcs,
-                    pl->d_off, pl->d_beta, pl->NT, pl->id_offset, beam, arg, tile_base, lc.best0);
+                    pl->d_off, pl->d_beta, pl->NT, pl->id_offset, beam, arg, tile_base, lc.best0, lc.u_estride,
+                    lc.out_estride);
             });
-        };
+        }); };
         if (pl->tpt == 2) {
             // Packed records of <= 16 stations keep a source's metadata in SGPRs: 16 waves per workgroup with
             // the 8-byte gathers of a dual plan, 12 (2 workgroups, 24 waves per CU) with 4-byte gathers, which
@@ -2138,7 +2177,7 @@ int bp_run_dev(const bpmf_bp_plan* pl, const float* d_features, const float* d_w
         int rc = launch_beam_direct(pl, U, N, out_of_bounds, reduce, stream, pbeam, parg, rows, (long long)N, best0);
         if (!rc && rows > 1) {
             bp_merge_splits_kernel<<<dim3((unsigned)((N + 255) / 256)), dim3(256), 0, stream>>>(
-                pbeam, parg, rows, rows, 0, (long long)N, N, beam_final, arg_final);
+                pbeam, parg, rows, rows, 0, (long long)N, N, beam_final, arg_final, 0);
             BPMF_LAUNCH_CHECK();
         }
         if (!rc && reduce == BPMF_BP_REDUCE_MAX) rc = finish(beam_final, arg_final);
@@ -2235,7 +2274,7 @@ int bp_run_dev(const bpmf_bp_plan* pl, const float* d_features, const float* d_w
         if (!rc && es != stream) BPMF_HIP_CHECK(hipStreamWaitEvent(stream, pl->ev_join, 0));
         if (!rc && rows > 1) {
             bp_merge_splits_kernel<<<dim3((unsigned)((N + 255) / 256)), dim3(256), 0, stream>>>(
-                pbeam, parg, rows, n_split_edge, lo_s, hi_s, N, beam_final, arg_final);
+                pbeam, parg, rows, n_split_edge, lo_s, hi_s, N, beam_final, arg_final, 0);
             BPMF_LAUNCH_CHECK();
         }
         if (!rc) rc = finish(beam_final, arg_final);
@@ -2254,7 +2293,7 @@ int bp_run_dev(const bpmf_bp_plan* pl, const float* d_features, const float* d_w
                            stream, d_beam_out, d_arg_out);
     if (!rc && merge) {
         bp_merge_splits_kernel<<<dim3((unsigned)((N + 255) / 256)), dim3(256), 0, stream>>>(
-            d_beam_out, d_arg_out, n_split, n_split, 0, (long long)N, N, beam_final, arg_final);
+            d_beam_out, d_arg_out, n_split, n_split, 0, (long long)N, N, beam_final, arg_final, 0);
         BPMF_LAUNCH_CHECK();
     }
     if (!rc && reduce == BPMF_BP_REDUCE_MAX) rc = finish(beam_final, arg_final);
@@ -2262,6 +2301,62 @@ int bp_run_dev(const bpmf_bp_plan* pl, const float* d_features, const float* d_w
 }
 
 }  // namespace
+
+// ---- a batch of short series (event relocation, bp_relocate.hip) ----
+// Partial rows behind the prestacks of `E` series: the group ranges of the general kernels count the tiles of the
+// WHOLE batch (a few hundred events fill the chip without any split); a plan without LDS windows runs its events
+// one after the other on the stream and folds each through the same rows.
+size_t bpmf::bp_max_batch_part_bytes(const bpmf_bp_plan* pl, size_t N, size_t E, int forced_split)
+{
+    if (pl->direct) {
+        const size_t rows = (size_t)direct_split_count(pl, N);
+        return rows > 1 ? align_up(rows * N * (sizeof(float) + sizeof(int32_t)), 256) : 0;
+    }
+    const size_t rows = (size_t)bp_split_count(pl, N, forced_split, E);
+    return rows > 1 ? align_up(E * rows * N * (sizeof(float) + sizeof(int32_t)), 256) : 0;
+}
+
+// reduce="max" of E series: event e reads the prestack U + e S P N and writes beam / arg + e N.  Always the general
+// kernel over every tile (series this short have next to no interior tiles), the build's conventions (running
+// maximum from (0, first id)).
+int bpmf::bp_max_batch(const bpmf_bp_plan* pl, const float* U, size_t N, size_t E, int out_of_bounds, int forced_split,
+                       void* d_part, hipStream_t stream, float* beam, int32_t* arg)
+{
+    const size_t u_estride = pl->S * pl->P * N;
+    const dim3 mgrid((unsigned)((N + 255) / 256), 1);
+    if (pl->direct) {
+        const int rows = direct_split_count(pl, N);
+        float* pbeam = (float*)d_part;
+        int32_t* parg = (int32_t*)((char*)d_part + (size_t)rows * N * sizeof(float));
+        for (size_t e = 0; e < E; ++e) {
+            float* be = beam + e * N;
+            int32_t* ae = arg + e * N;
+            if (int rc = launch_beam_direct(pl, U + e * u_estride, N, out_of_bounds, BPMF_BP_REDUCE_MAX, stream,
+                                            rows > 1 ? pbeam : be, rows > 1 ? parg : ae, rows, (long long)N, 0.0f))
+                return rc;
+            if (rows > 1) {
+                bp_merge_splits_kernel<<<mgrid, dim3(256), 0, stream>>>(pbeam, parg, rows, rows, 0, (long long)N, N, be, ae, 0);
+                BPMF_LAUNCH_CHECK();
+            }
+        }
+        return 0;
+    }
+    const int n_split = bp_split_count(pl, N, forced_split, E);
+    const bool merge = n_split > 1;
+    float* pbeam = merge ? (float*)d_part : beam;
+    int32_t* parg = merge ? (int32_t*)((char*)d_part + E * (size_t)n_split * N * sizeof(float)) : arg;
+    BpLaunch lc{0, -1, n_split, merge ? (long long)N : 0, 0.0f};
+    lc.n_events = (int)E;
+    lc.u_estride = (long long)u_estride;
+    lc.out_estride = (long long)(merge ? (size_t)n_split * N : N);
+    if (int rc = dispatch_beam(pl, U, N, out_of_bounds, BPMF_BP_REDUCE_MAX, lc, stream, pbeam, parg)) return rc;
+    if (merge) {
+        bp_merge_splits_kernel<<<dim3(mgrid.x, (unsigned)E), dim3(256), 0, stream>>>(
+            pbeam, parg, n_split, n_split, 0, (long long)N, N, beam, arg, (size_t)n_split * N);
+        BPMF_LAUNCH_CHECK();
+    }
+    return 0;
+}
 
 extern "C" int bpmf_bp_run_dev(const bpmf_bp_plan* pl, const float* d_features,
                                const float* d_w_phases, size_t N, size_t C, int out_of_bounds,

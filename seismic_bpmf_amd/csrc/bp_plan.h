@@ -121,6 +121,12 @@ namespace bpmf {
 int bp_run_host(const float* features, const int32_t* moveouts, const float* w_phases, const float* w_sources,
                 size_t N, size_t K, size_t S, size_t C, size_t P, int out_of_bounds, int reduce, int device,
                 float* beam_out, int32_t* arg_out, bool defer_finish);
+// bp.hip: reduce="max" of a batch of E short series (bp_relocate.hip): prestacks S P N floats apart in U, results N
+// elements apart in beam / arg, partial rows of the group-range split in d_part (bp_max_batch_part_bytes);
+// `forced_split` = option bp.split as the caller read it
+size_t bp_max_batch_part_bytes(const bpmf_bp_plan* pl, size_t N, size_t E, int forced_split);
+int bp_max_batch(const bpmf_bp_plan* pl, const float* U, size_t N, size_t E, int out_of_bounds, int forced_split,
+                 void* d_part, hipStream_t stream, float* beam, int32_t* arg);
 // bp_fast.hip: running (max, arg-max) over the sources of one class for its tiles [tile_lo, tile_hi)
 // (units of fc.tile samples), every one of which lies inside [-tmin_all, N - tmax_all) (no bounds
 // test per source).

@@ -602,6 +602,26 @@ def likelihood(beam_column):
     return np.clip(like, a_min=0.0, a_max=1.0)
 
 
+def focus_from_max(maxbeam, arg):
+    """Host mirror of the focus kernel of the batched relocation (csrc/bp_relocate.hip): the point of maximum
+    focusing of a (K, N) beam volume from its per-sample maximum over the sources alone -- `maxbeam` (N,) and
+    `arg` (N,), the running maximum of the build (start (0, source 0), replaced on strictly greater, sources
+    ascending: arg[t] is the LOWEST source that reaches maxbeam[t]).  With M = maxbeam.max(): among the samples
+    with maxbeam == M the smallest arg, then the smallest such sample.  Returns (src_idx, time_idx, M).
+
+    Equals np.unravel_index(vol.argmax(), vol.shape) -- the first maximum in source-major order -- whenever
+    M > 0 or the whole volume is zero: the lowest source that reaches M anywhere is the smallest arg among the
+    samples that reach M, and its first sample there is the smallest of them.  (M == 0 over a volume with negative
+    beams hides where its zeros are; workflow.relocate_events redoes such an event on the volume.)"""
+    mb = np.asarray(maxbeam)
+    a = np.asarray(arg)
+    m = mb.max()
+    at_max = np.flatnonzero(mb == m)
+    src = a[at_max].min()
+    time_idx = at_max[a[at_max] == src][0]
+    return int(src), int(time_idx), m
+
+
 def gibbs_weights(maxbeam, effective_kT=0.33):
     """Likelihood of the "temporal" uncertainty method of Event.relocate_beam
     (BPMF/dataset.py:2224-2231): exp(-(max - maxbeam) / effective_kT)."""

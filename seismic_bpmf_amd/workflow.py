@@ -693,6 +693,141 @@ def relocation_likelihood(beamformer, features, weights_phases, out_of_bounds="f
     return src_idx, time_idx, like.cpu().numpy()
 
 
+def _relocation_windows(features, starts, n_samples):
+    """Shapes of relocate_events' input, checked without touching a device: (E, S, C, N, starts int64 or None)."""
+    shape = tuple(features.shape) if hasattr(features, "shape") else np.shape(features)
+    if starts is None:
+        if n_samples is not None:
+            raise ValueError("n_samples goes with starts (windows of a day); a batch (E, S, C, N) carries its own")
+        if len(shape) != 4:
+            raise ValueError("features must be (E, S, C, N), one window per event -- or (S, C, N_day) with "
+                             f"starts and n_samples; got {shape}")
+        E, S, Cc, N = shape
+        if N < 1:
+            raise ValueError("windows of no samples")
+        return E, S, Cc, N, None
+    if n_samples is None:
+        raise ValueError("starts needs n_samples, the length of every window")
+    if len(shape) != 3:
+        raise ValueError(f"with starts, features must be the day (S, C, N_day); got {shape}")
+    st = np.asarray(starts.cpu() if hasattr(starts, "cpu") else starts)
+    if st.ndim != 1 or (st.size and not np.issubdtype(st.dtype, np.integer)):
+        raise ValueError("starts must be a vector of E integer sample indices")
+    st = st.astype(np.int64)
+    S, Cc, n_day = shape
+    N = int(n_samples)
+    if N < 1:
+        raise ValueError("n_samples must be at least 1")
+    if st.size and (st.min() < 0 or st.max() + N > n_day):
+        bad = int(np.flatnonzero((st < 0) | (st + N > n_day))[0])
+        raise ValueError(f"window {bad} = [{int(st[bad])}, {int(st[bad]) + N}) leaves the day of {n_day} samples "
+                         "(no wrap, no clipping)")
+    return st.size, S, Cc, N, st
+
+
+def relocate_events(beamformer, features, weights_phases, uncertainty_method="spatial",
+                    out_of_bounds="flexible", starts=None, n_samples=None, columns=False, _chunk=None):
+    """The beamforming step of ``Event.relocate_beam`` (BPMF/dataset.py:2186-2245) for a BATCH of events in one
+    call on a resident BeamformerGPU -- what tutorial notebook 6 does in a loop over every detected event, and
+    what relocation_focus / relocation_likelihood do for one.  The events share the launches
+    (bpmf_bp_relocate_batch_dev, csrc/bp_relocate.hip): their tiles fill the chip as a day's do, the (K, N)
+    volume of an event is never made, and the host synchronises once.
+
+    `features`: (E, S, C, N), one window per event (array or device tensor) -- or the day (S, C, N_day) with
+    `starts` (E first samples) and `n_samples`: event e is features[:, :, starts[e]:starts[e] + n_samples], read
+    where the day lies in HBM (what backprojection_detections(..., return_device=True) leaves there).  A window
+    that leaves the day raises ValueError.
+
+    Returns a dict: ``src_idx`` (E,) int64, ``time_idx`` (E,) int64, ``max_beam`` (E,) float32 on the host, and
+      "spatial":  ``likelihood`` (E, K) float32 DEVICE tensor, row e = Beamformer._likelihood of
+                  beam_e[:, time_idx[e]] (NaN row for a constant column); columns=True adds ``columns``, the raw
+                  beam columns.  Take likelihood[e, domain_e] to postprocess.compute_location_uncertainty.
+      "temporal": ``maxbeam`` (E, N) float32 and ``maxbeam_sources`` (E, N) int32 device tensors;
+                  time_idx[e] = maxbeam[e].argmax(), src_idx[e] = maxbeam_sources[e, time_idx[e]].
+    For every event the result is what relocation_focus / relocation_likelihood return for it alone, bit for
+    bit, ties included (first maximum in source-major order).  An event whose maximum is not > 0 although its
+    window is not all zero (negative features or weights) is redone on its volume by the per-event path.
+    Events run in chunks sized from the free device memory; the results do not depend on the chunks."""
+    if uncertainty_method not in ("spatial", "temporal"):
+        raise ValueError("uncertainty_method should be 'spatial' or 'temporal'")
+    if out_of_bounds not in ("strict", "flexible"):
+        raise ValueError("out_of_bounds should be 'strict' or 'flexible'")
+    E, S, Cc, N, st = _relocation_windows(features, starts, n_samples)
+    bf = beamformer
+    if S != bf.S:
+        raise ValueError("features and moveouts disagree on the number of stations")
+    if tuple(np.shape(weights_phases)) != (S, Cc, bf.P):
+        raise ValueError(f"weights_phases must be ({S}, {Cc}, {bf.P})")
+    t = bf.torch
+    dev = bf.device
+    spatial = uncertainty_method == "spatial"
+    K = bf.K
+    time_idx = t.empty(E, dtype=t.int32, device=dev)
+    src_idx = t.empty(E, dtype=t.int32, device=dev)
+    max_beam = t.empty(E, dtype=t.float32, device=dev)
+    like = t.empty((E, K), dtype=t.float32, device=dev) if spatial else None
+    cols = t.empty((E, K), dtype=t.float32, device=dev) if spatial and columns else None
+    mbeam = None if spatial else t.empty((E, N), dtype=t.float32, device=dev)
+    marg = None if spatial else t.empty((E, N), dtype=t.int32, device=dev)
+    res = {"src_idx": np.zeros(E, np.int64), "time_idx": np.zeros(E, np.int64), "max_beam": np.zeros(E, np.float32)}
+    res.update({"likelihood": like} if spatial else {"maxbeam": mbeam, "maxbeam_sources": marg})
+    if cols is not None:
+        res["columns"] = cols
+    if E == 0:
+        return res
+    wp = bf._dev(weights_phases, t.float32)
+    resident = isinstance(features, t.Tensor) and features.device == dev
+    day = bf._dev(features, t.float32) if st is not None else None
+    st_dev = None if st is None else t.as_tensor(st, device=dev)
+    # events per launch: a quarter of the free memory for the prestacks (S P N floats per event) and the rows
+    # behind them, at most the 65535 of a launch
+    if _chunk is None:
+        free = t.cuda.mem_get_info(dev)[0]
+        per_event = (S * bf.P * N + 4 * N) * 4 + (0 if resident or st is not None else S * Cc * N * 4)
+        _chunk = max(1, (free // 4) // per_event)
+    chunk = int(max(1, min(_chunk, E, 65535)))
+    ws = t.empty(max(bf.relocation_workspace_bytes(min(chunk, E - e0), N, Cc) for e0 in range(0, E, chunk)),
+                 dtype=t.uint8, device=dev)
+
+    def part(x, e0, e1):
+        return None if x is None else x[e0:e1]
+
+    for e0 in range(0, E, chunk):
+        e1 = min(E, e0 + chunk)
+        if st is not None:
+            f, ev_stride, row_stride, sd = day, 0, day.shape[2], st_dev[e0:e1]
+        else:
+            f, ev_stride, row_stride, sd = bf._dev(features[e0:e1], t.float32), S * Cc * N, N, None
+        bf.relocate_batch(f, ev_stride, row_stride, sd, wp, e1 - e0, N, Cc, out_of_bounds, uncertainty_method, ws,
+                          time_idx[e0:e1], src_idx[e0:e1], max_beam[e0:e1], part(like, e0, e1), part(cols, e0, e1),
+                          part(mbeam, e0, e1), part(marg, e0, e1))
+    del ws
+    res["time_idx"] = time_idx.cpu().numpy().astype(np.int64)          # (the one synchronisation of the batch)
+    res["src_idx"] = src_idx.cpu().numpy().astype(np.int64)
+    res["max_beam"] = max_beam.cpu().numpy()
+    if not spatial:
+        return res
+    res["src_idx"] -= bf.source_id_offset          # rows of the volume, as np.unravel_index gives them
+    # A maximum that is not > 0: the running maximum starts at (0, first source), so a volume whose largest
+    # beam is 0 or negative does not show in the max-beam where its first maximum lies.  All-zero windows give
+    # an all-zero volume, whose first maximum is (0, 0) as found; anything else goes through its volume.
+    for e in np.flatnonzero(~(res["max_beam"] > 0)):
+        e = int(e)
+        win = day[:, :, int(st[e]):int(st[e]) + N] if st is not None else bf._dev(features[e], t.float32)
+        if not bool((win != 0).any()):
+            continue
+        vol = bf.run(win.contiguous(), wp, "none", out_of_bounds)
+        k, ti = divmod(int(t.argmax(vol.reshape(-1))), N)
+        col = vol[:, ti]
+        lo, hi = col.min(), col.max()
+        like[e] = ((col - lo) / (hi - lo)).clamp_(0.0, 1.0)
+        if cols is not None:
+            cols[e] = col
+        res["src_idx"][e], res["time_idx"][e], res["max_beam"][e] = k, ti, float(col[k])
+        del vol
+    return res
+
+
 def backprojection_detections(features, moveouts, weights_phases, weights_sources, *, sr,
                               minimum_interevent_time, threshold_window_dur=None, n_dev=15.0,
                               overlap=0.75, threshold=None, out_of_bounds="strict", device=None,

@@ -278,6 +278,41 @@ int bpmf_bp_relocate_batch_dev(const bpmf_bp_plan *plan, const float *d_features
                                float *d_likelihood, float *d_columns, float *d_maxbeam,
                                int32_t *d_maxbeam_sources);
 
+/* The end of Event.relocate_beam (BPMF/dataset.py:2207-2245) for a chunk of E events that
+ * bpmf_bp_relocate_batch_dev has just relocated, on its outputs where they lie (bp_uncertainty.hip): the restricted
+ * domain around each new epicentre (Beamformer._rectangular_domain, BPMF/template_search.py:1232-1267), and the
+ * likelihood-weighted mean geodesic distance and mean absolute depth difference of the domain's sources
+ * (Beamformer._compute_location_uncertainty, :1269-1333).  No host synchronisation; everything on `stream`.
+ *   d_src_idx (E) i32: the events' source ids as bpmf_bp_relocate_batch_dev wrote them (the plan's source_id_offset
+ *     included; the tables are indexed with id - offset).
+ *   d_tables (6, K) f64, one value per source ROW of the plan: longitude, latitude (degrees), depth (km),
+ *     dist_per_lat = 2 pi / 360 * 6371 * sin(deg2rad(90 - latitude)), sin and cos of the reduced latitude
+ *     atan((1 - f) tan(latitude)) on WGS84.  dist_per_lon = 2 pi / 360 * 6371; half_side_km = side_km / 2.
+ *   SPATIAL:  terms are the K sources, weight d_likelihood[e, k] (f32, widened exactly), source k takes part if
+ *     |lon_k - lon_0| dist_per_lon < half_side_km and |lat_k - lat_0| dist_per_lat[row_0] < half_side_km, evaluated
+ *     as NumPy evaluates it in float64.  d_domain_mask (E, K) u8 or NULL receives the test.
+ *   TEMPORAL: terms are the N samples, source d_maxbeam_sources[e, t] - offset, weight
+ *     expf(-(d_max_beam[e] - d_maxbeam[e, t]) / (float)effective_kT) in float32; a sample takes part if its weight
+ *     is > (float)gibbs_cutoff.  d_domain_mask must be NULL.
+ *   Outputs (E): d_hunc = sum w d / sum w, d in km along the WGS84 geodesic (Vincenty's inverse, |d lambda| < 1e-12,
+ *     200 iterations at most, pi (a + b) / 2 for a pair that does not converge); d_vunc = sum w |depth_0 - depth| /
+ *     sum w; d_n_domain: the terms that took part; d_longitude, d_latitude, d_depth: the event's row of the tables.
+ *     sum w = 0 and NaN weights give NaN.  A source id outside the plan gives NaN and d_n_domain = -1.
+ *   The numerators are float64 sums in a fixed tree (256 terms per workgroup, then one workgroup per event).  The
+ *     denominator is what the reference divides by: np.sum of the float32 weights that take part, a FLOAT32 sum in
+ *     NumPy's order (chunks of 8192 added in turn, each summed pairwise), reproduced bit for bit.  The result of an
+ *     event does not depend on E, on the chunk or on the run.
+ * E <= 65535 per call.  Workspace: bpmf_bp_location_uncertainty_workspace_bytes(E, K or N) bytes. */
+size_t bpmf_bp_location_uncertainty_workspace_bytes(size_t E, size_t n_terms);
+int bpmf_bp_location_uncertainty_dev(const bpmf_bp_plan *plan, int method, size_t E, size_t N,
+                                     const int32_t *d_src_idx, const float *d_likelihood, const float *d_maxbeam,
+                                     const int32_t *d_maxbeam_sources, const float *d_max_beam,
+                                     const double *d_tables, double dist_per_lon, double half_side_km,
+                                     double effective_kT, double gibbs_cutoff, void *d_workspace,
+                                     size_t workspace_bytes, bpmf_stream_t stream, double *d_hunc, double *d_vunc,
+                                     int32_t *d_n_domain, double *d_longitude, double *d_latitude, double *d_depth,
+                                     uint8_t *d_domain_mask);
+
 /* Multi-GPU exchange step of reduce="max": pack (beam, source id) into one uint64 whose
  * unsigned order is (beam ascending, then source id DEscending), so that an RCCL
  * all-reduce with ncclMax over uint64 (or int64 after the bias below) yields the global

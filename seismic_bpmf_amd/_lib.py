@@ -62,6 +62,10 @@ SIGNATURES = {
     "bpmf_bp_relocate_workspace_bytes": (_sz, [_vp, _sz, _sz, _sz]),
     "bpmf_bp_relocate_batch_dev": (C.c_int, [_vp, _vp, _sz, _sz, _vp, _vp, _vp, _vp, _sz, _sz, _sz, C.c_int, C.c_int,
                                              _vp, _sz, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "bpmf_bp_location_uncertainty_workspace_bytes": (_sz, [_sz, _sz]),
+    "bpmf_bp_location_uncertainty_dev": (C.c_int, [_vp, C.c_int, _sz, _sz, _vp, _vp, _vp, _vp, _vp, _vp, C.c_double,
+                                                   C.c_double, C.c_double, C.c_double, _vp, _sz, _vp, _vp, _vp, _vp,
+                                                   _vp, _vp, _vp, _vp]),
     "bpmf_bp_pack_max_dev": (C.c_int, [_vp, _vp, _sz, C.c_int, _vp, _vp]),
     "bpmf_bp_unpack_max_dev": (C.c_int, [_vp, _sz, C.c_int, _vp, _vp, _vp]),
     "bpmf_intertemplate_workspace_bytes": (_sz, [_sz, _sz, _sz, _sz]),

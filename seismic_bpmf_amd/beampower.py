@@ -83,8 +83,29 @@ def beamform(waveform_features, time_delays, weights_phases, weights_sources, de
     return beam if reduce == "none" else (beam, arg)
 
 
+def source_coordinate_tables(longitude, latitude, depth, K):
+    """The (6, K) float64 tables of bpmf_bp_location_uncertainty_dev from the coordinates of K source rows:
+    longitude, latitude, depth, postprocess.domain_scale_per_latitude, sin and cos of the reduced latitude.
+    Wrong lengths and values that are not finite raise ValueError (host only: no device is touched)."""
+    from . import postprocess as pp
+    cols = []
+    for name, x in (("longitude", longitude), ("latitude", latitude), ("depth", depth)):
+        x = np.asarray(x, dtype=np.float64)
+        if x.shape != (K,):
+            raise ValueError(f"{name} must be ({K},), one value per source row of the plan; got {x.shape}")
+        if not np.isfinite(x).all():
+            raise ValueError(f"{name} holds values that are not finite")
+        cols.append(x)
+    if np.abs(cols[1]).max(initial=0.0) > 90.0:
+        raise ValueError("latitude outside [-90, 90] degrees")
+    su, cu = pp.reduced_latitude_sin_cos(cols[1])
+    return np.ascontiguousarray(np.stack(cols + [pp.domain_scale_per_latitude(cols[1]), su, cu]))
+
+
 class BeamformerGPU:
     """Device-resident beamformer bound to one moveout table and one set of source weights."""
+    _coord_tables = None         # set_source_coordinates
+    source_coordinates = None
 
     def __init__(self, moveouts, weights_sources, device=None, source_id_offset=0):
         import torch
@@ -197,6 +218,42 @@ class BeamformerGPU:
                 time_idx.data_ptr(), src_idx.data_ptr(), max_beam.data_ptr(), ptr(likelihood), ptr(columns),
                 ptr(maxbeam), ptr(maxbeam_sources))
         _lib.check(rc, "bpmf_bp_relocate_batch_dev")
+
+    def set_source_coordinates(self, longitude, latitude, depth):
+        """Coordinates of this plan's source rows, three (K,) arrays: degrees, degrees, km -- what
+        ``Beamformer.set_source_coordinates`` (BPMF/template_search.py:753) keeps in a DataFrame.  The float64
+        tables of bpmf_bp_location_uncertainty_dev are built and uploaded once, here."""
+        tables = source_coordinate_tables(longitude, latitude, depth, self.K)
+        self.source_coordinates = {"longitude": tables[0].copy(), "latitude": tables[1].copy(),
+                                   "depth": tables[2].copy()}
+        self._coord_tables = self.torch.as_tensor(tables, device=self.device)
+
+    def uncertainty_workspace_bytes(self, E, n_terms):
+        return int(self.lib.bpmf_bp_location_uncertainty_workspace_bytes(int(E), int(n_terms)))
+
+    def location_uncertainty(self, method, E, N, src_idx, workspace, out, n_domain, likelihood=None, maxbeam=None,
+                             maxbeam_sources=None, max_beam=None, side_km=100.0, effective_kT=0.33,
+                             gibbs_cutoff=0.25, domain_mask=None):
+        """bpmf_bp_location_uncertainty_dev (include/bpmf_hip.h) on device tensors, behind relocate_batch on the
+        same stream: `out` (5, E) float64 receives hunc, vunc, longitude, latitude, depth and `n_domain` (E,)
+        int32 the size of the domain.  workflow.relocate_events(uncertainties=True) is the call with checks."""
+        from . import postprocess as pp
+        t = self.torch
+        if getattr(self, "_coord_tables", None) is None:
+            raise ValueError("no source coordinates: call set_source_coordinates(longitude, latitude, depth) first")
+
+        def ptr(x):
+            return None if x is None else x.data_ptr()
+
+        stream = t.cuda.current_stream(self.device).cuda_stream
+        with t.cuda.device(self.device):
+            rc = self.lib.bpmf_bp_location_uncertainty_dev(
+                self._plan, self._METHOD[method], int(E), int(N), src_idx.data_ptr(), ptr(likelihood), ptr(maxbeam),
+                ptr(maxbeam_sources), ptr(max_beam), self._coord_tables.data_ptr(), pp.domain_scale_per_longitude(),
+                float(side_km) / 2.0, float(effective_kT), float(gibbs_cutoff), workspace.data_ptr(),
+                workspace.numel(), C.c_void_p(stream), out[0].data_ptr(), out[1].data_ptr(), n_domain.data_ptr(),
+                out[2].data_ptr(), out[3].data_ptr(), out[4].data_ptr(), ptr(domain_mask))
+        _lib.check(rc, "bpmf_bp_location_uncertainty_dev")
 
     # -- multi-GPU exchange step of reduce="max" (SURVEY.md section 8e) ----------------
     def pack_max(self, beam, arg):

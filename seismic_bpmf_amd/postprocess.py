@@ -629,6 +629,50 @@ def gibbs_weights(maxbeam, effective_kT=0.33):
     return np.exp(-(mb.max() - mb) / effective_kT)
 
 
+DOMAIN_EARTH_RADIUS_KM = 6371.0     # the sphere of Beamformer._rectangular_domain
+
+
+def rectangular_domain(lon0, lat0, longitudes, latitudes, side_km=100.0):
+    """Beamformer._rectangular_domain (BPMF/template_search.py:1232-1267), operation for operation in float64:
+    the sources of a grid inside a rectangle of `side_km` centred on (lon0, lat0), on a sphere of 6371 km.
+    `longitudes`, `latitudes`: (K,) coordinates of the grid.  Returns a (K,) bool array.  (The reference scales the
+    LATITUDE differences by the length of a degree along the parallel of lat0 and the longitude differences by
+    the length of a degree of a great circle; so does this.)"""
+    lat0 = np.float64(lat0)
+    lon0 = np.float64(lon0)
+    R_earth_km = DOMAIN_EARTH_RADIUS_KM
+    colat0 = 90.0 - lat0
+    Rlat = R_earth_km * np.sin(np.deg2rad(colat0))
+    dist_per_lat = 2.0 * np.pi * (1.0 / 360.0) * Rlat
+    dist_per_lon = 2.0 * np.pi * (1.0 / 360.0) * R_earth_km
+    longitudes = np.asarray(longitudes, dtype=np.float64)
+    latitudes = np.asarray(latitudes, dtype=np.float64)
+    return (np.abs(longitudes - lon0) * dist_per_lon < side_km / 2.0) & (
+        np.abs(latitudes - lat0) * dist_per_lat < side_km / 2.0)
+
+
+def domain_scale_per_latitude(latitudes):
+    """`dist_per_lat` of rectangular_domain for every source of a grid as the centre: table[k] is the scalar
+    the function computes for lat0 = latitudes[k] (same expression, evaluated on the vector)."""
+    latitudes = np.asarray(latitudes, dtype=np.float64)
+    colat0 = 90.0 - latitudes
+    Rlat = DOMAIN_EARTH_RADIUS_KM * np.sin(np.deg2rad(colat0))
+    return 2.0 * np.pi * (1.0 / 360.0) * Rlat
+
+
+def domain_scale_per_longitude():
+    """`dist_per_lon` of rectangular_domain: the length in km of a degree of a great circle of the 6371 km sphere."""
+    return 2.0 * np.pi * (1.0 / 360.0) * DOMAIN_EARTH_RADIUS_KM
+
+
+def reduced_latitude_sin_cos(latitudes):
+    """(sin u, cos u) of the reduced latitudes u = atan((1 - f) tan(lat)) on WGS84, as geodesic_distance_m
+    computes them for its end points."""
+    lat = np.asarray(latitudes, dtype=np.float64)
+    u = np.arctan((1.0 - WGS84_F) * np.tan(np.deg2rad(lat)))
+    return np.sin(u), np.cos(u)
+
+
 WGS84_A = 6378137.0                 # semi-major axis, m
 WGS84_F = 1.0 / 298.257223563       # flattening
 

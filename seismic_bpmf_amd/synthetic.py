@@ -106,6 +106,17 @@ def make_bp_geometry(grid, S, P=2, sr=50.0, seed=20260928, extent_km=(100.0, 100
                 sources=src, stations=sta)
 
 
+def geographic_coordinates(sources_km, origin=(30.0, 40.0)):
+    """(longitude, latitude, depth) of make_bp_geometry's `sources` (x east, y north, z down, km) placed with
+    their (0, 0) corner at `origin` = (longitude, latitude) in degrees: 111.19 km per degree of latitude, and
+    per degree of longitude times cos(origin latitude).  What BeamformerGPU.set_source_coordinates takes."""
+    src = np.asarray(sources_km, dtype=np.float64)
+    km_per_deg = 111.19
+    lat = origin[1] + src[:, 1] / km_per_deg
+    lon = origin[0] + src[:, 0] / (km_per_deg * np.cos(np.deg2rad(origin[1])))
+    return lon, lat, src[:, 2].copy()
+
+
 def phase_weights(S, C=3, P=2):
     """One-hot channel->phase map: component 0 (Z) -> P, the others -> S (nb6 cell 52)."""
     w = np.zeros((S, C, P), dtype=np.float32)

@@ -725,8 +725,78 @@ def _relocation_windows(features, starts, n_samples):
     return st.size, S, Cc, N, st
 
 
+def location_uncertainties_host(result, longitude, latitude, depth, uncertainty_method="spatial",
+                                source_id_offset=0, restricted_domain_side_km=100.0, effective_kT=0.33,
+                                gibbs_cutoff=0.25):
+    """The end of ``Event.relocate_beam`` (BPMF/dataset.py:2207-2245) for every event of a relocate_events
+    `result`, one after the other on the host -- the loop a user of relocate_events(uncertainties=False) writes,
+    and the yardstick of relocate_events(uncertainties=True).  `longitude`, `latitude`, `depth`: (K,) coordinates
+    of the plan's source rows.  Per event:
+      "spatial":  postprocess.rectangular_domain around the new epicentre, likelihood[e][domain],
+                  postprocess.compute_location_uncertainty;
+      "temporal": postprocess.gibbs_weights of maxbeam[e], the samples with a weight > gibbs_cutoff, their
+                  maxbeam_sources (minus `source_id_offset`) as the domain (dataset.py:2218-2227).
+    Device tensors of `result` are downloaded here.  Returns a dict of (E,) arrays: longitude, latitude, depth,
+    hunc, vunc (float64), n_domain (int64), and for "spatial" ``domain`` (E, K) bool."""
+    from . import postprocess as pp
+    if uncertainty_method not in ("spatial", "temporal"):
+        raise ValueError("uncertainty_method should be 'spatial' or 'temporal'")
+    spatial = uncertainty_method == "spatial"
+
+    def host(x):
+        return np.asarray(x.cpu() if hasattr(x, "cpu") else x)
+
+    lon, lat, dep = (np.asarray(x, dtype=np.float64) for x in (longitude, latitude, depth))
+    src = np.asarray(result["src_idx"], dtype=np.int64) - (0 if spatial else int(source_id_offset))
+    E = src.shape[0]
+    out = {k: np.zeros(E, np.float64) for k in ("longitude", "latitude", "depth", "hunc", "vunc")}
+    out["n_domain"] = np.zeros(E, np.int64)
+    if spatial:
+        like = host(result["likelihood"])
+        out["domain"] = np.zeros((E, lon.shape[0]), dtype=bool)
+    else:
+        maxbeam, sources = host(result["maxbeam"]), host(result["maxbeam_sources"])
+    for e in range(E):
+        lon0, lat0, dep0 = lon[src[e]], lat[src[e]], dep[src[e]]
+        if spatial:
+            domain = pp.rectangular_domain(lon0, lat0, lon, lat, side_km=restricted_domain_side_km)
+            weights = like[e][domain]
+            out["domain"][e] = domain
+        else:
+            gibbs = pp.gibbs_weights(maxbeam[e], effective_kT)
+            mask = gibbs > gibbs_cutoff
+            domain = sources[e][mask].astype(np.int64) - int(source_id_offset)
+            weights = gibbs[mask]
+        with np.errstate(invalid="ignore", divide="ignore"):
+            hunc, vunc = pp.compute_location_uncertainty(lon0, lat0, dep0, weights, lon[domain], lat[domain],
+                                                         dep[domain])
+        out["longitude"][e], out["latitude"][e], out["depth"][e] = lon0, lat0, dep0
+        out["hunc"][e], out["vunc"][e], out["n_domain"][e] = hunc, vunc, weights.shape[0]
+    return out
+
+
+def _uncertainty_arguments(beamformer, uncertainty_method, restricted_domain_side_km, effective_kT, gibbs_cutoff,
+                           domain_mask):
+    """Checks of relocate_events(uncertainties=True), made before anything touches a device."""
+    if getattr(beamformer, "_coord_tables", None) is None:
+        raise ValueError("uncertainties=True needs the coordinates of the sources: call "
+                         "beamformer.set_source_coordinates(longitude, latitude, depth) first")
+    if uncertainty_method == "spatial":
+        if not (np.isfinite(restricted_domain_side_km) and restricted_domain_side_km > 0):
+            raise ValueError("restricted_domain_side_km must be a positive number of kilometres")
+    else:
+        if domain_mask:
+            raise ValueError("domain_mask belongs to the spatial method (the temporal domain is a list of samples)")
+        if not (np.isfinite(effective_kT) and np.float32(effective_kT) > 0):
+            raise ValueError("effective_kT must be positive")
+        if not np.isfinite(gibbs_cutoff):
+            raise ValueError("gibbs_cutoff must be finite")
+
+
 def relocate_events(beamformer, features, weights_phases, uncertainty_method="spatial",
-                    out_of_bounds="flexible", starts=None, n_samples=None, columns=False, _chunk=None):
+                    out_of_bounds="flexible", starts=None, n_samples=None, columns=False, _chunk=None,
+                    uncertainties=False, restricted_domain_side_km=100.0, effective_kT=0.33, gibbs_cutoff=0.25,
+                    domain_mask=False):
     """The beamforming step of ``Event.relocate_beam`` (BPMF/dataset.py:2186-2245) for a BATCH of events in one
     call on a resident BeamformerGPU -- what tutorial notebook 6 does in a loop over every detected event, and
     what relocation_focus / relocation_likelihood do for one.  The events share the launches
@@ -741,17 +811,35 @@ def relocate_events(beamformer, features, weights_phases, uncertainty_method="sp
     Returns a dict: ``src_idx`` (E,) int64, ``time_idx`` (E,) int64, ``max_beam`` (E,) float32 on the host, and
       "spatial":  ``likelihood`` (E, K) float32 DEVICE tensor, row e = Beamformer._likelihood of
                   beam_e[:, time_idx[e]] (NaN row for a constant column); columns=True adds ``columns``, the raw
-                  beam columns.  Take likelihood[e, domain_e] to postprocess.compute_location_uncertainty.
+                  beam columns.
       "temporal": ``maxbeam`` (E, N) float32 and ``maxbeam_sources`` (E, N) int32 device tensors;
                   time_idx[e] = maxbeam[e].argmax(), src_idx[e] = maxbeam_sources[e, time_idx[e]].
     For every event the result is what relocation_focus / relocation_likelihood return for it alone, bit for
     bit, ties included (first maximum in source-major order).  An event whose maximum is not > 0 although its
     window is not all zero (negative features or weights) is redone on its volume by the per-event path.
-    Events run in chunks sized from the free device memory; the results do not depend on the chunks."""
+    Events run in chunks sized from the free device memory; the results do not depend on the chunks.
+
+    ``uncertainties=True`` finishes ``Event.relocate_beam`` (dataset.py:2207-2245) in the same call, on the device
+    (bpmf_bp_location_uncertainty_dev, csrc/bp_uncertainty.hip, per chunk behind the likelihood -- or the focus
+    for "temporal" -- on the same stream; still one synchronisation).  The beamformer needs its sources'
+    coordinates (``set_source_coordinates``), else ValueError.  The dict gains HOST arrays (E,): ``longitude``,
+    ``latitude``, ``depth`` of the new hypocentre, ``hunc`` and ``vunc`` in km (float64) -- the event's
+    hmax_unc = hmin_unc = hunc, vmax_unc = vunc -- and ``n_domain`` (int64), the number of sources (samples) they
+    average over: "spatial" the rectangle of `restricted_domain_side_km` around the epicentre
+    (postprocess.rectangular_domain, the same booleans), weighted by the likelihood; "temporal" the samples whose
+    Gibbs weight exp(-(max - maxbeam) / effective_kT) exceeds `gibbs_cutoff`.  ``domain_mask=True`` ("spatial")
+    adds ``domain``, the (E, K) bool device tensor of the rectangles.  location_uncertainties_host is the same
+    on the host, event by event: n_domain and the rectangles are equal, hunc and vunc agree to about 1e-14 km
+    (the numerators are float64 sums in a fixed order that does not depend on the batch; the denominator is the
+    reference's np.sum of the float32 weights, a float32 sum in NumPy's order, reproduced bit for bit).
+    With ``uncertainties=False`` the call is what it was: same launches, same keys."""
     if uncertainty_method not in ("spatial", "temporal"):
         raise ValueError("uncertainty_method should be 'spatial' or 'temporal'")
     if out_of_bounds not in ("strict", "flexible"):
         raise ValueError("out_of_bounds should be 'strict' or 'flexible'")
+    if uncertainties:
+        _uncertainty_arguments(beamformer, uncertainty_method, restricted_domain_side_km, effective_kT,
+                               gibbs_cutoff, domain_mask)
     E, S, Cc, N, st = _relocation_windows(features, starts, n_samples)
     bf = beamformer
     if S != bf.S:
@@ -773,6 +861,22 @@ def relocate_events(beamformer, features, weights_phases, uncertainty_method="sp
     res.update({"likelihood": like} if spatial else {"maxbeam": mbeam, "maxbeam_sources": marg})
     if cols is not None:
         res["columns"] = cols
+    unc = unc_n = dmask = unc_ws = None
+    if uncertainties:
+        unc = t.empty((5, E), dtype=t.float64, device=dev)     # hunc, vunc, longitude, latitude, depth
+        unc_n = t.empty(E, dtype=t.int32, device=dev)
+        dmask = t.empty((E, K), dtype=t.bool, device=dev) if spatial and domain_mask else None
+        unc_kw = dict(side_km=restricted_domain_side_km, effective_kT=effective_kT, gibbs_cutoff=gibbs_cutoff)
+
+        def unpack():
+            host = unc.cpu().numpy()
+            res.update(hunc=host[0].copy(), vunc=host[1].copy(), longitude=host[2].copy(), latitude=host[3].copy(),
+                       depth=host[4].copy(), n_domain=unc_n.cpu().numpy().astype(np.int64))
+            if dmask is not None:
+                res["domain"] = dmask
+
+        if E == 0:
+            unpack()
     if E == 0:
         return res
     wp = bf._dev(weights_phases, t.float32)
@@ -784,10 +888,14 @@ def relocate_events(beamformer, features, weights_phases, uncertainty_method="sp
     if _chunk is None:
         free = t.cuda.mem_get_info(dev)[0]
         per_event = (S * bf.P * N + 4 * N) * 4 + (0 if resident or st is not None else S * Cc * N * 4)
+        if uncertainties:                     # the compacted weights of the event's domain
+            per_event += (K if spatial else N) * 4
         _chunk = max(1, (free // 4) // per_event)
     chunk = int(max(1, min(_chunk, E, 65535)))
     ws = t.empty(max(bf.relocation_workspace_bytes(min(chunk, E - e0), N, Cc) for e0 in range(0, E, chunk)),
                  dtype=t.uint8, device=dev)
+    if uncertainties:
+        unc_ws = t.empty(bf.uncertainty_workspace_bytes(chunk, K if spatial else N), dtype=t.uint8, device=dev)
 
     def part(x, e0, e1):
         return None if x is None else x[e0:e1]
@@ -801,16 +909,24 @@ def relocate_events(beamformer, features, weights_phases, uncertainty_method="sp
         bf.relocate_batch(f, ev_stride, row_stride, sd, wp, e1 - e0, N, Cc, out_of_bounds, uncertainty_method, ws,
                           time_idx[e0:e1], src_idx[e0:e1], max_beam[e0:e1], part(like, e0, e1), part(cols, e0, e1),
                           part(mbeam, e0, e1), part(marg, e0, e1))
+        if uncertainties:
+            bf.location_uncertainty(uncertainty_method, e1 - e0, N, src_idx[e0:e1], unc_ws, unc[:, e0:e1],
+                                    unc_n[e0:e1], likelihood=part(like, e0, e1), maxbeam=part(mbeam, e0, e1),
+                                    maxbeam_sources=part(marg, e0, e1), max_beam=max_beam[e0:e1],
+                                    domain_mask=part(dmask, e0, e1), **unc_kw)
     del ws
     res["time_idx"] = time_idx.cpu().numpy().astype(np.int64)          # (the one synchronisation of the batch)
     res["src_idx"] = src_idx.cpu().numpy().astype(np.int64)
     res["max_beam"] = max_beam.cpu().numpy()
+    if uncertainties:
+        unpack()
     if not spatial:
         return res
     res["src_idx"] -= bf.source_id_offset          # rows of the volume, as np.unravel_index gives them
     # A maximum that is not > 0: the running maximum starts at (0, first source), so a volume whose largest
     # beam is 0 or negative does not show in the max-beam where its first maximum lies.  All-zero windows give
     # an all-zero volume, whose first maximum is (0, 0) as found; anything else goes through its volume.
+    redone = False
     for e in np.flatnonzero(~(res["max_beam"] > 0)):
         e = int(e)
         win = day[:, :, int(st[e]):int(st[e]) + N] if st is not None else bf._dev(features[e], t.float32)
@@ -825,6 +941,13 @@ def relocate_events(beamformer, features, weights_phases, uncertainty_method="sp
             cols[e] = col
         res["src_idx"][e], res["time_idx"][e], res["max_beam"][e] = k, ti, float(col[k])
         del vol
+        if uncertainties:                    # from the corrected row and likelihood
+            src_idx[e] = k + bf.source_id_offset
+            bf.location_uncertainty("spatial", 1, N, src_idx[e:e + 1], unc_ws, unc[:, e:e + 1], unc_n[e:e + 1],
+                                    likelihood=like[e:e + 1], domain_mask=part(dmask, e, e + 1), **unc_kw)
+            redone = True
+    if uncertainties and redone:
+        unpack()
     return res
 
 

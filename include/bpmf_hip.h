@@ -112,8 +112,12 @@ int bpmf_host_call_stats(double *out, int n);
  *     it: a straggler that writes the start of the piece k ms later, every time; out[10] of bpmf_host_call_stats)
  *   mf.split16 (off by default; CHANGES RESULTS within a stated tolerance: matched-filter numerators on the fp16
  *     matrix pipe from hi/lo splits of data and templates, three products, fp32 accumulation -- csrc/mf_split.h;
- *     |d cc_sum| <= 3e-7 * sum|w| measured, 2e-5 allowed by the north star; x 2.3-2.4 at configs[1]; templates of up
- *     to 2049 samples (in segments of at most 376); composes with the mf.compat_* switches; 1 leaves launches of fewer
+ *     |d cc_sum| <= 3e-7 * sum|w| measured, 2e-5 allowed by the north star; against its float64 definition: bit-equal
+ *     to the exact path where the split is exact, rms error 0.8-2.3 x the exact path's own elsewhere;
+ *     x 2.3-2.4 at configs[1]; TEMPLATES OF UP TO 2049 SAMPLES -- the one statement of that limit: it is the MFMA kernels' own (mf_uses_mfma in csrc/mf.hip: 4096
+ *     lags + the padded template within 24 staging registers of 256 threads), correlated in segments of at most 376
+ *     samples; a longer template runs the exact generic kernel, bit-identical to the oracle
+ *     (tests/test_gpu_split16_anchor.py pins both sides); composes with the mf.compat_* switches; 1 leaves launches of fewer
  *     than 128 (template, 8192-lag block) pairs to the exact kernel (latency-bound there), 2 takes every launch; enlarges
  *     bpmf_mf_workspace_bytes and what a prepared day holds: set it before the day's first call)
  *   and the result-changing upstream-compatibility switches (off by default; every one has

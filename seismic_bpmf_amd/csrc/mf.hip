@@ -1362,8 +1362,8 @@ extern "C" int bpmf_mf_run_dev(const float* d_templates, const int32_t* d_moveou
     const size_t off_hi = ranged ? std::min<size_t>((size_t)t_mf_off_hi, n_offsets) : n_offsets;
     if (off_hi <= off_lo) return 0;
     const bool first_piece = !(ranged && t_mf_continue);
-    // option mf.split16: the split-precision kernel takes every launch the MFMA kernels would take for templates of
-    // whatever length (in segments of at most 376 samples; under mf.compat_sqrt_norm its epilogue divides by sqrtf(E_t * E_d))
+    // option mf.split16: the split-precision kernel takes every launch the MFMA kernels would take (use_mfma: the
+    // template-length limit stated in include/bpmf_hip.h; in segments of at most 376 samples; under mf.compat_sqrt_norm its epilogue divides by sqrtf(E_t * E_d))
     // mf.split16 = 1 leaves small launches to the exact kernel (below SP_MIN_BLOCKS (template, 8192-lag block) pairs a
     // wave's chain of per-channel stagings is latency, not rate: configs[0], 88 pairs, ran 0.71x the exact kernel's speed, 176 pairs x 1.1-1.6:
     // profiles/r06_mf_split16.txt); = 2 takes the split kernel for every launch (the small shapes of the tests)
@@ -1488,7 +1488,7 @@ extern "C" int bpmf_mf_run_dev(const float* d_templates, const int32_t* d_moveou
             if (network_sum) BPMF_MF_LAUNCH(true, 17, 2); else BPMF_MF_LAUNCH(false, 17, 2);
         } else if (need_r <= 20 && need_t <= 5) {   // L <= 1041
             if (network_sum) BPMF_MF_LAUNCH(true, 20, 5); else BPMF_MF_LAUNCH(false, 20, 5);
-        } else {                                    // L <= 2065
+        } else {                                    // L <= 2049 (mf_uses_mfma: need_r <= 24)
             if (network_sum) BPMF_MF_LAUNCH(true, 24, 9); else BPMF_MF_LAUNCH(false, 24, 9);
         }
 #undef BPMF_MF_LAUNCH

@@ -86,6 +86,8 @@ __host__ __device__ inline int segment_len_of(int L)
     const int n = n_segments_of(L);
     return ((L + n - 1) / n + 7) / 8 * 8;
 }
+// What the segment arithmetic and the band images are sized for -- NOT the longest template mf.split16 takes: that
+// limit is stated once, in include/bpmf_hip.h (option mf.split16), and is the MFMA kernels' own (mf_uses_mfma, mf.hip).
 __host__ __device__ inline int max_template_len() { return 4096; }
 __host__ __device__ inline int band_e_dwords(int nks) { return 8 * nks + 32; }
 // first dword index >= the length of E that is 17 (mod 32)

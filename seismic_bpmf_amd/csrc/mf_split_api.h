@@ -12,7 +12,9 @@ namespace sp {
 size_t day_region_bytes(size_t N, size_t n_ch);
 size_t batch_region_bytes(size_t T, size_t n_ch, size_t L);
 
-// can this launch take the split kernel?  (templates of up to 4096 samples, in segments of at most 376; N < 2^30 - 8192)
+// can the split kernel's own arithmetic take this launch?  (segments of at most 376 samples, sized for 4096; N < 2^30 -
+// 8192.)  bpmf_mf_run_dev asks mf_uses_mfma first: the template-length limit of mf.split16 is the one stated in
+// include/bpmf_hip.h.
 bool usable(size_t L, size_t N);
 
 // once per day, behind bpmf_mf_prepare_data_dev's own kernels: channel maxima -> scales -> split planes

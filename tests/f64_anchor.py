@@ -22,6 +22,21 @@ BP, per beam:    gamma_(n_terms + C) sum |beta| |alpha| |f|  (a C-term chain ins
 In the exact regime (small integers, every partial sum below 2^24) numerators, energies and beams are exact
 in float32: BP must equal float64 bit for bit and the MF bound shrinks to 7u |cc|.
 
+MF under mf.split16 (mf_split_f64: what the split kernel computes, in float64; B_split bounds |kernel - cc|, cc the
+TRUE correlation above, not the split form).  With x' = x 2^s the scaled samples, hi = fp16(x'), rho = x' - hi,
+lo_t = fp16(rho_t), lo'_d = fp16(rho_d 2^11), hs = fp16(hi_t 2^-11), num = sum (hi_t hi_d + hs lo'_d + lo_t hi_d):
+    B_split = (E_rep + E_abs + E_acc) (1 + rho) + rho |cc|,   rho = gamma_L + 7u + E_term / |cc|
+    E_rep = (3 + 2^-10) 2^-22 A              the two fp16 roundings of each kept lo half and the lo_t lo_d term left out
+    E_abs = (1 + 2^-11) (2 * 2^-25 sum |d'| + 2^-36 sum |t'|) / (2^(s_t + s_d) sqrt(E_t E_d))
+                                             fp16 operands that are subnormal: lo_t, hs (absolute error 2^-25 each) and lo'_d
+    E_acc = gamma'_n_acc (1 + 2^-11)^2 (1 + 2^-10) A      [sum (|hi_t hi_d| + |hs lo'_d| + |lo_t hi_d|) is at most that]
+            n_acc = 3 * 16 * nks * n_seg exact products into one float32 accumulator in ANY order, 2u per addition
+            (gamma'_n = 2 n u / (1 - 2 n u)): the matrix pipe's summation order and rounding mode are not documented,
+            and truncation cannot be excluded
+    rho      the unchanged part of B: the chain of E_t, the normalisation, the prefix sums of E_d.
+Exact regime of the split (mf_split_exact_ok): every fp16 operand exact and zero or normal, every window's
+sum of |products| below 2^24 quanta -> the three products and every partial sum in any order are exact in float32.
+
 The build zeroes r_t r_d >= 1000 and the definition E_t E_d <= 1e-6: the same threshold up to rounding, so
 the definitions ASSERT that no active window has E_t E_d in [2.5e-7, 4e-6] -- a condition on the inputs.
 """
@@ -70,7 +85,16 @@ class MFRef:
 
 def mf_f64(templates, moveouts, weights, data, step=1, lags=None, exclusive_last_lag=False,
            range_all_channels=False, sequential_csum=False, exact=False):
-    """The definition at `lags` (all n_corr of them when None): O(len(lags) * L) per template-channel."""
+    """The definition at `lags` (all n_corr of them when None): O(len(lags) * L) per template-channel.
+    exact=True: integers of magnitude <= 3 (float32 exact throughout, B = 7u |cc|); exact="split": the wider
+    exact regime of mf_split_exact_ok (numerators exact on both paths; the float32 chain of E_t is not exact for wide
+    templates and keeps its term: B = (7u + gamma_L) |cc| there)."""
+    return _mf_eval(templates, moveouts, weights, data, step, lags, exclusive_last_lag, range_all_channels,
+                    sequential_csum, exact, None)
+
+
+def _mf_eval(templates, moveouts, weights, data, step, lags, exclusive_last_lag, range_all_channels,
+             sequential_csum, exact, split):
     tp32 = np.asarray(templates)
     T, S, C, L = tp32.shape
     mv = np.broadcast_to(np.asarray(moveouts).reshape(T, S, -1), (T, S, C)).astype(np.int64)
@@ -81,7 +105,9 @@ def mf_f64(templates, moveouts, weights, data, step=1, lags=None, exclusive_last
     lags = np.arange(n_corr) if lags is None else np.asarray(lags, dtype=np.int64)
     assert lags.size and lags.min() >= 0 and lags.max() < n_corr
     c_N = N if sequential_csum else CSUM_CHUNK + -(-N // CSUM_CHUNK)
-    if exact:
+    if exact == "split":
+        assert mf_split_exact_ok(tp32, data), "exact regime of the split: see mf_split_exact_ok"
+    elif exact:
         assert np.abs(data).max() <= 3 and np.abs(tp32).max() <= 3 and 9 * L < EXACT_LIMIT
         assert np.array_equal(data, np.round(data)) and np.array_equal(tp32, np.round(tp32))
     ref = MFRef()
@@ -89,14 +115,27 @@ def mf_f64(templates, moveouts, weights, data, step=1, lags=None, exclusive_last
     ref.active = w != 0
     ref.cc = np.zeros((T, lags.size, S, C))
     ref.B = np.zeros((T, lags.size, S, C))
+    ref.num = np.zeros((T, lags.size, S, C))            # the unscaled numerators sum_l t_l d_l
+    if split is not None:
+        # the three products of the split numerator, unscaled (hl: hs * lo'_d; hl_half: the same with lo'_d scaled by
+        # 2^10, the planted defect "lo_scale"), and B_split
+        ref.split_terms = {k: np.zeros_like(ref.cc) for k in ("hh", "lh", "hl", "hl_half")}
+        ref.split_den, ref.B_split = np.full_like(ref.cc, np.inf), np.zeros_like(ref.cc)
     ref.valid = np.zeros((T, lags.size), dtype=bool)
     ref.zero_windows = 0            # valid entries whose data window is all exact zeros (a data gap): cc = B = 0
-    idx_l = np.arange(L)
     for s in range(S):
         for c in range(C):
             if not ref.active[:, s, c].any():
                 continue
             d = data[s, c]
+            rows = np.lib.stride_tricks.sliding_window_view(d, L)          # rows[i] = d[i : i + L]
+            if split is not None:
+                sd = split_planes(d, SPLIT_LO_SCALE)
+                # (lo'_d scaled by 2^10 instead: the planted defect "lo_scale")
+                lo_half = (sd.rho * (SPLIT_LO_SCALE / 2)).astype(np.float16).astype(np.float64)
+                # (fp16 values: float32 holds them exactly and halves the bytes the windows are gathered from)
+                rows_hi, rows_lo, rows_lo_half = (np.lib.stride_tricks.sliding_window_view(x.astype(np.float32), L)
+                                                  for x in (sd.hi, sd.lo, lo_half))
             csum_total = sum(float(np.dot(x, x)) for x in (d[i:i + (1 << 22)].astype(np.float64)
                                                            for i in range(0, N, 1 << 22)))
             for t in range(T):
@@ -109,13 +148,22 @@ def mf_f64(templates, moveouts, weights, data, step=1, lags=None, exclusive_last
                 ref.valid[t] = ok
                 tmpl = tp32[t, s, c].astype(np.float64)
                 E_t = float(tmpl @ tmpl)
+                if exact == "split" and E_t / _quantum(tmpl) ** 2 >= EXACT_LIMIT:
+                    exact_B = (NORM_ROUNDINGS * U + gamma(L))          # (the float32 chain of E_t rounds)
+                else:
+                    exact_B = NORM_ROUNDINGS * U
+                if split is not None:
+                    st = split_planes(tmpl, 1.0)
+                    hs = (st.hi * (1.0 / SPLIT_LO_SCALE)).astype(np.float16).astype(np.float64)
+                    unscale = 2.0 ** -(st.s + sd.s)
+                    n_acc = 3 * 16 * split_nks(L) * split_n_segments(L)
                 sel = np.flatnonzero(ok)
-                for j0 in range(0, sel.size, 2048):
-                    j = sel[j0:j0 + 2048]
+                for j0 in range(0, sel.size, 256):
+                    j = sel[j0:j0 + 256]
                     starts = lags[j] * step + mv[t, s, c]
                     assert starts.min() >= 0 and starts.max() + L <= N
-                    win = d[starts[:, None] + idx_l[None, :]].astype(np.float64)
-                    E_d = (win * win).sum(axis=1)
+                    win = rows[starts].astype(np.float64)
+                    E_d = np.einsum("ij,ij->i", win, win)
                     prod = E_t * E_d
                     ref.zero_windows += int((E_d == 0).sum())
                     in_window = (prod >= GUARD_WINDOW[0]) & (prod <= GUARD_WINDOW[1])
@@ -123,19 +171,209 @@ def mf_f64(templates, moveouts, weights, data, step=1, lags=None, exclusive_last
                         f"input condition: E_t*E_d = {prod[in_window][0]:.3e} inside the guard window (t={t}, s={s}, c={c})"
                     keep = prod > GUARD
                     den = np.sqrt(np.where(keep, prod, 1.0))
-                    cc = np.where(keep, (win @ tmpl) / den, 0.0)
+                    num = win @ tmpl
+                    cc = np.where(keep, num / den, 0.0)
+                    a_sum, d_sum = (np.abs(win) @ np.stack([np.abs(tmpl), np.ones(L)], axis=1)).T
+                    A = np.where(keep, a_sum / den, 0.0)
+                    E_rel = 0.5 * c_N * 2.0 ** -53 * csum_total / np.where(keep, E_d, 1.0)
                     if exact:
-                        B = NORM_ROUNDINGS * U * np.abs(cc)
+                        B = exact_B * np.abs(cc)
                     else:
-                        A = np.where(keep, (np.abs(win) @ np.abs(tmpl)) / den, 0.0)
-                        E_term = 0.5 * np.abs(cc) * c_N * 2.0 ** -53 * csum_total / np.where(keep, E_d, 1.0)
-                        B = np.where(keep, gamma(L) * (A + np.abs(cc)) + NORM_ROUNDINGS * U * np.abs(cc) + E_term, 0.0)
+                        B = np.where(keep, gamma(L) * (A + np.abs(cc)) + (NORM_ROUNDINGS * U + E_rel) * np.abs(cc), 0.0)
                     ref.cc[t, j, s, c] = cc
                     ref.B[t, j, s, c] = B
-    aw = np.abs(w)[:, None]
-    ref.net = (ref.cc * w[:, None]).sum(axis=(2, 3))
-    ref.B_net = (ref.B * aw).sum(axis=(2, 3)) + gamma(S * C) * (np.abs(ref.cc) * aw).sum(axis=(2, 3))
+                    ref.num[t, j, s, c] = num
+                    if split is not None:
+                        w_hi, w_lo = rows_hi[starts].astype(np.float64), rows_lo[starts].astype(np.float64)
+                        hh, lh = (w_hi @ np.stack([st.hi, st.lo], axis=1)).T
+                        hl = w_lo @ hs
+                        hl_half = rows_lo_half[starts].astype(np.float64) @ hs if split == "defects" else hl
+                        # sum of |products|: |hi| <= (1 + 2^-11) |x'|, |lo_t| and |hs lo'_d| / |hi_t| <= (1 + 2^-11) 2^-11 |x'|
+                        p_abs = (1 + 2.0 ** -11) ** 2 * (1 + 2.0 ** -10) * a_sum / unscale
+                        e_abs = (1 + 2.0 ** -11) * (2 * 2.0 ** -25 * d_sum * 2.0 ** -st.s
+                                                   + 2.0 ** -36 * np.abs(tmpl).sum() * 2.0 ** -sd.s)
+                        rho = gamma(L) + NORM_ROUNDINGS * U + E_rel
+                        e_num = SPLIT_C_REP * A + (e_abs + gamma(2 * n_acc) * p_abs * unscale) / den
+                        for k, v in (("hh", hh), ("lh", lh), ("hl", hl), ("hl_half", hl_half)):
+                            ref.split_terms[k][t, j, s, c] = v * unscale
+                        ref.split_den[t, j, s, c] = np.where(keep, den, np.inf)
+                        ref.B_split[t, j, s, c] = np.where(keep, e_num * (1 + rho) + rho * np.abs(cc), 0.0)
+    ref.net, ref.B_net = _mf_network(ref.cc, ref.cc, ref.B, w)
     return ref
+
+
+def _mf_network(cc, cc_true, B, w):
+    """The weighted sum of `cc` and the bound of a float32 fmaf chain over the S * C channels on per-channel values
+    that lie within B of cc_true."""
+    S, C = w.shape[1:]
+    aw = np.abs(w)[:, None]
+    return ((cc * w[:, None]).sum(axis=(2, 3)),
+            (B * aw).sum(axis=(2, 3)) + gamma(S * C) * (np.abs(cc_true) * aw).sum(axis=(2, 3)))
+
+
+# ----------------------------------------------------------- matched filter under mf.split16 ---
+# Written from the header comment of csrc/mf_split.h and DESIGN.md s4 "MF, split precision", not from the kernel.
+SPLIT_S_TARGET, SPLIT_S_CLAMP = 14, 60          # a channel's largest magnitude scaled into [2^14, 2^15); |s| <= 60
+SPLIT_LO_SCALE = 2.0 ** 11                      # the data's lo halves are stored times 2^11, paired with fp16(hi_t 2^-11)
+SPLIT_SEGMENT = 376                             # samples one band image holds; longer templates in equal segments
+SPLIT_C_REP = (3 + 2.0 ** -10) * 2.0 ** -22     # E_rep / A (module docstring)
+SPLIT_DROPS = ("hi_lo", "lo_hi", "lo_scale")
+
+
+def split_n_segments(L):
+    return -(-L // SPLIT_SEGMENT)
+
+
+def split_nks(L):
+    """k-steps of 16 per segment: segments of equal length, a multiple of 8, each with a band of seg_len + 38."""
+    seg_len = -(-(-(-L // split_n_segments(L))) // 8) * 8
+    return (seg_len + 38 + 15) // 16
+
+
+class SplitPlanes:
+    """s: the scale exponent; hi = fp16(x 2^s); lo = fp16((x 2^s - hi) * lo_scale); rho = x 2^s - hi, as float64."""
+
+
+def split_planes(x, lo_scale):
+    x = np.asarray(x, dtype=np.float64)
+    p = SplitPlanes()
+    m = float(np.abs(x).max(initial=0.0))
+    p.s = 0
+    if m > 0 and np.isfinite(m):
+        p.s = int(np.clip(SPLIT_S_TARGET - (np.frexp(m)[1] - 1), -SPLIT_S_CLAMP, SPLIT_S_CLAMP))
+    p.scaled = x * 2.0 ** p.s
+    with np.errstate(over="ignore"):
+        p.hi = p.scaled.astype(np.float16).astype(np.float64)
+    assert np.isfinite(p.hi).all(), "input condition: a scaled sample beyond fp16 (the clamp |s| <= 60 is active)"
+    p.rho = p.scaled - p.hi
+    p.lo = (p.rho * lo_scale).astype(np.float16).astype(np.float64)
+    return p
+
+
+def mf_split_f64(templates, moveouts, weights, data, step=1, lags=None, exclusive_last_lag=False,
+                 range_all_channels=False, sequential_csum=False, exact=False, drop=None, _true=None):
+    """What mf.split16 computes, in float64: .cc / .net / .num the split form (norms, guard, lag ranges and the
+    weighted sum as in mf_f64), .B / .B_net = B_split, the bound of |kernel - TRUE cc| (module docstring), .true the
+    mf_f64 result at the same lags.  `drop` plants a defect IN THIS DEFINITION for the sensitivity tests: "hi_lo" /
+    "lo_hi" leave a product out, "lo_scale" scales the data's lo halves by 2^10 against the 2^-11 of hs (pass the
+    result's .true of a call with a `drop` as `_true` and the next variant costs nothing)."""
+    assert drop is None or drop in SPLIT_DROPS
+    true = _true or _mf_eval(templates, moveouts, weights, data, step, lags, exclusive_last_lag, range_all_channels,
+                             sequential_csum, exact, "defects" if drop else "plain")
+    terms = true.split_terms
+    ref = MFRef()
+    ref.true, ref.lags, ref.step, ref.w, ref.active, ref.valid = true, true.lags, step, true.w, true.active, true.valid
+    ref.zero_windows = true.zero_windows
+    ref.num = terms["hh"] + (0.0 if drop == "lo_hi" else terms["lh"]) + \
+        (0.0 if drop == "hi_lo" else terms["hl_half" if drop == "lo_scale" else "hl"])
+    ref.cc, ref.B = ref.num / true.split_den, true.B_split
+    ref.net, ref.B_net = _mf_network(ref.cc, true.cc, ref.B, true.w)
+    return ref
+
+
+def mf_split_anchor(sref):
+    """The reference mf_compare judges a split16 KERNEL by: the true correlation with B_split around it."""
+    ref = MFRef()
+    ref.lags, ref.step, ref.w, ref.active, ref.valid = sref.lags, sref.step, sref.w, sref.active, sref.valid
+    ref.cc, ref.net, ref.B, ref.B_net = sref.true.cc, sref.true.net, sref.B, sref.B_net
+    return ref
+
+
+def mf_split_lags(args, step, seed, n_random=2400, extra=(), **range_kw):
+    """The sampled lags of a split16 case: first and last valid lag of every template with their neighbours and the
+    tail behind, the neighbours of multiples of 1024, 2048 and 8192 (tile, wave and workgroup of the split kernel),
+    `extra`, and seeded random ones -- more than 2000 in all."""
+    tp, mv, w, d = args
+    N, L = d.shape[-1], tp.shape[-1]
+    rg = [mf_lag_range(mv[t], w[t], N, L, step, **range_kw) for t in range(tp.shape[0])]
+    lags = edge_sample((N - L) // step + 1, [r[0] for r in rg] + list(extra), [r[1] for r in rg], n_random, seed,
+                       multiples=(1024, 2048, 8192))
+    assert lags.size >= min(2000, n_random)
+    return lags
+
+
+def mf_rms_ratio(got, exact_path, sref, network_sum, what="MF split16"):
+    """The sharp check of a split16 result: per channel (per template row for network sums), over the sampled valid
+    lags, rms(got - cc) / rms(exact_path - cc) with cc the true float64 correlation and `exact_path` the float32
+    chain's result (the oracle's) at the same lags.  Returns the ratios (NaN where the exact path's error is 0:
+    there `got` must have none either, which is asserted)."""
+    true = sref.true
+    want = true.net if network_sum else true.cc
+    got, exact_path = np.asarray(got, np.float64), np.asarray(exact_path, np.float64)
+    assert got.shape == want.shape == exact_path.shape, (got.shape, want.shape, exact_path.shape)
+    valid = sref.valid if network_sum else sref.valid[:, :, None, None] & np.ones(want.shape, bool)
+    n = np.maximum(valid.sum(axis=1), 1)
+    rms_got = np.sqrt((np.where(valid, got - want, 0.0) ** 2).sum(axis=1) / n)
+    rms_exact = np.sqrt((np.where(valid, exact_path - want, 0.0) ** 2).sum(axis=1) / n)
+    assert not rms_got[rms_exact == 0].any(), f"{what}: an error where the exact path has none"
+    with np.errstate(invalid="ignore", divide="ignore"):
+        ratio = np.where(rms_exact > 0, rms_got / rms_exact, np.nan)
+    return ratio, rms_exact
+
+
+def mf_rms_require(got, exact_path, sref, network_sum, K, what):
+    ratio, _ = mf_rms_ratio(got, exact_path, sref, network_sum, what)
+    worst = float(np.nanmax(ratio)) if np.isfinite(ratio).any() else 0.0
+    print(f"f64-anchor {what}: rms(kernel - f64) / rms(exact path - f64) worst {worst:.3f}, "
+          f"median {float(np.nanmedian(ratio)) if worst else 0.0:.3f} (K = {K})")
+    assert worst <= K, f"{what}: rms ratio {worst:.3f} > K = {K}"
+    return worst
+
+
+def _quantum(x):
+    """The largest power of two that divides every non-zero element (1 for none)."""
+    x = np.asarray(x, dtype=np.float64).ravel()
+    x = x[x != 0]
+    if not x.size:
+        return 1.0
+    m, e = np.frexp(x)
+    mi = np.abs(m * 2.0 ** 53).astype(np.int64)
+    tz = np.frexp((mi & -mi).astype(np.float64))[1] - 1
+    return 2.0 ** int((e - 53 + tz).min())
+
+
+FP16_MIN_NORMAL = 2.0 ** -14
+
+
+def mf_split_exact_ok(templates, data):
+    """The exact regime of mf.split16.  Per template channel and data channel: hi + lo reproduce the scaled sample
+    (nothing is left for an error term), hs = hi_t 2^-11 exactly, every fp16 operand is zero or normal, and with q_t,
+    q_d the quanta of the two channels every window -- at every offset of the trace -- has
+    sum_l (|hi_t hi_d| + |hs lo'_d| + |lo_t hi_d|) < 2^24 q_t q_d: every product and every partial sum in any order is
+    an integer multiple of q_t q_d below 2^24 of them, exact in float32.  Also sum d^2 < 2^53 q_d^2 (the prefix sums)."""
+    tp = np.asarray(templates)
+    d = np.asarray(data)
+    T, S, C, L = tp.shape
+    N = d.shape[-1]
+    nfft = 1 << int(np.ceil(np.log2(N + L)))
+
+    def normal(*planes):
+        return all(((x == 0) | (np.abs(x) >= FP16_MIN_NORMAL)).all() for x in planes)
+
+    for s in range(S):
+        for c in range(C):
+            sd = split_planes(d[s, c], SPLIT_LO_SCALE)
+            if not (np.array_equal(sd.lo, sd.rho * SPLIT_LO_SCALE) and normal(sd.hi, sd.lo)):
+                return False
+            q_d = _quantum(np.concatenate([sd.hi, sd.rho]))
+            if float((sd.scaled / q_d) @ (sd.scaled / q_d)) >= 2.0 ** 53:
+                return False
+            f_hi, f_lo = (np.fft.rfft(np.abs(x) / q_d, nfft) for x in (sd.hi, sd.rho))
+            for t in range(T):
+                st = split_planes(tp[t, s, c], 1.0)
+                hs = (st.hi / SPLIT_LO_SCALE).astype(np.float16).astype(np.float64)
+                if not (np.array_equal(st.lo, st.rho) and np.array_equal(hs * SPLIT_LO_SCALE, st.hi)
+                        and normal(st.hi, st.lo, hs)):
+                    return False
+                q_t = _quantum(np.concatenate([st.hi, st.rho]))
+                # sum_l a_l b_(i + l) at every offset i, in quanta (integers: the FFT's rounding is rounded away, and
+                # one quantum of margin is left for it)
+                a_hi, a_lo = np.abs(st.hi) / q_t, np.abs(st.rho) / q_t
+                corr = np.fft.irfft(f_hi * np.conj(np.fft.rfft(a_hi + a_lo, nfft))
+                                    + f_lo * np.conj(np.fft.rfft(a_hi, nfft)), nfft)[:N - L + 1]
+                if np.round(corr).max(initial=0.0) + 1 >= EXACT_LIMIT:
+                    return False
+    return True
 
 
 class Report:
@@ -317,16 +555,17 @@ def bp_compare_max(m, a, ref, first_computed=False, what="BP max"):
 EDGE_MULTIPLES = (128, 256, 512, 2048, 8192)
 
 
-def edge_sample(n, firsts, lasts, n_random, seed, per_multiple=12, tail=24):
+def edge_sample(n, firsts, lasts, n_random, seed, per_multiple=12, tail=24, multiples=EDGE_MULTIPLES):
     """Sorted unique indices in [0, n): 0 and n - 1; every `firsts` / `lasts` index (first / last valid lag or
     sample) with its neighbours, and `tail` indices behind each `lasts` (the strict tail); the neighbours
-    -1, 0, +1 of `per_multiple` multiples of 128, 256, 512, 2048 and 8192 spread over the axis; seeded random."""
+    -1, 0, +1 of `per_multiple` multiples of 128, 256, 512, 2048 and 8192 (or of `multiples`) spread over the axis;
+    seeded random."""
     idx = [0, n - 1]
     for x in list(firsts) + list(lasts):
         idx += [x - 1, x, x + 1]
     for x in lasts:
         idx += list(range(x + 1, x + 1 + tail)) + [(x + n) // 2]
-    for m in EDGE_MULTIPLES:
+    for m in multiples:
         n_mult = (n - 1) // m
         for q in np.unique(np.linspace(1, max(1, n_mult), per_multiple).astype(np.int64)):
             idx += [q * m - 1, q * m, q * m + 1]
@@ -395,6 +634,129 @@ def mf_case(regime, L, N, step, seed, T=2, S=2, C=3, mv_lo=-70, mv_hi=400):
         dead = 1 + int(np.flatnonzero(w.reshape(T, -1)[T - 1, 1:] != 0)[0])
         tp.reshape(T, n_ch, L)[T - 1, dead] = 0.0
     return (tp.astype(np.float32), mv.astype(np.int32), w.astype(np.float32), d.astype(np.float32))
+
+
+SPLIT_EXACT_REGIMES = ("int", "int_wide_data", "int_wide_templates")
+SPLIT_GENERAL_REGIMES = ("noise", "scaled", "glitch")
+# which planted defect (mf_split_f64's `drop`) each exact regime exposes: "int" has no lo halves at all
+SPLIT_EXACT_DROPS = {"int": (), "int_wide_data": ("hi_lo", "lo_scale"), "int_wide_templates": ("lo_hi",)}
+WIDE_MAX_L = 682                                 # 3 * (2 * 4096 + 3) * L < 2^24
+
+
+def mf_split_case(regime, L, N, step, seed, T=3, S=2, C=3):
+    """Inputs of one mf.split16 case (T * S * C = 18 template channels): 16 live ones whose moveouts hold every
+    remainder mod 8 with both signs, one zero-weight channel with a moveout beyond every weighted one, one dead
+    (all-zero) weighted template channel, a data gap of exact zeros; the most negative weighted moveout of every
+    template is no multiple of the step.
+    Exact regimes (mf_split_exact_ok), every channel times its own power of two (data 2^7, 1, 2^-9; templates 2^-9, 1,
+    2^11): "int" integers in -3..3 (hi * hi only); "int_wide_data" data 4096 a + b, b in -3..3, a in -2..2 and
+    templates in -3..3 -- a in -1..1 and templates in -1..1 beyond L = 682 -- (hi_t * lo_d); "int_wide_templates" its
+    mirror image (lo_t * hi_d).
+    General regimes: "noise"; "scaled" (mf_case's: per-channel scales 1e-6..1e4, a glitch of 3e4 sigma); "glitch" (a
+    sample of 3e4 sigma in unit noise, and a channel at 1e-7 whose last sample is 1 -- every other sample of it 2^-23 of
+    the channel's maximum, lo halves in fp16's subnormal range unless stored scaled -- with its templates at 1e6)."""
+    assert T * S * C == 18 and L >= 8
+    rng = np.random.default_rng(seed)
+    n_ch = S * C
+    if regime in SPLIT_EXACT_REGIMES:
+        small, a_max = (3, 2) if L <= WIDE_MAX_L else (1, 1)
+
+        def ints(shape, wide):
+            b = rng.integers(-3, 4, shape) if wide else rng.integers(-small, small + 1, shape)
+            return (4096 * rng.integers(-a_max, a_max + 1, shape) * wide + b).astype(np.float64)
+
+        if regime == "int":
+            small = 3
+        tp = ints((T, S, C, L), regime == "int_wide_templates")
+        d = ints((S, C, N), regime == "int_wide_data")
+        d *= np.resize([2.0 ** 7, 1.0, 2.0 ** -9], n_ch).reshape(S, C, 1)
+        tp *= np.resize([2.0 ** -9, 1.0, 2.0 ** 11], n_ch).reshape(1, S, C, 1)
+        w = rng.integers(1, 3, (T, S, C)).astype(np.float64)
+    else:
+        tp, d = rng.standard_normal((T, S, C, L)), rng.standard_normal((S, C, N))
+        w = rng.uniform(0.1, 1.0, (T, S, C))
+        if regime == "scaled":
+            d[S - 1, C - 1, N // 3] = 3e4
+            d *= np.resize([1e-6, 1e-3, 1e-1, 1.0, 1e2, 1e4], n_ch).reshape(S, C, 1)
+            tp *= np.resize([1e-3, 1e3, 1e1, 1.0, 1e-2, 1e-4], n_ch).reshape(1, S, C, 1)
+        elif regime == "glitch":
+            d[0, 1, N // 3] = 3e4
+            d[1, 1] *= 1e-7
+            d[1, 1, N - 1] = 1.0        # (the last sample: the prefix sums in front of it, and so the exact path's window
+                                        #  norms, stay accurate -- what the rms ratio is measured against)
+            tp[:, 1, 1] *= 1e6
+        else:
+            assert regime == "noise"
+    # the 16 live moveouts: remainder r = 0..7, one positive (8 k + r) and one negative (-8 k + r) each, the negative
+    # ones dealt over the templates
+    pos = list(rng.permutation([8 * int(rng.integers(1, 50)) + r for r in range(8)]))
+    neg = list(rng.permutation([-8 * int(rng.integers(2, 10)) + r for r in range(8)]))
+    mv = np.zeros((T, n_ch), dtype=np.int64)
+    flat_w = w.reshape(-1)
+    zero_w, dead = 0 * n_ch + 3 % n_ch, (T - 1) * n_ch + 1            # (template 0, channel 3), (template T - 1, channel 1)
+    for t in range(T):
+        live = [i for i in range(n_ch) if t * n_ch + i not in (zero_w, dead)]
+        n_neg = -(-(len(neg) * len(live)) // (len(neg) + len(pos)))
+        vals = [neg.pop() for _ in range(n_neg)] + [pos.pop() for _ in range(len(live) - n_neg)]
+        mv[t, live] = rng.permutation(vals)
+        k = live[int(np.argmin(mv[t, live]))]
+        if mv[t, k] % step == 0:                                 # first valid lag off the step grid (same remainder mod 8)
+            mv[t, k] -= 8
+    assert not pos and not neg
+    mv.reshape(-1)[dead] = 17
+    flat_w[zero_w] = 0.0
+    mv.reshape(-1)[zero_w] = mv.min() - 333
+    g0 = N // 2
+    d[0, 0, g0:g0 + L + 50] = 0.0                                # a data gap: 51 windows of exact zeros
+    tp.reshape(T * n_ch, L)[dead] = 0.0
+    mv = mv.reshape(T, S, C)
+    res = set((int(m) % 8, bool(m < 0)) for i, m in enumerate(mv.ravel()) if i not in (zero_w, dead))
+    assert len(res) == 16, "every remainder mod 8 with both signs among the live moveouts"
+    return (tp.astype(np.float32), mv.astype(np.int32), w.astype(np.float32), d.astype(np.float32))
+
+
+# The shapes of tests/test_gpu_split16_anchor.py, which tests/test_split16_definition.py walks on the CPU.
+SPLIT_N = 20011                                  # > 8192 + L: three lag blocks; no multiple of 8: a partial last q-chunk
+SPLIT_MAX_L = 2049                               # the longest template of the MFMA kernels (include/bpmf_hip.h)
+SPLIT_LENGTHS = (8, 32, 100, 257, 376, 377, 379, 752, 753, 1040, 2040, SPLIT_MAX_L)
+SPLIT_STEP3_LENGTHS = (32, 257, 379, 1040)       # step 3 in the host-call tests (1 at the other lengths)
+SPLIT_RESIDENT_LENGTHS = (376, 753)              # MatchedFilterGPU on a prepared day, with the other step
+SPLIT_SWITCH_SHAPES = ((100, 1), (379, 3))       # (L, step) of the mf.compat_* tests, regimes "noise" and "scaled"
+# Allowed rms(kernel - f64) / rms(exact float32 path - f64) per template length: K = 3 x SPLIT_RMS_MEASURED, the worst
+# ratio of any channel, regime, step and entry point at that length on an MI355X (DESIGN.md s3,
+# profiles/split16_anchor.txt); the factor 3 covers the spread of an rms over ~2000 samples from seed to seed and an
+# accumulation order that changes with the k-step and segment counts.  tests/test_split16_definition.py holds K to the
+# sensitivity condition: every planted defect of the definition exceeds K by a factor of 8 at least.
+SPLIT_RMS_MEASURED = {8: 2.268, 32: 1.218, 100: 0.954, 257: 0.887, 376: 0.862, 377: 0.828, 379: 0.876, 752: 0.863,
+                      753: 0.801, 1040: 0.814, 2040: 0.787, 2049: 0.815}
+SPLIT_RMS_K = {L: round(3 * r, 1) for L, r in SPLIT_RMS_MEASURED.items()}
+assert tuple(SPLIT_RMS_K) == SPLIT_LENGTHS
+
+
+def split_exact_seed(L):
+    return 2000 + L
+
+
+def split_general_seed(L):
+    return 3000 + L
+
+
+def split_step_of(L):
+    return 3 if L in SPLIT_STEP3_LENGTHS else 1
+
+
+def split_gpu_cases():
+    """(regime, L, step) of every case the GPU tests run (the compat switches add lag-range rules, not inputs)."""
+    cases = [(r, L, split_step_of(L)) for L in SPLIT_LENGTHS for r in SPLIT_EXACT_REGIMES + SPLIT_GENERAL_REGIMES]
+    cases += [(r, L, 4 - split_step_of(L)) for L in SPLIT_RESIDENT_LENGTHS
+              for r in ("int_wide_data", "int_wide_templates", "glitch")]
+    cases += [(r, L, step) for L, step in SPLIT_SWITCH_SHAPES for r in ("noise", "scaled")]
+    return sorted(set(cases), key=lambda x: (x[1], x[2], x[0]))
+
+
+def split_glitch_lags(L, step):
+    """Lags whose windows hold the sample of 3e4 sigma of the "scaled" and "glitch" regimes (at N // 3)."""
+    return ((SPLIT_N // 3 - L // 2) // step, (SPLIT_N // 3 - L) // step, (SPLIT_N // 3) // step)
 
 
 def mf_dead_channels(templates, ref):

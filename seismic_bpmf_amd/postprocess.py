@@ -685,9 +685,11 @@ def geodesic_distance_m(lon0, lat0, lon, lat, max_iter=200, tol=1e-12, nonconver
     millimetre of GeographicLib for every pair that is not nearly antipodal.  Vincenty's iteration does not
     converge for pairs within about half a degree of antipodal, where GeographicLib still returns a length:
     `nonconverged="raise"` (default) raises ValueError rather than return a wrong length;
-    `nonconverged="antipodal"` gives those pairs pi (a + b) / 2 = 20 020.7 km -- every geodesic between nearly
-    antipodal points is between pi b = 20 003.9 and pi a = 20 037.5 km long, so the value is within 17 km
-    (0.09 %) of the true length -- and leaves every other pair exact.
+    `nonconverged="antipodal"` gives those pairs pi (a + b) / 2 = 20 003.917 km and leaves every other pair exact.
+    (pi b = 19 970.3, pi a = 20 037.5 km.)  Exact antipodes are joined over a pole by half a meridian,
+    20 003.931 km: for them the value is 14 m short.  Any other pair the iteration gives up on has its second point
+    within about 180 f = 0.6 degrees, some 70 km, of the antipode of its first, so by the triangle inequality its
+    true length is within that of the half meridian, and the value within about 70 km (0.35 %) of the true length.
     Host code (float64 NumPy): a domain has a few thousand sources."""
     if nonconverged not in ("raise", "antipodal"):
         raise ValueError("nonconverged must be 'raise' or 'antipodal'")
@@ -743,9 +745,9 @@ def compute_location_uncertainty(event_longitude, event_latitude, event_depth, l
     event and their mean absolute depth difference.  `source_*`: the coordinates of the sources OF THE
     DOMAIN (the reference indexes its grid with `domain`), `likelihood`: theirs.
     One limitation against cartopy / GeographicLib: a source within about half a degree of the event's
-    ANTIPODE (never the case for a regional source grid) gets the length pi (a + b) / 2, within 17 km (0.09 %)
-    of its true geodesic distance, instead of failing the whole relocation (geodesic_distance_m,
-    nonconverged="antipodal"); every other distance is exact to a fraction of a millimetre."""
+    ANTIPODE (never the case for a regional source grid) gets the length pi (a + b) / 2 = 20 003.917 km, within
+    about 70 km (0.35 %) of its true geodesic distance (14 m for the antipode itself), instead of failing the whole
+    relocation (geodesic_distance_m, nonconverged="antipodal"); every other distance is exact to a fraction of a millimetre."""
     d_km = geodesic_distance_m(event_longitude, event_latitude, source_longitude, source_latitude,
                                nonconverged="antipodal") / 1000.0
     depth_diff = np.abs(float(event_depth) - np.asarray(source_depth, dtype=np.float64))

@@ -339,6 +339,8 @@ int bpmf_bp_unpack_max_dev(const uint64_t *d_packed, size_t N, int as_signed,
  * equals the reference's per-template loop bit for bit.  The caller symmetrises ((out + out^T)/2,
  * dataset.py:4833-4834).
  *   d_waveforms (T,S,C,Lw) f32   d_base_weights (T,S,C) f32   d_pair_mask (T,T) u8   d_out (T,T) f32
+ * Limits, checked before anything is launched or written (-1, d_out untouched): Lw > 2 max_lag, max_lag <= 31, and
+ * 4 (Lw + 8 (2 max_lag + 1) + 8 S C) <= 65536 bytes -- one channel with its CCs against a tile of 8 templates in LDS.
  */
 size_t bpmf_intertemplate_workspace_bytes(size_t T, size_t S, size_t C, size_t max_lag);
 int bpmf_intertemplate_cc_dev(const float *d_waveforms, const float *d_base_weights,

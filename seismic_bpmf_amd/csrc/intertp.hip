@@ -222,12 +222,8 @@ extern "C" int bpmf_intertemplate_cc_dev(const float* d_waveforms, const float* 
         set_error("bpmf_intertemplate_cc_dev: workspace too small");
         return -1;
     }
-    float* r_t = (float*)d_workspace;
-    float* r_d = (float*)((char*)d_workspace + align_up(n_rows * sizeof(float), 256));
-    intertp_norms_kernel<<<dim3((unsigned)((n_rows + 127) / 128)), dim3(128), 0, stream>>>(
-        d_waveforms, (int)n_rows, (int)Lw, (int)max_lag, r_t, r_d);
-    BPMF_LAUNCH_CHECK();
-    // channels of t staged per pass: as many as fit beside the CC and product buffers in 64 KB
+    // channels of t staged per pass: as many as fit beside the CC and product buffers in 64 KB (decided before anything
+    // is launched or written: a problem the kernel cannot take leaves the output untouched)
     const size_t fixed = (size_t)ITP_UB * n_ch * sizeof(float);
     size_t ch_chunk = n_ch;
     auto need = [&](size_t cc) { return (cc * Lw + (size_t)ITP_UB * cc * n_lag) * sizeof(float) + fixed; };
@@ -236,6 +232,14 @@ extern "C" int bpmf_intertemplate_cc_dev(const float* d_waveforms, const float* 
         set_error("bpmf_intertemplate_cc_dev: one channel of %zu samples does not fit the LDS budget", Lw);
         return -1;
     }
+    // option debug.poison_output (tests): an entry no kernel writes comes back as NaN
+    if (option(OPT_DEBUG_POISON_OUTPUT) != 0)
+        BPMF_HIP_CHECK(hipMemsetAsync(d_out, 0xFF, T * T * sizeof(float), stream));
+    float* r_t = (float*)d_workspace;
+    float* r_d = (float*)((char*)d_workspace + align_up(n_rows * sizeof(float), 256));
+    intertp_norms_kernel<<<dim3((unsigned)((n_rows + 127) / 128)), dim3(128), 0, stream>>>(
+        d_waveforms, (int)n_rows, (int)Lw, (int)max_lag, r_t, r_d);
+    BPMF_LAUNCH_CHECK();
     dim3 grid((unsigned)((T + ITP_UB - 1) / ITP_UB), (unsigned)T);
     intertp_cc_kernel<<<grid, dim3(ITP_THREADS), need(ch_chunk), stream>>>(
         d_waveforms, d_base_weights, d_pair_mask, r_t, r_d, (int)T, (int)n_ch, (int)Lw, (int)max_lag,

@@ -1018,19 +1018,34 @@ def factorise_pair_weights(weights):
     return base, mask
 
 
-def intertemplate_cc(waveforms_arr, weights, max_lag=10, device=None, pair_mask=None):
-    """Pair-wise template similarity: intertp[t, u] = sum_{s,c} w[t][u,s,c] * max_lag CC, symmetrised.
+INTERTP_MAX_LAG = 31                 # the batched kernel keeps 2 * max_lag + 1 <= 63 lags per pair
+INTERTP_LDS_BYTES = 64 * 1024        # ... and this much LDS per workgroup (csrc/intertp.hip)
+
+
+def intertp_batched_fits(n_ch, Lw, max_lag):
+    """Whether the batched launch takes the problem -- the launcher's own rule (bpmf_intertemplate_cc_dev): at most 63
+    lags, and ONE channel of a template (Lw samples), its CCs against a tile of 8 templates (8 * n_lag) and the tile's
+    weighted maxima (8 * n_ch) within the LDS budget."""
+    n_lag = 2 * int(max_lag) + 1
+    return max_lag <= INTERTP_MAX_LAG and 4 * (Lw + 8 * n_lag + 8 * n_ch) <= INTERTP_LDS_BYTES
+
+
+def intertemplate_cc(waveforms_arr, weights, max_lag=10, device=None, pair_mask=None, symmetrise=True):
+    """Pair-wise template similarity: intertp[t, u] = sum_{s,c} w[t][u,s,c] * max_lag CC, symmetrised
+    (symmetrise=False: the matrix before (x + x.T) / 2).
 
     waveforms_arr (T,S,C,L).  weights: (T, S, C) with pair_mask (T, T) -- row t's channel weights and
     the pairs within the distance threshold, the factors the reference multiplies together
     (dataset.py:4789-4816) -- or the full (T, T, S, C) array / a callable t -> (T, S, C).  Factorised
     weights (given, or recognised in a full array) run as ONE batched launch
-    (bpmf_intertemplate_cc_dev); anything else takes the per-template loop of the reference
-    (intertemplate_cc_loop).  Both give the same bits."""
+    (bpmf_intertemplate_cc_dev); anything else -- weights that do not factorise, more than 63 lags, a channel too long
+    for the kernel's LDS budget (intertp_batched_fits, decided here before anything is launched) -- takes the
+    per-template loop of the reference (intertemplate_cc_loop).  Both give the same bits."""
     import torch
     if np.shape(waveforms_arr)[-1] <= 2 * int(max_lag) or max_lag < 0:
         raise ValueError("intertemplate_cc: the waveforms must be longer than 2 * max_lag samples")
-    if not callable(weights) and max_lag <= 31:      # the batched kernel keeps 2 * max_lag + 1 <= 63 lags per pair
+    shape = np.shape(waveforms_arr)
+    if not callable(weights) and intertp_batched_fits(shape[1] * shape[2], shape[3], max_lag):
         w = np.asarray(weights, dtype=np.float32)
         fact = None
         if w.ndim == 3:
@@ -1058,17 +1073,18 @@ def intertemplate_cc(waveforms_arr, weights, max_lag=10, device=None, pair_mask=
                                                    out.data_ptr())
             _lib.check(rc, "bpmf_intertemplate_cc_dev")
             o = out.cpu().numpy()
-            return (o + o.T) / 2.0
-    if not callable(weights) and np.ndim(weights) == 3:     # factorised weights, too many lags for the batched kernel
+            return (o + o.T) / 2.0 if symmetrise else o
+    if not callable(weights) and np.ndim(weights) == 3:     # factorised weights the batched kernel does not take
         w = np.asarray(weights, dtype=np.float32)
         T = w.shape[0]
         mask = np.ones((T, T), bool) if pair_mask is None else np.asarray(pair_mask, dtype=bool)
         weights = lambda t: w[t][None, :, :] * mask[t][:, None, None]
-    return intertemplate_cc_loop(waveforms_arr, weights, max_lag=max_lag, device=device)
+    return intertemplate_cc_loop(waveforms_arr, weights, max_lag=max_lag, device=device, symmetrise=symmetrise)
 
 
-def intertemplate_cc_loop(waveforms_arr, weights, max_lag=10, device=None):
-    """Pair-wise template similarity: intertp[t, u] = sum_{s,c} w[t][u,s,c] * max_lag CC.
+def intertemplate_cc_loop(waveforms_arr, weights, max_lag=10, device=None, symmetrise=True):
+    """Pair-wise template similarity: intertp[t, u] = sum_{s,c} w[t][u,s,c] * max_lag CC, symmetrised
+    (symmetrise=False: the matrix before (x + x.T) / 2).
 
     waveforms_arr (T,S,C,L); weights (T, T, S, C), or a callable t -> (T, S, C) -- row t holds the
     channel weights the reference builds for template t against every other template
@@ -1099,4 +1115,4 @@ def intertemplate_cc_loop(waveforms_arr, weights, max_lag=10, device=None):
         best = cc.max(dim=1).values
         out_dev[t, keep_dev] = numpy_order_sum((w_dev * best).reshape(keep.size, S * Cc))
     out = out_dev.cpu().numpy()
-    return (out + out.T) / 2.0
+    return (out + out.T) / 2.0 if symmetrise else out

@@ -39,6 +39,23 @@ sum of |products| below 2^24 quanta -> the three products and every partial sum 
 
 The build zeroes r_t r_d >= 1000 and the definition E_t E_d <= 1e-6: the same threshold up to rounding, so
 the definitions ASSERT that no active window has E_t E_d in [2.5e-7, 4e-6] -- a condition on the inputs.
+
+Inter-template CC (intertp_f64: written from TemplateGroup.compute_intertemplate_cc of the reference, the header comment
+of csrc/intertp.hip and DESIGN.md, not from the kernel body).  m = max_lag, L = Lw - 2m, w (T, n_ch) the base weights:
+    per ordered pair (t, u) inside the mask, channel ch with w[t, ch] != 0, lag j = 0 .. 2m:
+        cc_j, B_j   the MF definition above: template wf[u, ch, m : Lw - m], data wf[t, ch], moveout 0, step 1, N = Lw
+                    (c_N = 1024 + ceil(Lw / 1024); 0 under the energy guard; the guard-window condition asserted)
+        best = max_j cc_j  (max, not max |x|),   Bb = max_j B_j           [|max a - max b| <= max |a - b|]
+    raw[t, u] = sum_ch w[t, ch] best
+    B_raw     = sum_ch |w| Bb + gamma_(n_ch + 1) sum_ch |w| (|best| + Bb)
+                one rounding of each product and an n_ch-term float32 sum in ANY order (the kernels sum in NumPy's
+                pairwise order; the bound does not use it)
+    sym   = (raw + raw^T) / 2
+    B_sym = (B_raw + B_raw^T) / 2 + u (|sym| + (B_raw + B_raw^T) / 2)     the one float32 addition; halving is exact
+raw is exactly +0 (compared bitwise) wherever B_raw = 0: pairs outside the mask, rows whose template has no weighted
+channel, and pairs all of whose weighted channels are dead (all-zero) on either side or under the energy guard.  A dead
+channel among live ones contributes an exact 0 with a zero bound.  Integer regime (waveforms in -3..3): B_j = 7u |cc_j|,
+the rest of the bound unchanged (cc is no integer, the products w * best round).
 """
 import numpy as np
 
@@ -551,6 +568,127 @@ def bp_compare_max(m, a, ref, first_computed=False, what="BP max"):
     return Report(what, bad, _worst(err[judged], B_a[judged]), detail)
 
 
+# ----------------------------------------------------------------------------- inter-template CC ---
+INTERTP_MAX_LAG = 31                             # the batched kernel holds 2 * 31 + 1 = 63 lags per pair
+INTERTP_LDS_FLOATS = 64 * 1024 // 4              # the batched launch's LDS budget
+INTERTP_TILE = 8                                 # templates u per workgroup
+INTERTP_DROPS = ("first_lag", "last_lag", "trim", "tail", "abs_max", "w_u", "mask_T", "last_channel", "lds_chunk",
+                 "no_sym")
+
+
+def intertp_lds_chunk(n_ch, Lw, max_lag):
+    """Channels of one template the batched launch stages per LDS pass: the largest c <= n_ch with
+    c * Lw + 8 * c * n_lag + 8 * n_ch floats within 64 KB (the data rows, the CCs of a tile of 8 templates, their
+    weighted maxima); 0 where one channel does not fit (workflow.intertemplate_cc then takes the per-template loop)."""
+    n_lag = 2 * max_lag + 1
+    room = INTERTP_LDS_FLOATS - INTERTP_TILE * n_ch
+    return int(max(0, min(n_ch, room // (Lw + INTERTP_TILE * n_lag))))
+
+
+class IntertpRef:
+    """raw, B_raw: (T, T) the un-symmetrised matrix and its bound; sym, B_sym: the symmetrised ones; zero: (T, T) where
+    raw must be exactly +0; live: (T, T, n_ch) the (pair, channel) entries the definition computes; best, Bb: (T, T, n_ch)
+    max over the lags and its bound; arg: (T, T, n_ch) the lag of the maximum."""
+
+
+def intertp_f64(waveforms, base_weights, pair_mask, max_lag, exact=False, drop=None):
+    """The definition of the module docstring, vectorised over pairs, channels and lags.  exact=True: the integer regime.
+    `drop` plants a defect IN THIS DEFINITION for the sensitivity tests: "first_lag" / "last_lag" leave that lag out,
+    "trim" cuts the templates at m + 1 (the three need max_lag >= 1 and change nothing at 0), "tail" leaves the last L % 8
+    samples out of the numerators, "abs_max" takes max |cc|, "w_u" weights pair (t, u) with w[u], "mask_T" transposes the
+    mask, "last_channel" leaves the last channel out of the sum, "lds_chunk" every channel behind the first
+    intertp_lds_chunk ones, "no_sym" returns raw as sym."""
+    assert drop is None or drop in INTERTP_DROPS
+    wf32 = np.asarray(waveforms)
+    T, S, C, Lw = wf32.shape
+    n_ch, m = S * C, int(max_lag)
+    L, n_lag = Lw - 2 * m, 2 * m + 1
+    assert m >= 0 and L >= 1
+    wf = wf32.reshape(T, n_ch, Lw).astype(np.float64)
+    w = np.asarray(base_weights).reshape(T, n_ch).astype(np.float64)
+    mask = np.asarray(pair_mask, dtype=bool).reshape(T, T)
+    if drop == "mask_T":
+        mask = mask.T
+    if exact:
+        assert np.abs(wf).max() <= 3 and 9 * L < EXACT_LIMIT and np.array_equal(wf, np.round(wf))
+    c_N = CSUM_CHUNK + -(-Lw // CSUM_CHUNK)
+    t0 = m + (1 if drop == "trim" and m else 0)
+    tp = wf[:, :, t0:t0 + L]                                                           # (u, ch, l)
+    win = np.lib.stride_tricks.sliding_window_view(wf, L, axis=-1)                     # (t, ch, lag, l)
+    assert win.shape[2] == n_lag
+    win_c = np.ascontiguousarray(win.transpose(1, 0, 2, 3)).reshape(n_ch, T * n_lag, L)
+    tp_c = np.ascontiguousarray(tp.transpose(1, 2, 0))                                 # (ch, l, u)
+    n_num = L - L % 8 if drop == "tail" else L
+
+    def pairs(x):                                                                      # (ch, t * lag, u) -> (t, u, ch, lag)
+        return x.reshape(n_ch, T, n_lag, T).transpose(1, 3, 0, 2)
+
+    num = pairs(np.matmul(win_c[:, :, :n_num], tp_c[:, :n_num]))
+    a_sum = pairs(np.matmul(np.abs(win_c), np.abs(tp_c)))
+    E_d = np.einsum("cil,cil->ci", win_c, win_c).reshape(n_ch, T, n_lag).transpose(1, 0, 2)      # (t, ch, lag)
+    E_t = np.einsum("ucl,ucl->uc", tp, tp)                                             # (u, ch)
+    csum_total = np.einsum("tcn,tcn->tc", wf, wf)
+    prod = E_t[None, :, :, None] * E_d[:, None, :, :]
+    w_pair = np.broadcast_to(w[None, :, :] if drop == "w_u" else w[:, None, :], (T, T, n_ch))
+    live = mask[:, :, None] & (w_pair != 0)
+    in_window = live[..., None] & (prod >= GUARD_WINDOW[0]) & (prod <= GUARD_WINDOW[1])
+    assert not in_window.any(), \
+        f"input condition: E_t*E_d = {prod[in_window][0]:.3e} inside the guard window at (t, u, ch, lag) {np.argwhere(in_window)[0]}"
+    keep = prod > GUARD
+    den = np.sqrt(np.where(keep, prod, 1.0))
+    cc = np.where(keep, num / den, 0.0)
+    if exact:
+        B = NORM_ROUNDINGS * U * np.abs(cc)
+    else:
+        A = np.where(keep, a_sum / den, 0.0)
+        E_rel = 0.5 * c_N * 2.0 ** -53 * csum_total[:, None, :, None] / np.where(keep, E_d[:, None], 1.0)
+        B = np.where(keep, gamma(L) * (A + np.abs(cc)) + (NORM_ROUNDINGS * U + E_rel) * np.abs(cc), 0.0)
+    lags = slice(1 if drop == "first_lag" and m else 0, n_lag - (1 if drop == "last_lag" and m else 0))
+    pick = np.abs(cc[..., lags]) if drop == "abs_max" else cc[..., lags]
+    ref = IntertpRef()
+    ref.live = live
+    ref.arg = np.where(live, pick.argmax(axis=-1) + lags.start, -1)
+    ref.best = np.where(live, pick.max(axis=-1), 0.0)
+    ref.Bb = np.where(live, B[..., lags].max(axis=-1), 0.0)
+    summed = np.ones(n_ch, dtype=bool)
+    if drop == "last_channel":
+        summed[n_ch - 1] = False
+    elif drop == "lds_chunk":
+        summed[intertp_lds_chunk(n_ch, Lw, m):] = False
+    aw = np.abs(w_pair) * summed
+    ref.raw = (w_pair * summed * ref.best).sum(axis=-1)
+    ref.B_raw = (aw * ref.Bb).sum(axis=-1) + gamma(n_ch + 1) * (aw * (np.abs(ref.best) + ref.Bb)).sum(axis=-1)
+    ref.zero = ref.B_raw == 0
+    half = (ref.B_raw + ref.B_raw.T) / 2
+    ref.sym = ref.raw if drop == "no_sym" else (ref.raw + ref.raw.T) / 2
+    ref.B_sym = half + U * (np.abs(ref.sym) + half)
+    return ref
+
+
+def intertp_compare(got, ref, raw=None, what="inter-template CC"):
+    """`got`: the float32 symmetrised matrix, |got - sym| <= B_sym entry by entry; `raw` (optional): the float32 matrix
+    before the symmetrisation, |raw - f64| <= B_raw and bitwise +0 wherever ref.zero."""
+    got = np.asarray(got)
+    assert got.dtype == np.float32 and got.shape == ref.sym.shape, (got.dtype, got.shape, ref.sym.shape)
+    err, B = np.abs(got.astype(np.float64) - ref.sym), ref.B_sym
+    bad = ~(err <= B)                                      # (NaN fails)
+    detail = ""
+    if bad.any():
+        i = tuple(int(x) for x in np.argwhere(bad)[0])
+        detail = f"first at {i}: got {got[i]!r}, f64 {ref.sym[i]!r}, B_sym {B[i]:.3e}"
+    worst = _worst(err, B)
+    if raw is not None:
+        raw = np.ascontiguousarray(raw)
+        assert raw.dtype == np.float32 and raw.shape == ref.raw.shape
+        err_r = np.abs(raw.astype(np.float64) - ref.raw)
+        bad_r = ~(err_r <= ref.B_raw) | (ref.zero & (raw.view(np.uint32) != 0))
+        if bad_r.any() and not detail:
+            i = tuple(int(x) for x in np.argwhere(bad_r)[0])
+            detail = f"first (before the symmetrisation) at {i}: got {raw[i]!r}, f64 {ref.raw[i]!r}, B_raw {ref.B_raw[i]:.3e}"
+        bad, worst = np.concatenate([bad.ravel(), bad_r.ravel()]), max(worst, _worst(err_r, ref.B_raw))
+    return Report(what, bad, worst, detail)
+
+
 # ----------------------------------------------------------------------------- sampled indices ---
 EDGE_MULTIPLES = (128, 256, 512, 2048, 8192)
 
@@ -813,3 +951,123 @@ def bp_case(regime, K, S, P, N, seed, C=3, tau_lo=-700, tau_hi=1200, n_used=None
             s = int(np.flatnonzero(ws[k] == 0)[0])
             tau[k, s, 0], tau[k, s, P - 1] = tau_lo - 150, tau_hi + 250
     return f.astype(np.float32), tau.astype(np.int32), wp.astype(np.float32), ws.astype(np.float32)
+
+
+# ----------------------------------------------------------------------------- inter-template CC: inputs ---
+INTERTP_REGIMES = MF_REGIMES + ("int",)
+INTERTP_SCALES = (1.0, 1e-3, 1e-1, 1e2, 1e4)     # "scaled": (L sigma^2)^2 is ~1e-8 at 1e-3 and >= 0.4 at 1e-1 for L >= 64
+
+
+def intertp_case(regime, T, S, C, Lw, max_lag, seed):
+    """Inputs of one inter-template case: (waveforms (T, S, C, Lw), base weights (T, S, C), pair mask (T, T)), float32 / bool.
+    As many of these as T holds:  template 1 = template 0 rolled by +max_lag and template 2 by -max_lag (the best lag of
+    the pairs with template 0 is the last / the first one);  template 3 = minus template 0 rolled by max_lag // 2 (max
+    and max |x| differ by about 1);  template 4 without any weighted channel;  a dead (all-zero) channel 1 of template 5
+    (of the last template below T = 6, where there are two channels);  row 6 of the mask empty.  Base weights differ from
+    row to row, with zeros from 3 channels on.  The mask holds every pair among templates 0..3 that involves template 0
+    and the diagonal, is random elsewhere and not symmetric: (1, 2), (3, 1), (2, 3) are set and their transposes are not.
+    Regimes as mf_case; "scaled": one scale per channel, INTERTP_SCALES in turn (the channels at 1e-3 fall under the energy
+    guard); "int": waveforms in -3..3 and weights in 0..2."""
+    rng = np.random.default_rng(seed)
+    n_ch, m = S * C, int(max_lag)
+    L = Lw - 2 * m
+    if regime == "int":
+        wf = rng.integers(-3, 4, (T, n_ch, Lw)).astype(np.float64)
+        if L < 8:
+            wf[wf == 0] = 1
+    elif regime == "sine":
+        om = 2 * np.pi / 23.0
+        wf = np.sin(om * np.arange(Lw) + rng.uniform(0, 2 * np.pi, (T, n_ch, 1))) + 0.01 * rng.standard_normal((T, n_ch, Lw))
+        if L < 8:
+            wf = wf + 1.5
+    else:
+        wf = rng.standard_normal((T, n_ch, Lw))
+        if L < 8:                                                # (keep a window of a few samples away from zero energy)
+            wf = np.sign(wf) * (0.5 + np.abs(wf))
+        if regime == "dc":
+            wf = wf + 50.0
+        elif regime == "scaled":
+            assert L >= 64
+            wf = wf * np.resize(INTERTP_SCALES, n_ch).reshape(1, n_ch, 1)
+        else:
+            assert regime == "noise"
+    if T > 1:
+        wf[1] = np.roll(wf[0], m, axis=-1)
+    if T > 2:
+        wf[2] = np.roll(wf[0], -m, axis=-1)
+    if T > 3:
+        wf[3] = -np.roll(wf[0], m // 2, axis=-1)
+    if regime == "int":
+        w = rng.integers(1, 3, (T, n_ch)).astype(np.float64)
+    else:
+        w = rng.uniform(0.1, 1.0, (T, n_ch))
+    if n_ch >= 3:
+        w[rng.random((T, n_ch)) < 0.25] = 0.0
+        w[:, :2] = np.where(w[:, :2] == 0, 1.0, w[:, :2])        # channels 0 and 1 stay weighted
+        w[0, n_ch - 1] = 1.0                                     # ... and the last one in row 0
+    if T > 4:
+        w[4] = 0.0                                               # a template without any weighted channel
+    if n_ch >= 2 or T > 5:
+        wf[5 if T > 5 else T - 1, 1 % n_ch] = 0.0                # a dead channel
+    mask = rng.random((T, T)) < 0.6
+    mask[np.arange(T), np.arange(T)] = True
+    k = min(T, 4)
+    mask[0, :k] = mask[:k, 0] = True
+    for a, b in ((1, 2), (3, 1), (2, 3)):
+        if a < T and b < T:
+            mask[a, b], mask[b, a] = True, False
+    if T > 6:
+        mask[6] = False                                          # a template without any partner
+    return (wf.reshape(T, S, C, Lw).astype(np.float32), w.reshape(T, S, C).astype(np.float32), mask)
+
+
+# The shapes of tests/test_gpu_intertp_anchor.py, which tests/test_intertp_definition.py walks on the CPU:
+# name -> (T, S, C, Lw, max_lag).
+INTERTP_ROWS = {
+    "1 63 lags, L=3": (9, 1, 1, 65, 31),
+    "2 L=8, one full tile, 7 channels": (8, 1, 7, 70, 31),
+    "3 L=17, 8 channels": (7, 2, 4, 79, 31),
+    "4 33 lags, 9 channels, three tiles": (17, 3, 3, 96, 16),
+    "5 129 channels": (16, 43, 3, 96, 5),
+    "6 136 channels": (5, 34, 4, 96, 5),
+    "7 137 channels": (3, 137, 1, 96, 5),
+    "8 84 channels = 2 chunks of 42": (3, 28, 3, 200, 10),
+    "9 Lw=1054 across the first prefix-sum chunk": (4, 1, 2, 1054, 20),
+    "10 Lw=2078 across the second prefix-sum chunk": (3, 1, 2, 2078, 31),
+    "11a Lw=1": (3, 1, 1, 1, 0),
+    "11b T=1": (1, 2, 3, 40, 4),
+}
+INTERTP_ROWS.update({f"12 m={m} L={L}": (9, 2, 3, L + 2 * m, m) for m in (3, 4, 7, 8, 28) for L in (7, 9, 15, 16)})
+INTERTP_ALL_REGIME_ROWS = ("4 33 lags, 9 channels, three tiles", "6 136 channels")
+# (n_ch, Lw, max_lag) -> the LDS passes of the batched launch, by intertp_lds_chunk
+INTERTP_CHUNKS = {"5 129 channels": (83, 46), "7 137 channels": (83, 54), "8 84 channels = 2 chunks of 42": (42, 42)}
+
+
+def intertp_regimes_of(row):
+    return INTERTP_REGIMES if row in INTERTP_ALL_REGIME_ROWS else ("noise", "int")
+
+
+def intertp_seed(row):
+    return 5000 + list(INTERTP_ROWS).index(row)
+
+
+def intertp_features(args, ref, max_lag):
+    """What a case holds of the list in intertp_case, counted on the definition: a dict of booleans."""
+    wf, w, mask = args
+    T = wf.shape[0]
+    n_ch = w[0].size
+    m, n_lag = int(max_lag), 2 * int(max_lag) + 1
+    ch0 = ref.live[..., 0]
+    dead = ~np.asarray(wf).reshape(T, n_ch, -1).any(axis=-1)                         # (T, n_ch)
+    dead_live = ref.live & (dead[:, None, :] | dead[None, :, :])
+    assert not ref.best[dead_live].any() and not ref.Bb[dead_live].any()
+    return {
+        "last_lag_best": T > 1 and bool(ch0[1, 0]) and ref.arg[1, 0, 0] == n_lag - 1 and ref.best[1, 0, 0] > 0.999,
+        "first_lag_best": T > 2 and bool(ch0[2, 0]) and ref.arg[2, 0, 0] == 0 and ref.best[2, 0, 0] > 0.999,
+        "negated": T > 3 and bool(ch0[3, 0]) and ref.best[3, 0, 0] < 0.9,
+        "dead_channel": bool(dead_live.any()),
+        "unweighted_row": bool((~(np.asarray(w).reshape(T, n_ch) != 0).any(axis=1) & mask.any(axis=1)).any()),
+        "empty_mask_row": bool((~mask.any(axis=1)).any()),
+        "asymmetric_mask": int((mask & ~mask.T).sum()),
+        "rows_differ": T > 1 and len({tuple(r) for r in np.asarray(w).reshape(T, n_ch)}) > 1,
+    }

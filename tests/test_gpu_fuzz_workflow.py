@@ -94,12 +94,20 @@ def test_fuzz_workflow_intertemplate_cc(oracle_lib, seed):
     T = int(rng.integers(1, 40))
     S = int(rng.integers(1, 9))
     C = int(rng.integers(1, 4))
-    L = int(rng.choice([1, 2, 9, 40, 100, 257, 1025, 1300]))
-    max_lag = int(rng.choice([0, 1, 5, 10, 33]))         # 33: more lags than the batched kernel holds -> the loop
+    if seed % 4 == 1:
+        # few templates of 129 or 138 channels: the recursive branch of the NumPy-order sum, several LDS passes
+        T, S, C = int(rng.integers(1, 9)), int(rng.choice([43, 46])), 3
+    lengths = [1, 2, 9, 40, 100, 257, 1025, 1300]
+    L = int(rng.choice(lengths))
+    # 0..31 run the batched kernel; 32, 33: more lags than it holds -> the loop (every value within 8 consecutive seeds)
+    max_lag = [0, 1, 5, 10, 16, 31, 32, 33][(3 * seed + int(rng.integers(0, 8)) * (seed >= 8)) % 8]
     if L <= 2 * max_lag:
         with pytest.raises(ValueError):
             workflow.intertemplate_cc(np.zeros((2, 1, 1, L), np.float32), np.ones((2, 1, 1), np.float32), max_lag=max_lag)
-        max_lag = (L - 1) // 2
+        if seed % 4:
+            L = int(rng.choice([x for x in lengths if x > 2 * max_lag]))       # longer waveforms, or
+        else:
+            max_lag = (L - 1) // 2                                             # as many lags as the waveforms hold
     wf = rng.standard_normal((T, S, C, L)).astype(np.float32)
     if T > 2:
         wf[2, 0, 0] = 0.0

@@ -521,6 +521,27 @@ int bpmf_row_kurtosis_parts_dev(const float *d_x, size_t rows, size_t n, void *d
                                 size_t workspace_bytes, bpmf_stream_t stream, float *d_kurtosis,
                                 float *d_parts);
 
+/* ------------------------------------------- events detected by several templates --- */
+/*
+ * The loop of TemplateGroup.remove_multiples (BPMF/dataset.py:5214-5282) on a catalog that is ALREADY in the
+ * stable order of its origin times (equal times: the caller's order): unique_out[n] = 1 where event n stays
+ * `unique_event`, 0 where another template's detection of the same event has the larger cc.  An event n1 that is
+ * still unique gathers n1, n1+1, ... for as long as the float64 sum of the inter-event times t[k] - t[k-1],
+ * accumulated left to right, stays < dt_criterion; of these, the ones still unique and with
+ * pair_ok[rows[n1] * T + rows[m]] != 0 are multiples when there are two or more: all are flagged, the one with the
+ * largest cc (equal cc: the earliest) is restored.  Host definition: seismic_bpmf_amd.postprocess.flag_multiples.
+ *   d_t_sorted (n) f64 seconds, ascending; d_rows_sorted (n) i32 rows of pair_ok; d_cc_sorted (n) f32, finite;
+ *   d_pair_ok (T, T) u8; d_unique_out (n) u8 out, every element written.
+ * n == 0 returns 0 and touches nothing.  A row outside [0, T) fails the call (bpmf_last_error names the event) and
+ * is never used as an index.  Synchronises `stream` once, to read that check back: on return the flags are complete.
+ * A run of events without a gap of dt_criterion is walked by one wavefront (csrc/multiples.hip).
+ */
+size_t bpmf_flag_multiples_workspace_bytes(size_t n);
+int bpmf_flag_multiples_dev(const double *d_t_sorted, const int32_t *d_rows_sorted,
+                            const float *d_cc_sorted, size_t n, const uint8_t *d_pair_ok, size_t T,
+                            double dt_criterion, void *d_workspace, size_t workspace_bytes,
+                            bpmf_stream_t stream, uint8_t *d_unique_out);
+
 /* ------------------------------------------------------------ running kurtosis --- */
 /*
  * Device version of BPMF.clib.kurtosis (BPMF/clib.py:86-102 -> BPMF/libc.c:11-53): kurto[ch][n],

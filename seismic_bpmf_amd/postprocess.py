@@ -763,3 +763,87 @@ def location_uncertainty(likelihood_domain, distances_km, depth_diff_km):
     hunc = np.sum(like * np.asarray(distances_km)) / np.sum(like)
     vunc = np.sum(like * np.asarray(depth_diff_km)) / np.sum(like)
     return hunc, vunc
+
+
+def multiples_pair_mask(ellipsoid_dist, distance_criterion, intertemplate_cc=None, similarity_criterion=-1.0):
+    """The template-pair test of ``TemplateGroup.remove_multiples`` (BPMF/dataset.py:5262-5274) for every pair at once:
+    pair_ok[i, j] = ellipsoid_dist[i, j] < distance_criterion, and -- only when similarity_criterion > -1 --
+    & (intertemplate_cc[i, j] >= similarity_criterion).  (T, T) arrays in, (T, T) bool out; the comparisons are
+    NumPy's own on the arrays as given (a NaN fails both), so the flagging itself compares no matrix value."""
+    dist = np.asarray(ellipsoid_dist)
+    if dist.ndim != 2 or dist.shape[0] != dist.shape[1]:
+        raise ValueError(f"multiples_pair_mask: ellipsoid_dist must be (T, T); got {dist.shape}")
+    ok = dist < distance_criterion
+    if similarity_criterion > -1.0:
+        if intertemplate_cc is None:
+            raise ValueError("multiples_pair_mask: similarity_criterion > -1 needs intertemplate_cc")
+        sim = np.asarray(intertemplate_cc)
+        if sim.shape != dist.shape:
+            raise ValueError(f"multiples_pair_mask: intertemplate_cc must be {dist.shape}; got {sim.shape}")
+        ok = ok & (sim >= similarity_criterion)
+    return np.ascontiguousarray(ok)
+
+
+def multiples_arguments(origin_time_sec, template_rows, cc, pair_ok):
+    """The arguments of flag_multiples, checked and typed: (t float64 (n,), rows int32 (n,), cc float32 (n,),
+    pair_ok bool (T, T)).  ValueError for mismatched lengths, a pair_ok that is not square, a row outside [0, T)
+    or a cc that is not finite (the keeper is the largest cc: a NaN has no order)."""
+    t = np.ascontiguousarray(np.asarray(origin_time_sec, dtype=np.float64).reshape(-1))
+    rows = np.asarray(template_rows).reshape(-1)
+    if rows.size and not np.issubdtype(rows.dtype, np.integer):
+        raise ValueError("flag_multiples: template_rows must be integers")
+    c = np.ascontiguousarray(np.asarray(cc, dtype=np.float32).reshape(-1))
+    ok = np.asarray(pair_ok)
+    if ok.ndim != 2 or ok.shape[0] != ok.shape[1]:
+        raise ValueError(f"flag_multiples: pair_ok must be (T, T); got {ok.shape}")
+    ok = np.ascontiguousarray(ok.astype(bool))
+    if not (t.shape == rows.shape == c.shape):
+        raise ValueError("flag_multiples: origin_time_sec, template_rows and cc must have one entry per event")
+    if rows.size and (rows.min() < 0 or rows.max() >= ok.shape[0]):
+        raise ValueError(f"flag_multiples: a template row lies outside [0, {ok.shape[0]})")
+    if not np.isfinite(c).all():
+        raise ValueError("flag_multiples: cc must be finite")
+    return t, np.ascontiguousarray(rows.astype(np.int32)), c, ok
+
+
+def flag_multiples(origin_time_sec, template_rows, cc, pair_ok, dt_criterion):
+    """The loop of ``TemplateGroup.remove_multiples`` (BPMF/dataset.py:5214-5282) on plain arrays: which events of
+    a catalog stay `unique_event` when several templates detect the same event.  `origin_time_sec` (n,) float64,
+    `template_rows` (n,) rows of `pair_ok`, `cc` (n,) float32 and finite, `pair_ok` (T, T) bool
+    (multiples_pair_mask), `dt_criterion` seconds.  Returns (n,) bool in the order of the input.
+
+    The events are visited in the STABLE order of their origin times (equal times: input order -- the reference's
+    pandas quicksort leaves that order to the platform).  A visited event n1 that is still unique gathers its
+    neighbours -- itself and the following events n2 for as long as the float64 sum of the inter-event times
+    ie[n1 + 1] + ... + ie[n2], accumulated left to right, stays < dt_criterion (the reference's running sum, not
+    t[n2] - t[n1]) --, keeps those still unique, and of them the ones with pair_ok[row of n1, row of m].  Two or more
+    of these are multiples: all are flagged False, then the one with the largest cc (equal cc: the earliest in the
+    visiting order, np.argmax) is set True again.  This is the definition workflow.flag_multiples (csrc/multiples.hip)
+    is tested against, element for element."""
+    t, rows, c, ok = multiples_arguments(origin_time_sec, template_rows, cc, pair_ok)
+    n = t.shape[0]
+    dt_criterion = float(dt_criterion)
+    order = np.argsort(t, kind="stable")
+    ts, r, c = t[order], rows[order], c[order]
+    ie = np.hstack(([0.0], ts[1:] - ts[:-1])).tolist() if n else []      # Python floats: the same float64 additions
+    unique = np.ones(n, dtype=bool)
+    for n1 in range(n - 1):
+        if not unique[n1]:
+            continue
+        n2 = n1 + 1
+        acc = ie[n2]
+        while acc < dt_criterion:
+            n2 += 1
+            if n2 >= n:
+                break
+            acc += ie[n2]
+        if n2 - n1 < 2:
+            continue
+        candidates = n1 + np.flatnonzero(unique[n1:n2])
+        multiples = candidates[ok[r[n1], r[candidates]]]
+        if len(multiples) >= 2:
+            unique[multiples] = False
+            unique[multiples[np.argmax(c[multiples])]] = True
+    out = np.empty(n, dtype=bool)
+    out[order] = unique
+    return out

@@ -399,6 +399,82 @@ def cc_detections(cc, moveouts, weights, *, step=1, sr, threshold_window_dur, mi
     return out
 
 
+def flag_multiples(origin_time_sec, template_rows, cc, pair_ok, dt_criterion=4.0, device=None, out=None):
+    """The loop of ``TemplateGroup.remove_multiples`` (BPMF/dataset.py:5214-5282) on the device
+    (bpmf_flag_multiples_dev, csrc/multiples.hip): which events stay `unique_event` when several templates detect the
+    same event.  Arguments and result as postprocess.flag_multiples, the host definition it equals element for element:
+    `origin_time_sec` (n,) float64, `template_rows` (n,) rows of `pair_ok`, `cc` (n,) float32 and finite, `pair_ok`
+    (T, T) bool (postprocess.multiples_pair_mask); returns an (n,) bool NumPy array in the order of the input.
+
+    The events are visited in the stable order of their origin times (np.argsort(kind="stable"): equal times keep the
+    input order, where the reference's pandas quicksort leaves the order to the platform).  One call of the library,
+    which synchronises once, then the flags are scattered back to the input order.  `device`: the GPU (default: the
+    current one); `out`: an optional uint8 tensor of length n on that GPU that receives the flags IN SORTED ORDER (the
+    library's own output buffer, every element written)."""
+    import ctypes as C
+    import torch
+    from . import _lib
+    t, rows, c, ok = pp.multiples_arguments(origin_time_sec, template_rows, cc, pair_ok)
+    n, T = t.shape[0], ok.shape[0]
+    dev = torch.device("cuda" if device is None else device)
+    if dev.type != "cuda":
+        raise ValueError("flag_multiples: no CPU implementation here (the host mirror is postprocess.flag_multiples)")
+    if dev.index is None:
+        dev = torch.device("cuda", torch.cuda.current_device())
+    if out is not None and (not isinstance(out, torch.Tensor) or out.dtype != torch.uint8 or out.shape != (n,) or
+                            out.device != dev or not out.is_contiguous()):
+        raise ValueError(f"flag_multiples: out must be a contiguous uint8 tensor of length {n} on {dev}")
+    if n == 0:
+        return np.zeros(0, dtype=bool)
+    if T == 0:
+        raise ValueError("flag_multiples: pair_ok is empty")
+    order = np.argsort(t, kind="stable")
+    lib = _lib.lib()
+    d_t = torch.as_tensor(t[order], device=dev)
+    d_rows = torch.as_tensor(rows[order], device=dev)
+    d_cc = torch.as_tensor(c[order], device=dev)
+    d_ok = torch.as_tensor(ok.view(np.uint8), device=dev)
+    ws = torch.empty(lib.bpmf_flag_multiples_workspace_bytes(n), dtype=torch.uint8, device=dev)
+    flags = torch.empty(n, dtype=torch.uint8, device=dev) if out is None else out
+    with torch.cuda.device(dev):
+        rc = lib.bpmf_flag_multiples_dev(C.c_void_p(d_t.data_ptr()), C.c_void_p(d_rows.data_ptr()),
+                                         C.c_void_p(d_cc.data_ptr()), n, C.c_void_p(d_ok.data_ptr()), T,
+                                         float(dt_criterion), C.c_void_p(ws.data_ptr()), ws.numel(),
+                                         C.c_void_p(torch.cuda.current_stream(dev).cuda_stream),
+                                         C.c_void_p(flags.data_ptr()))
+    _lib.check(rc, "bpmf_flag_multiples_dev")
+    unique = np.empty(n, dtype=bool)
+    unique[order] = flags.cpu().numpy().astype(bool)
+    return unique
+
+
+def _detections_events(detections, *, sr, step, t0_sec):
+    """The events of {template: (indices, cc, threshold)} in records_to_detections' order -- by template, then by
+    index as given: (templates in that order, origin_time_sec, template_rows, cc)."""
+    tids = sorted(detections)
+    idx = [np.asarray(detections[t][0], dtype=np.int64).reshape(-1) for t in tids]
+    rows = np.concatenate([np.full(len(i), t, dtype=np.int64) for t, i in zip(tids, idx)]) if tids else np.zeros(0, np.int64)
+    index = np.concatenate(idx) if tids else np.zeros(0, np.int64)
+    val = np.concatenate([np.asarray(detections[t][1], dtype=np.float32).reshape(-1) for t in tids]) if tids else \
+        np.zeros(0, np.float32)
+    return tids, t0_sec + index * step / sr, rows, val
+
+
+def detections_unique(detections, *, sr, step, pair_ok, dt_criterion, t0_sec=0.0, device=None, on_host=False):
+    """flag_multiples for the detections of a day as the sharded search returns them: `detections` = {template:
+    (cc indices, cc, threshold)}, the template being the row of `pair_ok`.  origin_time_sec = t0_sec + indices * step /
+    sr; the events are taken in records_to_detections' order (by template, then by index), which is therefore the
+    order among equal origin times.  Returns {template: bool array} aligned with the detections.  `on_host`: through
+    the host mirror (postprocess.flag_multiples) instead of the device."""
+    tids, t, rows, val = _detections_events(detections, sr=sr, step=step, t0_sec=t0_sec)
+    if on_host:
+        unique = pp.flag_multiples(t, rows, val, pair_ok, dt_criterion)
+    else:
+        unique = flag_multiples(t, rows, val, pair_ok, dt_criterion, device=device)
+    bounds = np.cumsum([0] + [len(detections[t][0]) for t in tids])
+    return {t: unique[bounds[k]:bounds[k + 1]] for k, t in enumerate(tids)}
+
+
 # ------------------------------------------------------------------ one process per GPU ---
 RECORD_WIDTH = 4      # (global template id, cc index, float32 bits of cc, float32 bits of the threshold) as int64
 
@@ -436,7 +512,7 @@ def sharded_matched_filter_detections(templates, moveouts, weights, data, *, gro
                                       engine=None, detector=None, data_src=None, balance=True, step=1,
                                       extract_peak_amplitudes=False, offset_win_peak_amp_sec=1.0,
                                       duration_win_peak_amp_sec=3.0, moveouts_peak_amp=None, data_norm=None,
-                                      **detection_kwargs):
+                                      multiples=None, **detection_kwargs):
     """Matched-filter search of one day on ALL ranks of a torch.distributed group (one process per GPU):
     what ``MatchedFilter.run_matched_filter_search`` (BPMF/similarity_search.py:726-807) does with its
     sequential template chunks, the chunks being the ranks' shards here.
@@ -460,6 +536,12 @@ def sharded_matched_filter_detections(templates, moveouts, weights, data, *, gro
     `data_src` the only place a rank other than the source can read the day from -- and a second all-gather of
     (n, S * C) float32 rows brings them together: info["peak_amplitudes"] = {global template id: (n, S, C)},
     identical on every rank and ordered like the returned detections.
+
+    `multiples` = dict(pair_ok=(T, T) bool, dt_criterion=seconds, t0_sec=0.0) (needs `sr` among the
+    detection_kwargs): after the all-gather every rank flags the events several templates detected
+    (``TemplateGroup.remove_multiples``, BPMF/dataset.py:5130-5295; detections_unique) -- the same records in the same
+    order on every rank, hence the same flags: info["unique_event"] = {global template id: bool array} aligned with the
+    returned detections.  On this rank's GPU, or through the host mirror when the engine's day is not on one.
 
     `engine` / `detector`: stand-ins for the per-rank MatchedFilterGPU and for cc_detections (the CPU tests
     of the choreography over gloo pass oracle-backed ones); None = the HIP path.  An engine whose day (`.data`) is not
@@ -512,7 +594,17 @@ def sharded_matched_filter_detections(templates, moveouts, weights, data, *, gro
         amp_all = np.concatenate([p.cpu().numpy() for p in parts]).reshape((-1,) + amp.shape[1:])
         order = np.lexsort((everything[:, 1], everything[:, 0]))              # records_to_detections' order
         info["peak_amplitudes"] = _split_by_row(everything[order, 0], amp_all[order], T)
-    return records_to_detections(everything, T), info
+    found = records_to_detections(everything, T)
+    if multiples is not None:
+        if "sr" not in detection_kwargs:
+            raise ValueError("sharded_matched_filter_detections: multiples needs sr")
+        day = smf.local.data
+        on_gpu = isinstance(day, torch.Tensor) and day.is_cuda
+        info["unique_event"] = detections_unique(found, sr=detection_kwargs["sr"], step=step,
+                                                 pair_ok=multiples["pair_ok"], dt_criterion=multiples["dt_criterion"],
+                                                 t0_sec=multiples.get("t0_sec", 0.0),
+                                                 device=day.device if on_gpu else None, on_host=not on_gpu)
+    return found, info
 
 
 def sharded_backprojection_detections(features, moveouts, weights_phases, weights_sources, *, sr,

@@ -548,6 +548,9 @@ int bpmf_flag_multiples_dev(const double *d_t_sorted, const int32_t *d_rows_sort
  * n >= W, is the kurtosis of the W samples before n; written only where the window variance
  * exceeds 1e-6 -- zero-initialise d_kurto like the reference wrapper does.
  *   d_signal, d_kurto (n_channels, length) f32, n_channels = stations x components
+ * Limits: 1 <= W <= 32768 (a workgroup stages W + 256 samples in LDS: 132 096 bytes of the CU's 160 KB at the
+ * largest window) and n_channels <= 65535 (gridDim.y) per call; anything beyond fails without a launch.
+ * length <= W writes nothing and returns 0.
  */
 int bpmf_kurtosis_dev(const float *d_signal, int W, size_t n_channels, size_t length,
                       bpmf_stream_t stream, float *d_kurto);

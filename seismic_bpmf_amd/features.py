@@ -177,7 +177,9 @@ def saturated_envelopes(traces, anomaly_threshold=1.0e-11, max_dynamic_range=1.0
 def kurtosis(signal, W, device=None):
     """Device version of BPMF.clib.kurtosis(signal, W) (BPMF/clib.py:86-102): running kurtosis of
     `signal (n_stations, n_components, length)` over the W samples before each sample.  Returns a
-    float32 device tensor of the same shape, zero where the reference leaves its zeros."""
+    float32 device tensor of the same shape, zero where the reference leaves its zeros.  W is at most 32768 (the
+    window and the 256 samples of a workgroup are staged in LDS: include/bpmf_hip.h); any number of channels, handed
+    to the library 65535 at a time (its gridDim.y)."""
     import ctypes as C
     torch, dev = _torch_device(device)
     x = signal if isinstance(signal, torch.Tensor) else torch.as_tensor(np.ascontiguousarray(signal, dtype=np.float32))
@@ -186,7 +188,12 @@ def kurtosis(signal, W, device=None):
         raise ValueError("signal must be (n_stations, n_components, length)")
     out = torch.zeros_like(x)
     stream = torch.cuda.current_stream(dev).cuda_stream
-    rc = _lib.lib().bpmf_kurtosis_dev(C.c_void_p(x.data_ptr()), int(W), x.shape[0] * x.shape[1], x.shape[2],
-                                      C.c_void_p(stream), C.c_void_p(out.data_ptr()))
-    _lib.check(rc, "bpmf_kurtosis_dev")
+    length = x.shape[2]
+    rows, out_rows = x.reshape(-1, length), out.reshape(-1, length)
+    with torch.cuda.device(dev):
+        for r0 in range(0, max(rows.shape[0], 1), 65535):         # (no channel at all: the library refuses, as before)
+            nr = min(65535, rows.shape[0] - r0)
+            rc = _lib.lib().bpmf_kurtosis_dev(C.c_void_p(rows[r0:].data_ptr()), int(W), nr, length,
+                                              C.c_void_p(stream), C.c_void_p(out_rows[r0:].data_ptr()))
+            _lib.check(rc, "bpmf_kurtosis_dev")
     return out

@@ -24,6 +24,12 @@ def window_params(sliding_window_samp, overlap):
     return int(sliding_window_samp) // 2, int((1.0 - overlap) * int(sliding_window_samp))
 
 
+def mad_rows_per_call(rows, per_row, limit):
+    """Rows of the MAD threshold per call of the library: at most 65535 (its gridDim.y), and few enough that
+    `per_row` bytes of workspace each stay under `limit` bytes; one row always goes."""
+    return int(max(1, min(rows, 65535, limit // max(1, per_row))))
+
+
 class ThresholdGPU:
     def __init__(self, device=None):
         import torch
@@ -99,7 +105,7 @@ class ThresholdGPU:
         # (per-row bytes from the library itself: short rows take the one-workgroup statistics and need next to nothing,
         # long ones ~n / 6 + 100 KB)
         per_row = max(1, int(self.lib.bpmf_tdt_mad_workspace_bytes(64, n, W, shift)) // 64)
-        chunk = int(max(1, min(rows, 65535, self.mad_workspace_limit // per_row)))
+        chunk = mad_rows_per_call(rows, per_row, self.mad_workspace_limit)
         nbytes = self.lib.bpmf_tdt_mad_workspace_bytes(chunk, n, W, shift)
         if self._ws is None or self._ws.numel() < nbytes:
             self._ws = None

@@ -391,6 +391,10 @@ int bpmf_bp_extract_peaks_dev(const float *d_beam, const int32_t *d_sources, siz
  *   gaussian: 500 standard-normal floats used to fill exact zeros (libc.c:606-612)
  *   thr_windows (n_rows, n_win): one threshold per sliding window, after "delay the jump"
  *   threshold (n_rows, n) or NULL: the step-wise expansion the reference returns
+ * Limits: 2 * half_window < 2^31, 1 <= shift <= 2 * half_window + 1, n >= 2 * half_window.  With `threshold`
+ * (the expansion) n_rows <= 65535 per call (gridDim.y); without it any number of rows goes.  Both extractions
+ * below take n_rows <= 65535 and n < 2^31 per call.  A call outside these limits returns -1 before anything
+ * is launched or written (bpmf_last_error says why); callers with more rows hand them over in slabs.
  */
 size_t bpmf_tdt_num_windows(size_t n, size_t half_window, size_t shift);
 size_t bpmf_tdt_workspace_bytes(size_t n_rows, size_t n, size_t half_window, size_t shift);

@@ -329,7 +329,10 @@ __global__ __launch_bounds__(256) void cand_extract_kernel(
         for (unsigned e = 0; e < 4; ++e) {
             if (e >= cnt[c]) break;
             const unsigned w = w_first == w_last ? w_first : window_of(i0[c] + e);
-            const float t = fminf(cap, tw[w]);
+            // np.minimum of the reference: a NaN threshold (a row whose global windows are all zero) stays NaN
+            // and nothing exceeds it -- fminf would fall back to the cap and report the whole row
+            const float th = tw[w];
+            const float t = cap < th ? cap : th;
             if (v[c][e] > t) {
                 unsigned slot = atomicAdd(count, 1u);
                 if (slot < capacity)
@@ -406,6 +409,8 @@ extern "C" int bpmf_tdt_rms_dev(const float* d_series, const float* d_gaussian, 
                   half_window, shift);
         return -1;
     }
+    // (the expansion's grid carries the row in gridDim.y; refused before anything is launched or written)
+    if (d_threshold && n_rows > 65535) { set_error("bpmf_tdt_rms_dev: at most 65535 rows per call with the expansion"); return -1; }
     TdtWorkspace ws = tdt_carve(d_workspace, n_rows, n_glob, n_win);
     if (workspace_bytes < ws.bytes) {
         set_error("bpmf_tdt_rms_dev: workspace too small (%zu < %zu)", workspace_bytes, ws.bytes);
@@ -432,7 +437,6 @@ extern "C" int bpmf_tdt_rms_dev(const float* d_series, const float* d_gaussian, 
     tdt_smooth_kernel<<<blocks(n_rows), dim3(B), 0, stream>>>(d_thr_windows, ws.diff, n_rows, n_win);
     BPMF_LAUNCH_CHECK();
     if (d_threshold) {
-        if (n_rows > 65535) { set_error("bpmf_tdt_rms_dev: at most 65535 rows per call"); return -1; }
         tdt_expand_kernel<<<dim3((unsigned)((n + 255) / 256), (unsigned)n_rows), dim3(256), 0, stream>>>(
             d_thr_windows, n_rows, n, shift, n_win, d_threshold);
         BPMF_LAUNCH_CHECK();

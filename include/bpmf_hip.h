@@ -455,6 +455,33 @@ int bpmf_peak_amplitudes_dev(const float *d_data, size_t S, size_t C, size_t N, 
                              int64_t offset, int64_t duration, const float *d_norm_or_null, bpmf_stream_t stream,
                              float *d_out);
 
+/* Matched-filter templates cut from the located events of a day that is in HBM (templates.hip; the reference:
+ * Event.read_waveforms(time_shifted=True) + set_availability + TemplateGroup.normalize + Event.compute_snr,
+ * BPMF/dataset.py:1929-2069, 2556-2607, 4152-4166, 1441-1475).  For event e and channel (s, c), with
+ * i0 = d_origin[e] + d_moveouts[e, s, c] and window[l] = data[s, c, i0 + l] where 0 <= i0 + l < N, else +0.0:
+ *     d_norm[e, s, c]         = np.std(window) (normalize 1) | np.max(np.abs(window)) (2) | 1 (0);   0 becomes 1
+ *     d_templates[e, s, c, l] = window[l] / d_norm[e, s, c]
+ *     d_flags[e, s, c]        = bit 0: any(window != 0) (a NaN counts);  bit 1: the window lies wholly inside [0, N)
+ *     d_snr[e, s, c]          = np.std(window) / np.std(noise window), a noise std of 0 taken as 1; the noise window
+ *                               is the noise_samples samples from d_origin[e] - noise_offset, the same for every
+ *                               channel, clipped in place like the signal window
+ * in NumPy's own float32 arithmetic (pairwise sums, mean, squared deviations, one division, one square root), so
+ * the results equal postprocess.templates_from_events_host bit for bit; a window that holds a NaN gets a NaN norm.
+ * A window cut by the START of the day keeps its alignment here (zeros in front); the reference left-aligns what
+ * it could read.
+ *   d_data (S, C, N) f32; d_origin (E) i64; d_moveouts (E, S, C) i32 WINDOW moveouts in samples (any sign);
+ *   d_templates (E, S, C, n_samples) f32; d_norm (E, S, C) f32; d_flags (E, S, C) u8; d_snr_or_null (E, S, C) f32,
+ *   given exactly when noise_samples > 0.  Every element of every output is written.
+ * Returns -1 for a null pointer, n_samples == 0 or > 8192, noise_samples > 8192 (NumPy sums longer rows in
+ * buffers of 8192 samples: another summation tree), normalize outside 0..2, S * C == 0, N == 0, E * S * C >= 2^31,
+ * N or |noise_offset| above 2^40, d_snr without noise_samples or the reverse, or an origin beyond +-2^40: the
+ * origins are checked on the host (a copy of 8 E bytes and one synchronisation of `stream`) before anything is
+ * launched.  n_events == 0 launches nothing and returns 0. */
+int bpmf_templates_from_events_dev(const float *d_data, size_t S, size_t C, size_t N, size_t n_events,
+                                   const int64_t *d_origin, const int32_t *d_moveouts, size_t n_samples,
+                                   int normalize, int64_t noise_offset, size_t noise_samples, bpmf_stream_t stream,
+                                   float *d_templates, float *d_norm, uint8_t *d_flags, float *d_snr_or_null);
+
 /* ------------------------------------------------- robust statistics (stats.hip) --- */
 /* np.median and MAD (median of |x - median|, float32 like NumPy) of every row of a (rows, n)
  * device array; skip_zeros != 0: over the samples != 0 only (`a[a != 0]`).  NaN for an empty

@@ -72,6 +72,114 @@ def peak_amplitudes_host(data, rows, samples, moveouts, offset, duration, data_n
     return out
 
 
+TEMPLATE_MAX_SAMPLES = 8192      # np.std sums a longer row in buffers of 8192 samples: another summation tree
+
+
+def _clipped_windows(data, start, length):
+    """(E, S, C, length) float32: data[s, c, start[e, s, c] + l] where that sample exists, +0.0 elsewhere."""
+    S, C, N = data.shape
+    idx = start[..., None] + np.arange(length, dtype=np.int64)
+    inside = (idx >= 0) & (idx < N)
+    out = data[np.arange(S)[None, :, None, None], np.arange(C)[None, None, :, None], np.where(inside, idx, 0)]
+    out[~inside] = 0.0
+    return out
+
+
+def template_window_moveouts(moveouts_sec, offset_phase_sec, phase_of_component, sr):
+    """The (E, S, C) int32 moveouts of the template WINDOWS, Template.moveouts_win / moveouts_arr
+    (BPMF/dataset.py:3451-3475): sec_to_samp(moveout - offset) of the phase each component is cut around.
+    `moveouts_sec` (E, S, P) float64 seconds after the origin time, `offset_phase_sec` (P,) the time the window
+    starts before the arrival (aux_data["offset_<phase>"]), `phase_of_component` (C,) the phase index of every
+    component (aux_data["phase_on_comp<cp>"])."""
+    mv = np.asarray(moveouts_sec, dtype=np.float64)
+    win = mv - np.asarray(offset_phase_sec, dtype=np.float64)[None, None, :]
+    return sec_to_samp(win[:, :, np.asarray(phase_of_component, dtype=np.int64)], sr).astype(np.int32)
+
+
+def templates_from_events_host(data, origin_samples, moveouts, n_samples, normalize="rms", noise_offset=None,
+                               noise_samples=None):
+    """The DEFINITION of bpmf_templates_from_events_dev (csrc/templates.hip), in NumPy's own np.std / np.max / `/`:
+    matched-filter templates cut from the day `data` (S, C, N) float32 at the located events.  For event e and channel
+    (s, c), i0 = origin_samples[e] + moveouts[e, s, c] (`moveouts` (E, S[, C]) int32 WINDOW moveouts, any sign) and
+
+    * waveforms[e, s, c, l] = data[s, c, i0 + l] where 0 <= i0 + l < N, else +0.0 -- Event.read_waveforms(
+      time_shifted=True) + utils.get_np_array (BPMF/dataset.py:1929-2069, BPMF/utils.py:1653-1657), whose zero padding
+      this is for a window cut by the END of the day.  DEPARTURE: a window cut by the START of the day keeps its
+      alignment here (zeros in front); the reference left-aligns the samples it could read and pads behind them;
+    * complete = the window lies wholly inside [0, N);  available = np.any(window != 0), Event.set_availability's test
+      (:2592; a NaN counts as data);
+    * norm = np.std(window) ("rms") | np.max(np.abs(window)) ("max") | 1 (None); 0 becomes 1; templates = waveforms /
+      norm in float32 (TemplateGroup.normalize, :4160-4165);
+    * snr (only with `noise_samples`) = np.std(window) / np.std(noise window) in float32, a noise std of 0 taken as 1,
+      always on the un-normalised window (Event.compute_snr, :1457-1461).  The noise window is the `noise_samples`
+      samples from origin_samples[e] - noise_offset, the same for every channel (time_shifted=False), clipped in place.
+      DEPARTURE: the reference hands int(noise_window_sec * sr) to an argument read as seconds; here the length is in
+      samples and says what it is.
+
+    n_samples and noise_samples stop at 8192 (TEMPLATE_MAX_SAMPLES).  Returns a dict: waveforms, templates
+    (E, S, C, L) float32; norm (E, S, C) float32; available, complete (E, S, C) bool; moveouts (E, S, C) int32; snr
+    (E, S, C) float32 or None."""
+    data = np.asarray(data, dtype=np.float32)
+    if data.ndim != 3:
+        raise ValueError("templates_from_events: data must be (S, C, N)")
+    S, C, N = data.shape
+    origin, mv, L, n_noise, offset = template_arguments(S, C, origin_samples, moveouts, n_samples, normalize,
+                                                        noise_offset, noise_samples)
+    E = len(origin)
+    start = origin[:, None, None] + mv.astype(np.int64)
+    waveforms = _clipped_windows(data, start, L)
+    out = {"waveforms": waveforms, "moveouts": mv, "complete": (start >= 0) & (start + L <= N),
+           "available": np.any(waveforms != 0.0, axis=-1), "snr": None}
+    if normalize == "rms":
+        norm = np.std(waveforms, axis=-1, keepdims=True)
+    elif normalize == "max":
+        norm = np.max(np.abs(waveforms), axis=-1, keepdims=True)
+    else:
+        norm = np.ones((E, S, C, 1), dtype=np.float32)
+    norm[norm == 0.0] = 1.0
+    out["templates"] = waveforms / norm
+    out["norm"] = norm[..., 0]
+    if n_noise:
+        noise = _clipped_windows(data, np.broadcast_to((origin - offset)[:, None, None], (E, S, C)), n_noise)
+        noise_std = np.std(noise, axis=-1)
+        noise_std[noise_std == 0.0] = 1.0
+        out["snr"] = np.std(waveforms, axis=-1) / noise_std
+    return out
+
+
+def template_arguments(S, C, origin_samples, moveouts, n_samples, normalize, noise_offset, noise_samples):
+    """The arguments of templates_from_events (host definition and device call alike), checked and in their final
+    types: (origin int64 (E,), moveouts int32 (E, S, C), L, noise_samples or 0, noise_offset).  Raises ValueError."""
+    origin = np.asarray(origin_samples)
+    mv = np.asarray(moveouts)
+    if origin.ndim != 1 or (origin.size and origin.dtype.kind not in "iu"):
+        raise ValueError("templates_from_events: origin_samples must be (E,) integers")
+    origin = origin.astype(np.int64)
+    E = len(origin)
+    if mv.ndim not in (2, 3) or mv.shape[:2] != (E, S) or (mv.ndim == 3 and mv.shape[2] not in (1, C)):
+        raise ValueError(f"templates_from_events: moveouts must be ({E}, {S}) or ({E}, {S}, {C}); got {mv.shape}")
+    if mv.size and mv.dtype.kind not in "iu":
+        raise ValueError("templates_from_events: moveouts must be integers (samples)")
+    if mv.size and (mv.min() < -2**31 or mv.max() >= 2**31):
+        raise ValueError("templates_from_events: moveouts must fit int32")
+    mv = np.array(np.broadcast_to(mv.reshape(E, S, 1 if mv.ndim == 2 else mv.shape[2]), (E, S, C)), dtype=np.int32,
+                  order="C")
+    if normalize not in ("rms", "max", None):
+        raise ValueError("templates_from_events: normalize must be 'rms', 'max' or None")
+    L = int(n_samples)
+    if not 1 <= L <= TEMPLATE_MAX_SAMPLES:
+        raise ValueError(f"templates_from_events: n_samples must be 1 .. {TEMPLATE_MAX_SAMPLES}; got {L}")
+    n_noise = 0 if noise_samples is None else int(noise_samples)
+    if not 0 <= n_noise <= TEMPLATE_MAX_SAMPLES:
+        raise ValueError(f"templates_from_events: noise_samples must be 0 .. {TEMPLATE_MAX_SAMPLES}; got {n_noise}")
+    if n_noise and noise_offset is None:
+        raise ValueError("templates_from_events: noise_samples needs noise_offset (samples before the origin)")
+    offset = 0 if noise_offset is None else int(noise_offset)
+    if np.any(np.abs(origin) > 2**40) or abs(offset) > 2**40:
+        raise ValueError("templates_from_events: origin_samples and noise_offset must lie within +-2^40")
+    return origin, mv, L, n_noise, offset
+
+
 def normalize_weights(weights):
     """Sum of channel weights = 1 per template, BPMF/similarity_search.py:469-472."""
     w = np.array(weights, dtype=np.float32, copy=True)

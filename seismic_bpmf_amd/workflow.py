@@ -10,6 +10,8 @@
   (BPMF/dataset.py:4775-4830).
 * :func:`peak_amplitudes` / :func:`detection_aux_data` = the peak amplitudes and the ``aux_data`` that
   ``_find_detections_t`` attaches to every detection (BPMF/similarity_search.py:695-722).
+* :func:`templates_from_events` = the templates of the located events, cut from the day on the device
+  (``Event.read_waveforms`` + ``Template.init_from_event`` + ``TemplateGroup.normalize``, BPMF/dataset.py).
 """
 import numpy as np
 
@@ -203,6 +205,68 @@ def peak_amplitudes(data_dev, rows, samples, moveouts, *, offset, duration, data
             C.c_void_p(torch.cuda.current_stream(dev).cuda_stream), C.c_void_p(out.data_ptr()))
     _lib.check(rc, "bpmf_peak_amplitudes_dev")
     return out.cpu().numpy()
+
+
+def templates_from_events(data_dev, origin_samples, moveouts, n_samples, *, normalize="rms", noise_offset=None,
+                          noise_samples=None, min_channels=6, min_stations=3, require_complete=True):
+    """Matched-filter templates cut from the day in HBM at the located events, all events in one launch
+    (bpmf_templates_from_events_dev, csrc/templates.hip) -- what Event.read_waveforms(time_shifted=True),
+    Template.init_from_event / set_availability, TemplateGroup.normalize and Event.compute_snr do array by array on
+    the host (BPMF/dataset.py:1929-2069, 3322-3405, 2556-2607, 4152-4166, 1441-1475).  The definition, with its two
+    stated departures from the reference, is postprocess.templates_from_events_host; the device equals it bit for bit.
+
+    `data_dev`: the (S, C, N) float32 day as a tensor on the GPU (what MatchedFilterGPU.data holds);
+    `origin_samples` (E,) int64; `moveouts` (E, S[, C]) int32 WINDOW moveouts (postprocess.template_window_moveouts);
+    `n_samples` 1 .. 8192; `normalize` "rms" | "max" | None; `noise_offset` / `noise_samples` (samples; up to 8192):
+    the noise window of the SNR, none by default.
+
+    Returns a dict.  On the day's device, as MatchedFilterGPU.run(templates, moveouts, weights) takes them:
+    `templates` (E, S, C, L) float32, `moveouts` (E, S, C) int32, `weights` (E, S, C) float32 =
+    normalize_weights(weights_channels_simple(available [& complete when `require_complete`], min_channels,
+    min_stations)).  On the host: `available`, `complete` (E, S, C) bool, `norm` (E, S, C) float32, `snr` (E, S, C)
+    float32 or None."""
+    import ctypes as C
+    import torch
+    from . import _lib
+    if not isinstance(data_dev, torch.Tensor) or not data_dev.is_cuda:
+        raise ValueError("templates_from_events: data_dev must be a tensor on the GPU (there is no CPU path; the "
+                         "definition on the host is postprocess.templates_from_events_host)")
+    if data_dev.dim() != 3:
+        raise ValueError("templates_from_events: data_dev must be (S, C, N)")
+    S, Cc, N = (int(v) for v in data_dev.shape)
+    if isinstance(moveouts, torch.Tensor):
+        moveouts = moveouts.detach().cpu().numpy()
+    if isinstance(origin_samples, torch.Tensor):
+        origin_samples = origin_samples.detach().cpu().numpy()
+    origin, mv, L, n_noise, offset = pp.template_arguments(S, Cc, origin_samples, moveouts, n_samples, normalize,
+                                                           noise_offset, noise_samples)
+    if N == 0:
+        raise ValueError("templates_from_events: the day is empty")
+    dev = data_dev.device
+    E = len(origin)
+    with torch.cuda.device(dev):
+        x = data_dev.to(dtype=torch.float32).contiguous()
+        d_mv = torch.as_tensor(mv, device=dev)
+        templates = torch.empty((E, S, Cc, L), dtype=torch.float32, device=dev)
+        norm = torch.empty((E, S, Cc), dtype=torch.float32, device=dev)
+        flags = torch.empty((E, S, Cc), dtype=torch.uint8, device=dev)
+        snr = torch.empty((E, S, Cc), dtype=torch.float32, device=dev) if n_noise else None
+        if E:
+            d_origin = torch.as_tensor(origin, device=dev)
+            rc = _lib.lib().bpmf_templates_from_events_dev(
+                C.c_void_p(x.data_ptr()), S, Cc, N, E, C.c_void_p(d_origin.data_ptr()), C.c_void_p(d_mv.data_ptr()),
+                L, {None: 0, "rms": 1, "max": 2}[normalize], offset, n_noise,
+                C.c_void_p(torch.cuda.current_stream(dev).cuda_stream), C.c_void_p(templates.data_ptr()),
+                C.c_void_p(norm.data_ptr()), C.c_void_p(flags.data_ptr()),
+                None if snr is None else C.c_void_p(snr.data_ptr()))
+            _lib.check(rc, "bpmf_templates_from_events_dev")
+        flags_host = flags.cpu().numpy()
+        available, complete = (flags_host & 1) != 0, (flags_host & 2) != 0
+        present = available & complete if require_complete else available
+        weights = pp.normalize_weights(pp.weights_channels_simple(present, min_channels, min_stations))
+        return {"templates": templates, "moveouts": d_mv, "weights": torch.as_tensor(weights, device=dev),
+                "available": available, "complete": complete, "norm": norm.cpu().numpy(),
+                "snr": None if snr is None else snr.cpu().numpy()}
 
 
 def _peak_amplitude_window(sr, offset_win_peak_amp_sec, duration_win_peak_amp_sec):

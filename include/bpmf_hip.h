@@ -114,7 +114,7 @@ int bpmf_host_call_stats(double *out, int n);
  *     matrix pipe from hi/lo splits of data and templates, three products, fp32 accumulation -- csrc/mf_split.h;
  *     |d cc_sum| <= 3e-7 * sum|w| measured, 2e-5 allowed by the north star; against its float64 definition: bit-equal
  *     to the exact path where the split is exact, rms error 0.8-2.3 x the exact path's own elsewhere;
- *     x 2.3-2.4 at configs[1]; TEMPLATES OF UP TO 2049 SAMPLES -- the one statement of that limit: it is the MFMA kernels' own (mf_uses_mfma in csrc/mf.hip: 4096
+ *     x 2.3-2.4 at configs[1]; TEMPLATES OF UP TO 2049 SAMPLES -- the one statement of that limit: it is the MFMA kernels' own (mf_choose in csrc/mf.hip: 4096
  *     lags + the padded template within 24 staging registers of 256 threads), correlated in segments of at most 376
  *     samples; a longer template runs the exact generic kernel, bit-identical to the oracle
  *     (tests/test_gpu_split16_anchor.py pins both sides); composes with the mf.compat_* switches; 1 leaves launches of fewer
@@ -157,6 +157,21 @@ int bpmf_mf_run_dev(const float *d_templates, const int32_t *d_moveouts,
                     size_t N, size_t T, size_t S, size_t C, size_t n_corr, int network_sum,
                     int flags, void *d_workspace, size_t workspace_bytes,
                     bpmf_stream_t stream, float *d_cc_out);
+
+/* Which kernel a bpmf_mf_run_dev launch of these sizes takes under the current options, and how: every
+ * matched-filter kernel family gives the same bits, so this is the only way to see which one runs (the tests
+ * assert it wherever they set an option to reach a family; the counterpart of bpmf_bp_plan_info).  Needs no
+ * device, workspace or stream.  out[BPMF_MF_LAUNCH_INFO_FIELDS]:
+ *   [0] family: 0 generic (direct) kernel, 1 workgroup MFMA kernel, 2 wave MFMA kernel, 3 mf.split16
+ *   [1] [2] staging registers per thread of the compiled MFMA variant (window, band); 0 for families 0 and 3
+ *   [3] tiles of 256 lags per wave (family 2)      [4] per-template preparation fused into the kernel
+ *   [5] channels split over four waves             [6] mf.compat_sqrt_norm epilogue    [7] step == 1
+ *   [8] mf_prologue_kernel runs in front           [9] lags per workgroup
+ *   [10] dynamic LDS bytes (families 1, 2)         [11] workgroups of the launch
+ *   [12] refusal: 0 none, 1 "grid too large", 2 "at most 65535 templates" (bpmf_mf_run_dev fails with it) */
+#define BPMF_MF_LAUNCH_INFO_FIELDS 13
+int bpmf_mf_launch_info(size_t step, size_t L, size_t N, size_t T, size_t S, size_t C, size_t n_corr,
+                        int network_sum, int flags, int64_t *out);
 
 int bpmf_mf_run(const float *templates, const int32_t *moveouts, const float *weights,
                 const float *data, size_t step, size_t L, size_t N, size_t T, size_t S,

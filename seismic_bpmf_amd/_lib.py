@@ -42,6 +42,7 @@ SIGNATURES = {
     "bpmf_mf_prepare_data_dev": (C.c_int, [_vp, _sz, _sz, _sz, _sz, _vp, _sz, _vp]),
     "bpmf_mf_run_dev": (C.c_int, [_vp, _vp, _vp, _vp, _sz, _sz, _sz, _sz, _sz, _sz, _sz, C.c_int,
                                   C.c_int, _vp, _sz, _vp, _vp]),
+    "bpmf_mf_launch_info": (C.c_int, [_sz, _sz, _sz, _sz, _sz, _sz, _sz, C.c_int, C.c_int, C.POINTER(C.c_int64)]),
     "bpmf_mf_run": (C.c_int, [_f, _i, _f, _f, _sz, _sz, _sz, _sz, _sz, _sz, _sz, C.c_int, C.c_int,
                               C.c_int, _f]),
     "bpmf_mf_run_multi": (C.c_int, [_f, _i, _f, _f, _sz, _sz, _sz, _sz, _sz, _sz, _sz, C.c_int, C.c_int,
@@ -187,6 +188,26 @@ def get_option(name):
     val, dflt = C.c_long(0), C.c_long(0)
     check(lib().bpmf_get_option(name.encode(), C.byref(val), C.byref(dflt)), f"bpmf_get_option({name})")
     return val.value, dflt.value
+
+
+MF_FAMILIES = ("direct", "workgroup", "wave", "split16")
+MF_REFUSALS = (None, "grid too large", "more than 65535 templates on the generic kernel")
+
+
+def mf_launch_info(step, L, N, T, n_stations, n_components, network_sum=True, flags=0):
+    """bpmf_mf_launch_info: the kernel a bpmf_mf_run_dev launch of these sizes takes under the current options (no
+    device needed).  `family` is one of MF_FAMILIES, `refusal` one of MF_REFUSALS."""
+    out = (C.c_int64 * 13)()
+    check(lib().bpmf_mf_launch_info(step, L, N, T, n_stations, n_components, (N - L) // step + 1, 1 if network_sum else 0, int(flags), out),
+          "bpmf_mf_launch_info")
+    names = ("family", "maxr", "maxt", "ntile", "fused", "csplit", "sqrt_norm", "step1", "prologue", "lags_per_wg",
+             "lds_bytes", "grid", "refusal")
+    info = dict(zip(names, (int(x) for x in out)))
+    for n in ("fused", "csplit", "sqrt_norm", "step1", "prologue"):
+        info[n] = bool(info[n])
+    info["family"] = MF_FAMILIES[info["family"]]
+    info["refusal"] = MF_REFUSALS[info["refusal"]]
+    return info
 
 
 class options:

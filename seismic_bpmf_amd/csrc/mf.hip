@@ -1190,12 +1190,14 @@ static int mf_check_sizes(size_t step, size_t L, size_t N, size_t T, size_t S, s
     return 0;
 }
 
-// bpmf_mf_run (host pointers) computes its first template batches piece by piece while the day is still
-// arriving from the host: a launch of bpmf_mf_run_dev restricted to the data offsets [t_mf_off_lo,
-// t_mf_off_hi) -- multiples of MF_LAGS_PER_WG, or the end -- (hi < 0: all of them), and, for the later
-// pieces of a batch, without the per-template preparation and output fill the first piece did.
-thread_local long long t_mf_off_lo = 0, t_mf_off_hi = -1;
-thread_local bool t_mf_continue = false;
+// Launch values of mf_run_dev.  bpmf_mf_run (host pointers) computes its first template batch piece by piece
+// while the day is still arriving from the host: a launch restricted to the data offsets [off_lo, off_hi) --
+// multiples of MF_LAGS_PER_WG, or the end -- (off_hi < 0: all of them), and, for the later pieces of a batch
+// (first_piece = false), without the output fill the first piece did.
+struct MfLaunch {
+    long long off_lo = 0, off_hi = -1;
+    bool first_piece = true;
+};
 
 // Which workspaces hold a day that was prepared WITH its fp16 split (option mf.split16): a caller of the *_dev entry
 // points that prepares a day with the option off and runs with it on (BPMF_MF_DATA_PREPARED) would otherwise correlate
@@ -1221,18 +1223,110 @@ static bool split_day_known(const void* ws_base, const void* data, size_t N, siz
     return false;
 }
 
-// the launch of bpmf_mf_run_dev takes the MFMA kernels (which can be restricted to a range of lag blocks)
-static bool mf_uses_mfma(size_t step, size_t L, size_t N, size_t T, size_t n_corr, int network_sum, int flags)
+// ------------------------------------------------------------ choice of kernel ---
+// Which kernel a launch of T templates runs, with which template arguments, LDS and grid: every rule is in
+// mf_choose, a function of the sizes and the options alone.  mf_run_dev launches what it returns, the
+// host-pointer call asks it whether its first batch can follow the arriving day, bpmf_mf_launch_info shows it
+// to the tests (every family gives the same bits: nothing else can tell which one ran).
+enum MfFamily { MF_DIRECT = 0, MF_WORKGROUP = 1, MF_WAVE = 2, MF_SPLIT16 = 3 };
+enum MfRefusal { MF_ACCEPTED = 0, MF_GRID_TOO_LARGE = 1, MF_TOO_MANY_TEMPLATES = 2 };
+static const char* const MF_REFUSAL_TEXT[] = {"", "grid too large", "generic kernel supports at most 65535 templates per call"};
+
+struct MfVariant {
+    int family, refusal;
+    int maxr, maxt;                     // MFMA kernels: staging registers per thread (window / band) of the compiled variant
+    int ntile;                          // wave kernel: tiles of 256 lags per wave
+    bool fused, csplit;                 // wave kernel: mf_fused_prologue in every workgroup; a tile's channels over four waves
+    bool sqrt_norm, step1, prologue;    // mf.compat_sqrt_norm epilogue; step == 1; mf_prologue_kernel runs in front
+    size_t lags_wg, lds, grid;          // lags (direct kernel: CC indices) per workgroup; dynamic LDS bytes (split16: its own,
+};                                      // mf_split.h); workgroups of a launch over all lags
+
+constexpr int MF_WAVE_MAXT = 5;
+constexpr int mf_wave_maxr(int ntile) { return ntile == 4 ? 20 : (ntile == 2 ? 12 : 8); }
+// 8 XCDs x ceil(n_blocks x T / 8) (lag block, template) pairs (mf_tile_of_block)
+static size_t mf_grid(size_t T, size_t n_blocks) { return 8 * ((T * n_blocks + 7) / 8); }
+
+// `ranged`: the launch is one piece of a larger one (MfLaunch); every piece takes the variant of the WHOLE problem
+static MfVariant mf_choose(size_t step, size_t L, size_t N, size_t T, size_t n_ch, size_t n_corr, int network_sum,
+                           int flags, bool ranged)
 {
+    MfVariant v = {};
+    v.sqrt_norm = option(OPT_MF_COMPAT_SQRT_NORM) != 0;
+    v.step1 = step == 1;
+    v.prologue = true;
+    // the MFMA kernels evaluate every data-sample offset and keep the multiples of `step`
     const size_t n_offsets = (n_corr - 1) * step + 1;
     const size_t n_lag_blocks = (n_offsets + MF_LAGS_PER_WG - 1) / MF_LAGS_PER_WG;
+    // staging registers needed per thread (window / band)
     const int need_r = (mf_window_len((int)L) + MF_THREADS - 1) / MF_THREADS;
     const int need_t = (mf_band_len((int)L) + MF_THREADS - 1) / MF_THREADS;
-    const size_t max_mfma_step = (size_t)option(OPT_MF_MAX_MFMA_STEP);
-    const bool sqrt_norm = option(OPT_MF_COMPAT_SQRT_NORM) != 0;
-    (void)sqrt_norm; (void)network_sum;       // (round 6: the MFMA epilogues store per-channel CCs under the switch too)
-    return step <= max_mfma_step && !(flags & BPMF_MF_FORCE_DIRECT) && need_r <= 24 &&
-           need_t <= 9 && T * (n_lag_blocks + 8) < 0x7fffffffull && N < ((size_t)1 << 30) - 8192;
+    // beyond mf.max_mfma_step (64) the direct kernel wins; the MFMA kernels address the data through buffer
+    // descriptors with 32-bit byte offsets: traces of 2^30 samples or more take the generic kernel
+    const bool mfma = step <= (size_t)option(OPT_MF_MAX_MFMA_STEP) && !(flags & BPMF_MF_FORCE_DIRECT) && need_r <= 24 &&
+                      need_t <= 9 && T * (n_lag_blocks + 8) < 0x7fffffffull && N < ((size_t)1 << 30) - 8192;
+    if (!mfma) {
+        v.family = MF_DIRECT;
+        v.lags_wg = 256;
+        v.grid = (n_corr + 255) / 256 * T;      // (x, y = T)
+        if (T > 65535) v.refusal = MF_TOO_MANY_TEMPLATES;
+        return v;
+    }
+    // option mf.split16: the split-precision kernel takes every launch the MFMA kernels would take (the
+    // template-length limit stated in include/bpmf_hip.h; in segments of at most 376 samples)
+    // mf.split16 = 1 leaves small launches to the exact kernel (below SP_MIN_BLOCKS (template, 8192-lag block) pairs a
+    // wave's chain of per-channel stagings is latency, not rate: configs[0], 88 pairs, ran 0.71x the exact kernel's speed, 176 pairs x 1.1-1.6:
+    // profiles/r06_mf_split16.txt); = 2 takes the split kernel for every launch (the small shapes of the tests)
+    constexpr size_t SP_MIN_BLOCKS = 128;
+    const size_t sp_blocks = (n_offsets + sp::LAGS_PER_WG - 1) / sp::LAGS_PER_WG;
+    const bool sp_small = option(OPT_MF_SPLIT16) == 1 && T * sp_blocks < SP_MIN_BLOCKS;
+    if (option(OPT_MF_SPLIT16) != 0 && sp::usable(L, N) && !sp_small) {
+        v.family = MF_SPLIT16;
+        v.lags_wg = sp::LAGS_PER_WG;
+        v.grid = mf_grid(T, sp_blocks);
+        return v;
+    }
+    if (option(OPT_MF_WAVE_KERNEL) == 0 || mf_kpad((int)L) > 272) {
+        // the workgroup kernel: 257 < L <= 1025, then L <= 2049 (need_r <= 24); under mf.wave_kernel = 0 every L
+        v.family = MF_WORKGROUP;
+        v.maxr = need_r <= 20 && need_t <= 5 ? 20 : 24;
+        v.maxt = v.maxr == 20 ? 5 : 9;
+        v.lags_wg = MF_LAGS_PER_WG;
+        v.lds = mf_lds_bytes((int)L);
+        v.grid = mf_grid(T, n_lag_blocks);
+        return v;
+    }
+    // L <= 257: independent waves, no barrier
+    v.family = MF_WAVE;
+    // tiles (of 256 lags) per wave: 4 unless the problem is too small to give every SIMD ~4 waves
+    // (option mf.tiles_per_wave: 0 = this rule, 1 / 2 / 4 = forced)
+    // (calibrated on an hour-long series with 4 .. 256 templates, tools/probe_mf_ntile_T.py,
+    // profiles/r04_mf_ntile_T.txt: 4 tiles from two full rounds of 4 waves per SIMD on, 2 tiles -- 5 waves
+    // per SIMD at 83-90 VGPRs -- from one wave per SIMD on, 1 tile below)
+    const size_t waves4 = T * n_lag_blocks * 4;
+    v.ntile = waves4 >= 8192 ? 4 : (waves4 >= 1024 ? 2 : 1);
+    const long forced = option(OPT_MF_TILES_PER_WAVE);
+    if (forced == 1 || forced == 2 || forced == 4) v.ntile = (int)forced;
+    v.maxr = mf_wave_maxr(v.ntile);
+    v.maxt = MF_WAVE_MAXT;
+    // small problems: the wave kernel does the per-template preparation itself
+    v.fused = v.ntile < 4 && n_ch <= 256 && option(OPT_MF_FUSED_PROLOGUE) != 0;
+    v.prologue = !v.fused;
+    // option mf.channel_split = n (0: off): tiny problems -- one tile per wave, fused prologue, network sum,
+    // step 1, at most 32 channels, at most n waves of 256 lags in the whole launch, not a piece of a larger
+    // launch -- run the CSPLIT variant
+    const long csplit_max = option(OPT_MF_CHANNEL_SPLIT);
+    v.csplit = v.ntile == 1 && v.fused && network_sum && v.step1 && n_ch <= 32 && !ranged && csplit_max > 0 &&
+               waves4 * 4 <= (size_t)csplit_max;
+    v.lags_wg = v.csplit ? (size_t)256 : (size_t)4 * 256 * v.ntile;
+    const size_t n_blocks_w = (n_offsets + v.lags_wg - 1) / v.lags_wg;
+    if (T * (n_blocks_w + 8) >= 0x7fffffffull) v.refusal = MF_GRID_TOO_LARGE;
+    v.grid = mf_grid(T, n_blocks_w);
+    // (+ 256: slack for the operand prefetch one k-step past the end; FUSED: 16 ints + the channel records)
+    const int Wbuf = v.ntile < 4 ? 64 * v.maxr : 256 * v.ntile - 16 + mf_kpad((int)L);      // (1 / 2 tiles: room for every staging register)
+    v.lds = (size_t)4 * (mf_band_len((int)L) + (Wbuf + 2 * (Wbuf >> 4) + 2 + 63) / 64 * 64 + 64) * sizeof(float) + 256 +
+            (v.fused ? 64 + (n_ch + MF_REC_TERMINATORS) * sizeof(int4) : 0) +
+            (v.csplit ? n_ch * 256 * sizeof(float) : 0);
+    return v;
 }
 
 }  // namespace bpmf
@@ -1314,17 +1408,30 @@ extern "C" int bpmf_mf_prepare_data_dev(const float* d_data, size_t L, size_t N,
     return 0;
 }
 
-extern "C" int bpmf_mf_run_dev(const float* d_templates, const int32_t* d_moveouts,
-                               const float* d_weights, const float* d_data, size_t step, size_t L,
-                               size_t N, size_t T, size_t S, size_t C, size_t n_corr,
-                               int network_sum, int flags, void* d_workspace,
-                               size_t workspace_bytes, bpmf_stream_t stream_, float* d_cc_out)
+namespace {
+
+template <int V>
+using IntC = std::integral_constant<int, V>;
+
+// f(network_sum, step1, sqrt_norm) with the three as std::bool_constant: the one place where they become
+// template arguments
+template <typename F>
+int with_sum_step_norm(bool network_sum, bool step1, bool sqrt_norm, F f)
 {
-    hipStream_t stream = (hipStream_t)stream_;
-    if (!d_templates || !d_moveouts || !d_weights || !d_data || !d_workspace || !d_cc_out) {
-        set_error("bpmf_mf_run_dev: null pointer");
-        return -1;
-    }
+    auto norm = [&](auto ns_c, auto s1_c) -> int {
+        return sqrt_norm ? f(ns_c, s1_c, std::true_type{}) : f(ns_c, s1_c, std::false_type{});
+    };
+    auto step = [&](auto ns_c) -> int { return step1 ? norm(ns_c, std::true_type{}) : norm(ns_c, std::false_type{}); };
+    return network_sum ? step(std::true_type{}) : step(std::false_type{});
+}
+
+// bpmf_mf_run_dev over the data offsets of `lc`.  Preconditions of a range: a variant of the MFMA kernels that
+// is not mf.split16 (a channel's scale is its maximum over the WHOLE day), off_lo a multiple of MF_LAGS_PER_WG.
+int mf_run_dev(const float* d_templates, const int32_t* d_moveouts, const float* d_weights, const float* d_data,
+               size_t step, size_t L, size_t N, size_t T, size_t S, size_t C, size_t n_corr, int network_sum,
+               int flags, void* d_workspace, size_t workspace_bytes, hipStream_t stream, float* d_cc_out,
+               const MfLaunch& lc)
+{
     if (int rc = mf_check_sizes(step, L, N, T, S, C, n_corr)) return rc;
     const size_t n_ch = S * C;
     MfWorkspace ws = mf_carve(d_workspace, L, N, T, n_ch);
@@ -1333,184 +1440,136 @@ extern "C" int bpmf_mf_run_dev(const float* d_templates, const int32_t* d_moveou
         return -1;
     }
     if (!(flags & BPMF_MF_DATA_PREPARED)) {
-        if (int rc = bpmf_mf_prepare_data_dev(d_data, L, N, S, C, d_workspace, workspace_bytes,
-                                              stream_))
+        if (int rc = bpmf_mf_prepare_data_dev(d_data, L, N, S, C, d_workspace, workspace_bytes, stream))
             return rc;
     }
-    const size_t lds = mf_lds_bytes((int)L);
-    // the MFMA kernels evaluate every data-sample offset and keep the multiples of `step`
-    const size_t n_offsets = (n_corr - 1) * step + 1;
-    const size_t n_lag_blocks = (n_offsets + MF_LAGS_PER_WG - 1) / MF_LAGS_PER_WG;
-    // staging registers needed per thread (window / band), rounded to a compiled variant
-    const int need_r = (mf_window_len((int)L) + MF_THREADS - 1) / MF_THREADS;
-    const int need_t = (mf_band_len((int)L) + MF_THREADS - 1) / MF_THREADS;
-    const size_t max_mfma_step = (size_t)option(OPT_MF_MAX_MFMA_STEP);  // beyond this (64) the direct kernel wins
-    // (the MFMA kernels address the data through buffer descriptors with 32-bit byte offsets:
-    // traces of 2^30 samples or more take the generic kernel)
-    // option mf.compat_sqrt_norm: num / sqrtf(E_t * E_d) in the epilogue of the MFMA kernels too (network sums and,
-    // since round 6, per-channel output: the inter-template CC keeps MFMA speed under the upstream-recollected profile)
-    const bool sqrt_norm = option(OPT_MF_COMPAT_SQRT_NORM) != 0;
-    const bool use_mfma = mf_uses_mfma(step, L, N, T, n_corr, network_sum, flags);
-    (void)max_mfma_step;
-    // a launch over a range of data offsets (bpmf_mf_run, see t_mf_off_lo): MFMA kernels only
-    const bool ranged = t_mf_off_hi >= 0;
-    if (ranged && (!use_mfma || t_mf_off_lo % MF_LAGS_PER_WG != 0)) {
+    const bool ranged = lc.off_hi >= 0;
+    const MfVariant v = mf_choose(step, L, N, T, n_ch, n_corr, network_sum, flags, ranged);
+    if (ranged && (v.family == MF_DIRECT || lc.off_lo % MF_LAGS_PER_WG != 0)) {
         set_error("bpmf_mf_run_dev: internal error: a range of lag blocks on a launch that cannot take one");
         return -1;
     }
-    const size_t off_lo = ranged ? (size_t)t_mf_off_lo : 0;
-    const size_t off_hi = ranged ? std::min<size_t>((size_t)t_mf_off_hi, n_offsets) : n_offsets;
-    if (off_hi <= off_lo) return 0;
-    const bool first_piece = !(ranged && t_mf_continue);
-    // option mf.split16: the split-precision kernel takes every launch the MFMA kernels would take (use_mfma: the
-    // template-length limit stated in include/bpmf_hip.h; in segments of at most 376 samples; under mf.compat_sqrt_norm its epilogue divides by sqrtf(E_t * E_d))
-    // mf.split16 = 1 leaves small launches to the exact kernel (below SP_MIN_BLOCKS (template, 8192-lag block) pairs a
-    // wave's chain of per-channel stagings is latency, not rate: configs[0], 88 pairs, ran 0.71x the exact kernel's speed, 176 pairs x 1.1-1.6:
-    // profiles/r06_mf_split16.txt); = 2 takes the split kernel for every launch (the small shapes of the tests)
-    constexpr size_t SP_MIN_BLOCKS = 128;
-    const bool sp_small = option(OPT_MF_SPLIT16) == 1 && T * ((n_offsets + sp::LAGS_PER_WG - 1) / sp::LAGS_PER_WG) < SP_MIN_BLOCKS;
-    const bool split16 = ws.sp_day != nullptr && use_mfma && sp::usable(L, N) && !sp_small;
-    if (split16 && ranged) {
+    if (ranged && v.family == MF_SPLIT16) {
         set_error("bpmf_mf_run_dev: internal error: a range of lag blocks under mf.split16");
         return -1;
     }
-    if (split16 && !split_day_known(d_workspace, d_data, N, n_ch)) {
+    const size_t n_offsets = (n_corr - 1) * step + 1;
+    const size_t off_lo = ranged ? (size_t)lc.off_lo : 0;
+    const size_t off_hi = ranged ? std::min<size_t>((size_t)lc.off_hi, n_offsets) : n_offsets;
+    if (off_hi <= off_lo) return 0;
+    if (v.family == MF_SPLIT16 && !split_day_known(d_workspace, d_data, N, n_ch)) {
         set_error("bpmf_mf_run_dev: option mf.split16 is on but the day in this workspace was prepared without it (or is "
                   "another day): call bpmf_mf_prepare_data_dev again, or drop BPMF_MF_DATA_PREPARED");
         return -1;
     }
-    const bool wave_kernel = !split16 && use_mfma && option(OPT_MF_WAVE_KERNEL) != 0 && mf_kpad((int)L) <= 272;
-    // tiles (of 256 lags) per wave of that kernel: 4 unless the problem is too small to give every SIMD ~4 waves
-    // (option mf.tiles_per_wave: 0 = this rule, 1 / 2 / 4 = forced)
-    // (calibrated on an hour-long series with 4 .. 256 templates, tools/probe_mf_ntile_T.py,
-    // profiles/r04_mf_ntile_T.txt: 4 tiles from two full rounds of 4 waves per SIMD on, 2 tiles -- 5 waves
-    // per SIMD at 83-90 VGPRs -- from one wave per SIMD on, 1 tile below)
-    // (by the size of the WHOLE problem, also for a launch over a range: every piece takes the same variant)
-    const size_t waves4 = T * ((n_offsets + 4095) / 4096) * 4;
-    int ntile = waves4 >= 8192 ? 4 : (waves4 >= 1024 ? 2 : 1);
-    {
-        const long forced = option(OPT_MF_TILES_PER_WAVE);
-        if (forced == 1 || forced == 2 || forced == 4) ntile = (int)forced;
+    if (v.refusal) {
+        set_error("bpmf_mf_run_dev: %s", MF_REFUSAL_TEXT[v.refusal]);
+        return -1;
     }
-    // small problems: the wave kernel does the per-template preparation itself (mf_fused_prologue)
-    const bool fused = wave_kernel && ntile < 4 && n_ch <= 256 && option(OPT_MF_FUSED_PROLOGUE) != 0;
     // (bit 0: mf.compat_exclusive_last_lag, bit 1: mf.compat_range_all_channels -- both only shape the valid lag range)
     const int exclusive_last = (option(OPT_MF_COMPAT_EXCLUSIVE_LAST_LAG) != 0 ? 1 : 0) |
                                (option(OPT_MF_COMPAT_RANGE_ALL_CHANNELS) != 0 ? 2 : 0);
-    if (!fused) {
+    if (v.prologue) {
         // template norms, lag ranges, channel records: one launch, one workgroup per template (also in front
         // of every later piece of a batch: the pieces of two batches alternate, and the records live in the
         // one workspace both use)
         mf_prologue_kernel<<<dim3((unsigned)T), dim3(64), 0, stream>>>(
             d_templates, d_moveouts, d_weights, (int)T, (int)n_ch, (long long)step, (long long)L, (long long)N,
-            (long long)n_corr, exclusive_last, sqrt_norm ? 1 : 0, ws.e_t, ws.range, ws.chan_rec);
+            (long long)n_corr, exclusive_last, v.sqrt_norm ? 1 : 0, ws.e_t, ws.range, ws.chan_rec);
         BPMF_LAUNCH_CHECK();
     }
-    if (!first_piece) {
-    } else if (!network_sum)
+    if (lc.first_piece && !network_sum)
         BPMF_HIP_CHECK(hipMemsetAsync(d_cc_out, 0, T * n_corr * n_ch * sizeof(float), stream));
-    else if (option(OPT_DEBUG_POISON_OUTPUT) != 0)      // tests: a CC sum that no kernel writes comes back as NaN
+    else if (lc.first_piece && option(OPT_DEBUG_POISON_OUTPUT) != 0)      // tests: a CC sum that no kernel writes comes back as NaN
         BPMF_HIP_CHECK(hipMemsetAsync(d_cc_out, 0xFF, T * n_corr * sizeof(float), stream));
 
+    // lag blocks [nb_lo, nb_lo + nb_cnt) of the variant's own size (off_lo is a multiple of 4096 = of every variant's span)
+    const size_t nb_lo = off_lo / v.lags_wg, nb_cnt = (off_hi - off_lo + v.lags_wg - 1) / v.lags_wg;
+    const dim3 grid((unsigned)mf_grid(T, nb_cnt));
+    const int prio = (int)option(OPT_MF_BOUNDARY_PRIO);
     profile_mark(BPMF_KERNEL_MF_MAIN, 0, stream);
-    if (split16) {
-        const size_t nb_cnt = (n_offsets + sp::LAGS_PER_WG - 1) / sp::LAGS_PER_WG;
-        if (int rc = sp::run(d_templates, d_moveouts, ws.sp_day, ws.sp_batch, ws.chan_rec, ws.e_d, ws.range, step, L, N, T,
-                             n_ch, n_corr, network_sum, sqrt_norm ? 1 : 0, 0, nb_cnt, d_cc_out, stream))
-            return rc;
-    } else if (use_mfma) {
-        // 8 XCDs x ceil(n_lag_blocks x T / 8) (lag block, template) pairs (mf_tile_of_block)
-        const size_t nb_lo = off_lo / MF_LAGS_PER_WG, nb_cnt = (off_hi - off_lo + MF_LAGS_PER_WG - 1) / MF_LAGS_PER_WG;
-        dim3 grid((unsigned)(8 * ((T * nb_cnt + 7) / 8)));
-        const bool big_lds = lds > 64 * 1024;  // long templates: opt in to > 64 KB dynamic LDS
-#define BPMF_MF_LAUNCH2(NS, R, TT, S1) \
-    do { if (sqrt_norm) BPMF_MF_LAUNCH3(NS, R, TT, S1, true); else BPMF_MF_LAUNCH3(NS, R, TT, S1, false); } while (0)
-#define BPMF_MF_LAUNCH3(NS, R, TT, S1, SQ)                                                        \
-    do {                                                                                              \
-        auto kfn = mf_mfma_kernel<NS, R, TT, S1, SQ>;                                                 \
-        if (big_lds)                                                                                  \
-            BPMF_HIP_CHECK(hipFuncSetAttribute((const void*)kfn,                                      \
-                                               hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024)); \
-        kfn<<<grid, dim3(MF_THREADS), lds, stream>>>(                                                 \
-            d_templates, ws.chan_rec, d_data, ws.e_d, ws.range, (int)L, (long long)N, (int)T,         \
-            (int)n_ch, (long long)n_corr, (int)step, d_cc_out, (int)nb_cnt,                            \
-            (int)option(OPT_MF_BOUNDARY_PRIO), (int)nb_lo);                                            \
-    } while (0)
-#define BPMF_MF_LAUNCH(NS, R, TT) \
-    do { if (step == 1) BPMF_MF_LAUNCH2(NS, R, TT, true); else BPMF_MF_LAUNCH2(NS, R, TT, false); } while (0)
-        if (wave_kernel) {                          // L <= 257: independent waves, no barrier
-            const int Kp = mf_kpad((int)L), Ww = 256 * ntile - 16 + Kp;
-            // option mf.channel_split = n (0: off): tiny problems -- one tile per wave, fused prologue, network sum,
-            // step 1, at most 32 channels, at most n waves of 256 lags in the whole launch, not a piece of a larger
-            // launch -- run the CSPLIT variant: four waves per 256 lags, every fourth used channel each
-            const long csplit_max = option(OPT_MF_CHANNEL_SPLIT);
-            const bool csplit = ntile == 1 && fused && network_sum && step == 1 && n_ch <= 32 && !ranged &&
-                                csplit_max > 0 && waves4 * 4 <= (size_t)csplit_max;
-            const size_t lags_wg = csplit ? (size_t)256 : (size_t)4 * 256 * ntile;
-            const size_t nbw_lo = off_lo / lags_wg;       // (off_lo is a multiple of 4096 = of every variant's span)
-            const size_t n_blocks_w = (off_hi - off_lo + lags_wg - 1) / lags_wg;
-            if (T * (n_blocks_w + 8) >= 0x7fffffffull) {
-                set_error("bpmf_mf_run_dev: grid too large");
-                return -1;
-            }
-            dim3 grid_w((unsigned)(8 * ((T * n_blocks_w + 7) / 8)));
-            // (+ 256: slack for the operand prefetch one k-step past the end; FUSED: 16 ints + the channel records)
-            const int Wbuf = ntile < 4 ? 64 * (ntile == 2 ? 12 : 8) : Ww;      // (FULLW: room for every staging register)
-            const size_t wl = (size_t)4 * (mf_band_len((int)L) + (Wbuf + 2 * (Wbuf >> 4) + 2 + 63) / 64 * 64 + 64) * sizeof(float) + 256 +
-                              (fused ? 64 + (n_ch + MF_REC_TERMINATORS) * sizeof(int4) : 0) +
-                              (csplit ? n_ch * 256 * sizeof(float) : 0);
-#define BPMF_MF_WAVE_LAUNCH4(NS, S1, R, NT, SQ, FU)  BPMF_MF_WAVE_LAUNCH5(NS, S1, R, NT, SQ, FU, false)
-#define BPMF_MF_WAVE_LAUNCH5(NS, S1, R, NT, SQ, FU, CS)                                         \
-    mf_mfma_wave_kernel<NS, R, 5, S1, NT, SQ, FU, CS><<<grid_w, dim3(MF_THREADS), wl, stream>>>( \
-        d_templates, ws.chan_rec, d_data, ws.e_d, ws.range, (int)L, (long long)N, (int)T,        \
-        (int)n_ch, (long long)n_corr, (int)step, d_cc_out, (int)n_blocks_w, (int)option(OPT_MF_BOUNDARY_PRIO), \
-        d_moveouts, d_weights, exclusive_last, (int)nbw_lo)
-#define BPMF_MF_WAVE_LAUNCH3(NS, S1, R, NT, FU) \
-    do { if (sqrt_norm) BPMF_MF_WAVE_LAUNCH4(NS, S1, R, NT, true, FU); else BPMF_MF_WAVE_LAUNCH4(NS, S1, R, NT, false, FU); } while (0)
-#define BPMF_MF_WAVE_LAUNCH(NS, S1)                                                              \
-    do {                                                                                         \
-        if (ntile == 4) BPMF_MF_WAVE_LAUNCH3(NS, S1, 20, 4, false);                              \
-        else if (ntile == 2 && fused) BPMF_MF_WAVE_LAUNCH3(NS, S1, 12, 2, true);                 \
-        else if (ntile == 2) BPMF_MF_WAVE_LAUNCH3(NS, S1, 12, 2, false);                         \
-        else if (fused) BPMF_MF_WAVE_LAUNCH3(NS, S1, 8, 1, true);                                \
-        else BPMF_MF_WAVE_LAUNCH3(NS, S1, 8, 1, false);                                          \
-    } while (0)
-            if (csplit) { if (sqrt_norm) BPMF_MF_WAVE_LAUNCH5(true, true, 8, 1, true, true, true); else BPMF_MF_WAVE_LAUNCH5(true, true, 8, 1, false, true, true); }
-            else if (network_sum && step == 1) BPMF_MF_WAVE_LAUNCH(true, true);
-            else if (network_sum) BPMF_MF_WAVE_LAUNCH(true, false);
-            else if (step == 1) BPMF_MF_WAVE_LAUNCH(false, true);
-            else BPMF_MF_WAVE_LAUNCH(false, false);
-#undef BPMF_MF_WAVE_LAUNCH
-#undef BPMF_MF_WAVE_LAUNCH3
-#undef BPMF_MF_WAVE_LAUNCH4
-#undef BPMF_MF_WAVE_LAUNCH5
-        } else if (need_r <= 17 && need_t <= 2) {   // L <= 273
-            if (network_sum) BPMF_MF_LAUNCH(true, 17, 2); else BPMF_MF_LAUNCH(false, 17, 2);
-        } else if (need_r <= 20 && need_t <= 5) {   // L <= 1041
-            if (network_sum) BPMF_MF_LAUNCH(true, 20, 5); else BPMF_MF_LAUNCH(false, 20, 5);
-        } else {                                    // L <= 2049 (mf_uses_mfma: need_r <= 24)
-            if (network_sum) BPMF_MF_LAUNCH(true, 24, 9); else BPMF_MF_LAUNCH(false, 24, 9);
+    const int rc = with_sum_step_norm(network_sum != 0, v.step1, v.sqrt_norm, [&](auto ns_c, auto s1_c, auto sq_c) -> int {
+        constexpr bool NS = decltype(ns_c)::value, S1 = decltype(s1_c)::value, SQ = decltype(sq_c)::value;
+        auto workgroup = [&](auto maxr_c, auto maxt_c) -> int {
+            auto kern = mf_mfma_kernel<NS, decltype(maxr_c)::value, decltype(maxt_c)::value, S1, SQ>;
+            if (v.lds > 64 * 1024)   // long templates: opt in to > 64 KB dynamic LDS
+                BPMF_HIP_CHECK(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+            kern<<<grid, dim3(MF_THREADS), v.lds, stream>>>(
+                d_templates, ws.chan_rec, d_data, ws.e_d, ws.range, (int)L, (long long)N, (int)T, (int)n_ch,
+                (long long)n_corr, (int)step, d_cc_out, (int)nb_cnt, prio, (int)nb_lo);
+            return 0;
+        };
+        auto wave = [&](auto ntile_c, auto fused_c, auto csplit_c) -> int {
+            constexpr int NTILE = decltype(ntile_c)::value;
+            mf_mfma_wave_kernel<NS, mf_wave_maxr(NTILE), MF_WAVE_MAXT, S1, NTILE, SQ, decltype(fused_c)::value,
+                                decltype(csplit_c)::value><<<grid, dim3(MF_THREADS), v.lds, stream>>>(
+                d_templates, ws.chan_rec, d_data, ws.e_d, ws.range, (int)L, (long long)N, (int)T, (int)n_ch,
+                (long long)n_corr, (int)step, d_cc_out, (int)nb_cnt, prio, d_moveouts, d_weights, exclusive_last,
+                (int)nb_lo);
+            return 0;
+        };
+        auto direct = [&]() -> int {
+            mf_direct_kernel<NS, SQ><<<dim3((unsigned)((n_corr + 255) / 256), (unsigned)T), dim3(256), 0, stream>>>(
+                d_templates, d_moveouts, d_weights, d_data, ws.e_t, ws.e_d, ws.range, (long long)step, (int)L,
+                (long long)N, (int)n_ch, (long long)n_corr, d_cc_out, ws.local, ws.off,
+                (long long)((N + CSUM_CHUNK - 1) / CSUM_CHUNK));
+            return 0;
+        };
+        const std::true_type yes{};
+        const std::false_type no{};
+        switch (v.family) {
+            case MF_SPLIT16:
+                return sp::run(d_templates, d_moveouts, ws.sp_day, ws.sp_batch, ws.chan_rec, ws.e_d, ws.range, step, L, N,
+                               T, n_ch, n_corr, network_sum, v.sqrt_norm ? 1 : 0, 0, nb_cnt, d_cc_out, stream);
+            case MF_WORKGROUP:
+                return v.maxr == 20 ? workgroup(IntC<20>{}, IntC<5>{})      // L <= 1025
+                                    : workgroup(IntC<24>{}, IntC<9>{});     // L <= 2049
+            case MF_WAVE:
+                if constexpr (NS && S1)
+                    if (v.csplit) return wave(IntC<1>{}, yes, yes);
+                if (v.ntile == 4) return wave(IntC<4>{}, no, no);
+                if (v.ntile == 2) return v.fused ? wave(IntC<2>{}, yes, no) : wave(IntC<2>{}, no, no);
+                return v.fused ? wave(IntC<1>{}, yes, no) : wave(IntC<1>{}, no, no);
+            default:
+                return direct();
         }
-#undef BPMF_MF_LAUNCH
-#undef BPMF_MF_LAUNCH2
-#undef BPMF_MF_LAUNCH3
-    } else {
-        dim3 grid((unsigned)((n_corr + 255) / 256), (unsigned)T);
-        if (T > 65535) {
-            set_error("bpmf_mf_run_dev: generic kernel supports at most 65535 templates per call");
-            return -1;
-        }
-        const long long nq = (long long)((N + CSUM_CHUNK - 1) / CSUM_CHUNK);
-#define BPMF_MF_DIRECT(NS, SQ)                                                                     \
-    mf_direct_kernel<NS, SQ><<<grid, dim3(256), 0, stream>>>(                                      \
-        d_templates, d_moveouts, d_weights, d_data, ws.e_t, ws.e_d, ws.range, (long long)step,     \
-        (int)L, (long long)N, (int)n_ch, (long long)n_corr, d_cc_out, ws.local, ws.off, nq)
-        if (network_sum) { if (sqrt_norm) BPMF_MF_DIRECT(true, true); else BPMF_MF_DIRECT(true, false); }
-        else { if (sqrt_norm) BPMF_MF_DIRECT(false, true); else BPMF_MF_DIRECT(false, false); }
-#undef BPMF_MF_DIRECT
-    }
+    });
+    if (rc) return rc;
     BPMF_LAUNCH_CHECK();
     profile_mark(BPMF_KERNEL_MF_MAIN, 1, stream);
+    return 0;
+}
+
+}  // namespace
+
+extern "C" int bpmf_mf_run_dev(const float* d_templates, const int32_t* d_moveouts, const float* d_weights,
+                               const float* d_data, size_t step, size_t L, size_t N, size_t T, size_t S, size_t C,
+                               size_t n_corr, int network_sum, int flags, void* d_workspace, size_t workspace_bytes,
+                               bpmf_stream_t stream, float* d_cc_out)
+{
+    if (!d_templates || !d_moveouts || !d_weights || !d_data || !d_workspace || !d_cc_out) {
+        set_error("bpmf_mf_run_dev: null pointer");
+        return -1;
+    }
+    return mf_run_dev(d_templates, d_moveouts, d_weights, d_data, step, L, N, T, S, C, n_corr, network_sum, flags,
+                      d_workspace, workspace_bytes, (hipStream_t)stream, d_cc_out, MfLaunch());
+}
+
+// The choice of mf_choose for a launch of these sizes under the current options, as out[BPMF_MF_LAUNCH_INFO_FIELDS]
+// (include/bpmf_hip.h).  No device, workspace or stream is touched.
+extern "C" int bpmf_mf_launch_info(size_t step, size_t L, size_t N, size_t T, size_t S, size_t C, size_t n_corr,
+                                   int network_sum, int flags, int64_t* out)
+{
+    if (!out) {
+        set_error("bpmf_mf_launch_info: null pointer");
+        return -1;
+    }
+    if (int rc = mf_check_sizes(step, L, N, T, S, C, n_corr)) return rc;
+    const MfVariant v = mf_choose(step, L, N, T, S * C, n_corr, network_sum, flags, false);
+    const int64_t fields[BPMF_MF_LAUNCH_INFO_FIELDS] = {
+        v.family, v.maxr, v.maxt, v.ntile, v.fused, v.csplit, v.sqrt_norm, v.step1, v.prologue,
+        (int64_t)v.lags_wg, (int64_t)v.lds, (int64_t)v.grid, v.refusal};
+    memcpy(out, fields, sizeof(fields));
     return 0;
 }
 
@@ -1520,6 +1579,33 @@ extern "C" int bpmf_mf_run_dev(const float* d_templates, const int32_t* d_moveou
 // second stream drains the previous batch in 64 MB pieces into two pinned buffers, from which a
 // few host threads copy into the caller's array while the next piece is in flight: the call takes
 // about max(compute, transfer) instead of their sum.
+
+// Batches [bt[b], bt[b + 1]) of the host-pointer call: at most TB templates each, TAPERING at the end -- ..., 21, 13, 8, 5, 3, 2.
+// The result of a batch travels to the host while the NEXT batch is computed; behind the last kernel there
+// is nothing left to hide a transfer behind, and a transfer takes about half as long as computing the same
+// templates: with equal batches the call ended with ~30 ms of draining (round 5: 17 batches of 31 and one
+// of 4 -- the drain of the last full batch outlived the 8 ms of the small one).  Each batch of the taper is
+// ~0.6 of the one before, so every drain fits behind the next kernel and the call ends with the drain of two
+// templates.  (Every launch still has thousands of workgroups: the lag blocks.)
+static std::vector<size_t> mf_batch_starts(size_t T, size_t TB)
+{
+    std::vector<size_t> taper;                    // from the end: 2, 3, 5, 8, 13, 21, ...  while below TB
+    size_t a = 2, b2 = 3, used = 0;
+    while (a < TB && used + a <= T) {
+        taper.push_back(a);
+        used += a;
+        const size_t next = b2;                   // 2, 3, 5, 8, 13, 21: each ~1.6 x the one behind it
+        b2 = a + b2;
+        a = next;
+    }
+    const size_t rest = T - used;
+    const size_t n_full = (rest + TB - 1) / TB;
+    std::vector<size_t> bt(1, 0);
+    for (size_t i = 0; i < n_full; ++i)           // near-equal batches of at most TB
+        bt.push_back(bt.back() + rest / n_full + (i < rest % n_full ? 1 : 0));
+    for (size_t i = taper.size(); i-- > 0;) bt.push_back(bt.back() + taper[i]);
+    return bt;
+}
 
 static int bpmf_mf_run_impl(const float* templates, const int32_t* moveouts, const float* weights,
                            const float* data, size_t step, size_t L, size_t N, size_t T, size_t S,
@@ -1544,31 +1630,7 @@ static int bpmf_mf_run_impl(const float* templates, const int32_t* moveouts, con
     size_t TB = std::max<size_t>(1, batch_bytes / std::max<size_t>(row_bytes, 1));
     if (!e_b) TB = std::max<size_t>(TB, 8);   // a launch of fewer templates wastes the device
     TB = std::min(T, TB);
-    // Batches [bt[b], bt[b + 1]): at most TB templates each, TAPERING at the end -- ..., 21, 13, 8, 5, 3, 2.
-    // The result of a batch travels to the host while the NEXT batch is computed; behind the last kernel there
-    // is nothing left to hide a transfer behind, and a transfer takes about half as long as computing the same
-    // templates: with equal batches the call ended with ~30 ms of draining (round 5: 17 batches of 31 and one
-    // of 4 -- the drain of the last full batch outlived the 8 ms of the small one).  Each batch of the taper is
-    // ~0.6 of the one before, so every drain fits behind the next kernel and the call ends with the drain of two
-    // templates.  (Every launch still has thousands of workgroups: the lag blocks.)
-    std::vector<size_t> bt;
-    {
-        std::vector<size_t> taper;                    // from the end: 2, 3, 5, 8, 13, 21, ...  while below TB
-        size_t a = 2, b2 = 3, used = 0;
-        while (a < TB && used + a <= T) {
-            taper.push_back(a);
-            used += a;
-            const size_t next = b2;                   // 2, 3, 5, 8, 13, 21: each ~1.6 x the one behind it
-            b2 = a + b2;
-            a = next;
-        }
-        const size_t rest = T - used;
-        const size_t n_full = (rest + TB - 1) / TB;
-        bt.push_back(0);
-        for (size_t i = 0; i < n_full; ++i)           // near-equal batches of at most TB
-            bt.push_back(bt.back() + rest / n_full + (i < rest % n_full ? 1 : 0));
-        for (size_t i = taper.size(); i-- > 0;) bt.push_back(bt.back() + taper[i]);
-    }
+    const std::vector<size_t> bt = mf_batch_starts(T, TB);
     const size_t n_batch = bt.size() - 1;
     const size_t b_tp = T * n_ch * L * sizeof(float), b_mv = T * n_ch * sizeof(int32_t),
                  b_w = T * n_ch * sizeof(float), b_d = n_ch * N * sizeof(float),
@@ -1608,11 +1670,11 @@ static int bpmf_mf_run_impl(const float* templates, const int32_t* moveouts, con
     if (!rc) MF_TRY(staged_upload_rows(ctx, (float*)(base + o_w), weights, 1, b_w / 4, 0, b_w / 4, s_run), "H2D weights");
     // ---- The day of data.  A peer of a multi-device call copies it from the first device; a small problem
     // uploads it in one go.  A day-long series arrives IN PIECES on the copy stream while the first
-    // template batch is computed on the lags whose windows have arrived (launches of bpmf_mf_run_dev over
-    // ranges of lag blocks, t_mf_off_lo): the 2 GB of configs[1] took 90 ms in front of the first kernel
+    // template batch is computed on the lags whose windows have arrived (launches of mf_run_dev over
+    // ranges of lag blocks, MfLaunch): the 2 GB of configs[1] took 90 ms in front of the first kernel
     // (1072.7 ms end to end against 982.9 resident, round-4 bench; BPMF makes exactly this call,
     // similarity_search.py:526-533).
-    const bool use_mfma = mf_uses_mfma(step, L, N, std::min(TB, T), n_corr, network_sum, flags);
+    const bool use_mfma = mf_choose(step, L, N, std::min(TB, T), n_ch, n_corr, network_sum, flags, true).family != MF_DIRECT;
     const size_t n_offsets = (n_corr - 1) * step + 1;
     bool from_peer = false;
     if (!rc) {
@@ -1626,19 +1688,12 @@ static int bpmf_mf_run_impl(const float* templates, const int32_t* moveouts, con
     // (not under mf.split16: a channel's scale is its maximum over the WHOLE day)
     const bool pieces = !rc && !from_peer && use_mfma && option(OPT_MF_COMPAT_SEQUENTIAL_CSUM) == 0 &&
                         option(OPT_MF_SPLIT16) == 0 && PIECE0 != 0 && N >= 8 * PIECE0;
-    auto launch_range = [&](size_t b, long long off_lo, long long off_hi, bool cont) {
+    auto launch_range = [&](size_t b, const MfLaunch& lc) {
         const size_t t0 = bt[b], nt = bt[b + 1] - bt[b];
         char* d_out = base + ((b & 1) ? o_out1 : o_out0);
-        struct Scope {
-            Scope(long long lo, long long hi, bool c) { t_mf_off_lo = lo; t_mf_off_hi = hi; t_mf_continue = c; }
-            ~Scope() { t_mf_off_lo = 0; t_mf_off_hi = -1; t_mf_continue = false; }
-        } scope(off_lo, off_hi, cont);
-        return bpmf_mf_run_dev((const float*)(base + o_tp) + t0 * n_ch * L,
-                               (const int32_t*)(base + o_mv) + t0 * n_ch,
-                               (const float*)(base + o_w) + t0 * n_ch, (const float*)(base + o_d),
-                               step, L, N, nt, S, C, n_corr, network_sum,
-                               (flags & ~BPMF_MF_DATA_PREPARED) | BPMF_MF_DATA_PREPARED,
-                               base + o_ws, b_ws, s_run, (float*)d_out);
+        return mf_run_dev((const float*)(base + o_tp) + t0 * n_ch * L, (const int32_t*)(base + o_mv) + t0 * n_ch,
+                          (const float*)(base + o_w) + t0 * n_ch, (const float*)(base + o_d), step, L, N, nt, S, C,
+                          n_corr, network_sum, flags | BPMF_MF_DATA_PREPARED, base + o_ws, b_ws, s_run, (float*)d_out, lc);
     };
     size_t n_streamed = 0;            // batches computed while the data arrived (their events are recorded)
     if (pieces) {
@@ -1681,7 +1736,7 @@ static int bpmf_mf_run_impl(const float* templates, const int32_t* moveouts, con
                                          : ((long long)have - mv_max[b] - (long long)L - 2 * MF_LAGS_PER_WG) / MF_LAGS_PER_WG * MF_LAGS_PER_WG;
                 hi = std::min<long long>(hi, (long long)n_offsets);
                 if (hi <= done[b]) continue;
-                rc = launch_range(b, done[b], hi, done[b] > 0);
+                rc = launch_range(b, MfLaunch{done[b], hi, done[b] == 0});
                 if (t_call_stats.first_kernel_ms == 0.0) t_call_stats.first_kernel_ms = host_now_ms() - t_call0;
                 done[b] = hi;
             }
@@ -1703,7 +1758,7 @@ static int bpmf_mf_run_impl(const float* templates, const int32_t* moveouts, con
     }
     auto launch = [&](size_t b) {
         if (b < n_streamed) return 0;                            // computed while the data arrived
-        int r = launch_range(b, 0, -1, false);
+        int r = launch_range(b, MfLaunch());
         if (!r) MF_TRY(hipEventRecord(ev_batch[b & 1], s_run), "event record");
         return r;
     };

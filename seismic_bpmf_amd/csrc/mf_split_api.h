@@ -13,7 +13,7 @@ size_t day_region_bytes(size_t N, size_t n_ch);
 size_t batch_region_bytes(size_t T, size_t n_ch, size_t L);
 
 // can the split kernel's own arithmetic take this launch?  (segments of at most 376 samples, sized for 4096; N < 2^30 -
-// 8192.)  bpmf_mf_run_dev asks mf_uses_mfma first: the template-length limit of mf.split16 is the one stated in
+// 8192.)  mf_choose asks whether the MFMA kernels take the launch first: the template-length limit of mf.split16 is the one stated in
 // include/bpmf_hip.h.
 bool usable(size_t L, size_t N);
 

@@ -43,7 +43,7 @@ const OptionDef OPTION_DEFS[OPT_COUNT] = {
     {"bp.fast_tile", 0, 0, 512, true},        // 0: the cost model picks each class's tile; 512 / 256 / 128: only that one
     {"bp.halves", 1, 0, 1, true},             // 33-64 stations: two LDS residencies per group at tile 256 where cheaper
     {"bp.direct", 0, 0, 1, true},             // 1: every plan takes the global-memory path of bp_direct.hip (tests)
-    {"mf.wave_kernel", 1, 0, 1, false},        // independent-wave kernel for L <= 257
+    {"mf.wave_kernel", 1, 0, 1, false},        // independent-wave kernel for L <= 257 (0: the workgroup kernel takes those lengths too)
     {"mf.max_mfma_step", 64, 0, 1 << 20, false},  // larger steps take the generic kernel
     {"mf.host_batch_kb", 0, 0, 1L << 30, false},  // host-pointer call: output per batch (0 = 1 GB, >= 8 templates)
     {"mf.host_piece_kb", 0, 0, 1L << 30, false},  // host-pointer call: pinned piece (0 = 64 MB)

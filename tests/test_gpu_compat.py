@@ -6,6 +6,8 @@ against either convention."""
 import numpy as np
 import pytest
 
+from mf_launch import assert_takes
+
 pytestmark = pytest.mark.gpu
 
 
@@ -16,6 +18,18 @@ def _mf_case(seed, step):
     m["weights"][1, 2] = 0.0
     m["data"][0, 0, 2000:2300] = 0.0            # zero-energy windows: the stability rule matters
     return m
+
+
+def _mf_takes(m, step, network_sum, wave, ntile=0, **fields):
+    """The kernel family the options (mf.wave_kernel, mf.tiles_per_wave, mf.max_mfma_step = 0) are meant to select for
+    a case of _mf_case (L = 48) is the one its launches take."""
+    if wave is None:
+        fields.update(family="direct")
+    elif wave:
+        fields.update(family="wave", **({"ntile": ntile} if ntile else {}))
+    else:
+        fields.update(family="workgroup", maxr=20, maxt=5)
+    assert_takes(m["templates"].shape, m["data"].shape[-1], step, network_sum, **fields)
 
 
 @pytest.mark.parametrize("step", [1, 2, 3])
@@ -35,9 +49,11 @@ def test_mf_exclusive_last_lag(oracle_lib, hip_opts, step, network_sum):
     hip_opts("mf.compat_exclusive_last_lag", 1)
     for wave in (1, 0):
         hip_opts("mf.wave_kernel", wave)
+        _mf_takes(m, step, network_sum, wave)
         got = matched_filter(*args, arch="gpu", network_sum=network_sum, check_zeros=False)
         assert np.array_equal(got, want), (step, network_sum, wave)
     hip_opts("mf.max_mfma_step", 0)               # the generic kernel
+    _mf_takes(m, step, network_sum, None)
     assert np.array_equal(matched_filter(*args, arch="gpu", network_sum=network_sum, check_zeros=False), want)
     hip_opts.reset("mf.compat_exclusive_last_lag")
     assert np.array_equal(matched_filter(*args, arch="gpu", network_sum=network_sum, check_zeros=False), base)
@@ -64,9 +80,11 @@ def test_mf_sqrt_norm(oracle_lib, hip_opts, step, network_sum):
     for wave, ntile in ((1, 0), (1, 1), (1, 2), (1, 4), (0, 0)):
         hip_opts("mf.wave_kernel", wave)
         hip_opts("mf.tiles_per_wave", ntile)
+        _mf_takes(m, step, network_sum, wave, ntile, sqrt_norm=True)
         got = matched_filter(*args, arch="gpu", network_sum=network_sum, check_zeros=False)
         assert np.array_equal(got, want), (step, network_sum, wave, ntile)
     hip_opts("mf.max_mfma_step", 0)
+    _mf_takes(m, step, network_sum, None, sqrt_norm=True)
     assert np.array_equal(matched_filter(*args, arch="gpu", network_sum=network_sum, check_zeros=False), want)
     # both MF switches together
     hip_opts("mf.compat_exclusive_last_lag", 1)
@@ -181,9 +199,11 @@ def test_mf_range_all_channels(oracle_lib, hip_opts, step, network_sum):
     for wave, fused in ((1, 1), (1, 0), (0, 0)):
         hip_opts("mf.wave_kernel", wave)
         hip_opts("mf.fused_prologue", fused)
+        _mf_takes(m, step, network_sum, wave, fused=bool(fused), prologue=not fused)
         got = matched_filter(*args, arch="gpu", network_sum=network_sum, check_zeros=False)
         assert np.array_equal(got, want), (step, network_sum, wave, fused)
     hip_opts("mf.max_mfma_step", 0)               # the generic kernel
+    _mf_takes(m, step, network_sum, None)
     assert np.array_equal(matched_filter(*args, arch="gpu", network_sum=network_sum, check_zeros=False), want)
     hip_opts.reset("mf.compat_range_all_channels")
     assert np.array_equal(matched_filter(*args, arch="gpu", network_sum=network_sum, check_zeros=False), base)

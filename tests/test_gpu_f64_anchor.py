@@ -15,6 +15,7 @@ import numpy as np
 import pytest
 
 import f64_anchor as fa
+from mf_launch import assert_takes
 
 pytestmark = pytest.mark.gpu
 
@@ -35,9 +36,13 @@ def _mf_resident(args, step, ns):
     return again
 
 
-def _mf_family(label, L, step, N, run=_mf_host, regimes=("noise", "scaled", "int"), T=2, kw=None):
+def _mf_family(label, L, step, N, run=_mf_host, regimes=("noise", "scaled", "int"), T=2, kw=None, takes=None):
+    """`takes`: fields of bpmf_mf_launch_info the launches must show (a function of network_sum where it decides): the
+    family the caller's options are meant to select is the one that runs."""
     for regime in regimes:
         args = fa.mf_case(regime, L, N, step, seed=1000 + L + step, T=T)
+        for ns in (True, False):
+            assert_takes(args[0].shape, N, step, ns, **{k: v(ns) if callable(v) else v for k, v in (takes or {}).items()})
         ref = fa.mf_f64(*args, step=step, exact=regime == "int", **(kw or {}))
         assert ref.valid.any() and not ref.valid.all()
         assert fa.mf_dead_channels(args[0], ref) >= 1              # a dead template, weighted, inside the lag range
@@ -49,43 +54,49 @@ def _mf_family(label, L, step, N, run=_mf_host, regimes=("noise", "scaled", "int
 @pytest.mark.parametrize("wave_kernel", [1, 0])
 def test_mf_wave_and_workgroup_kernels(hip_opts, wave_kernel):
     hip_opts("mf.wave_kernel", wave_kernel)
+    takes = dict(family="wave") if wave_kernel else dict(family="workgroup", maxr=20, maxt=5)
     for L, step in ((200, 1), (257, 3), (1, 1)):
-        _mf_family(f"wave_kernel={wave_kernel}", L, step, 9300)
+        _mf_family(f"wave_kernel={wave_kernel}", L, step, 9300, takes=takes)
 
 
 @pytest.mark.parametrize("ntile", [1, 2, 4])
 def test_mf_tiles_per_wave(hip_opts, ntile):
     hip_opts("mf.tiles_per_wave", ntile)
-    _mf_family(f"tiles_per_wave={ntile}", 128, 1, 9100)
-    _mf_family(f"tiles_per_wave={ntile}", 40, 7, 5000)
+    _mf_family(f"tiles_per_wave={ntile}", 128, 1, 9100, takes=dict(family="wave", ntile=ntile))
+    _mf_family(f"tiles_per_wave={ntile}", 40, 7, 5000, takes=dict(family="wave", ntile=ntile))
 
 
 @pytest.mark.parametrize("fused", [1, 0])
 def test_mf_fused_prologue(hip_opts, fused):
     hip_opts("mf.tiles_per_wave", 1)
     hip_opts("mf.fused_prologue", fused)
-    _mf_family(f"fused_prologue={fused}", 100, 1, 2600)
-    _mf_family(f"fused_prologue={fused}", 33, 3, 2500)
+    takes = dict(family="wave", ntile=1, fused=bool(fused), prologue=not fused)
+    _mf_family(f"fused_prologue={fused}", 100, 1, 2600, takes=takes)
+    _mf_family(f"fused_prologue={fused}", 33, 3, 2500, takes=takes)
 
 
 def test_mf_channel_split(hip_opts):
     hip_opts("mf.channel_split", 1 << 20)
     hip_opts("mf.tiles_per_wave", 1)
+    takes = dict(family="wave", ntile=1, fused=True, csplit=lambda ns: ns)       # (the channel split is the network sum's)
     for L in (64, 256):
-        _mf_family("channel_split", L, 1, 5200)
-        _mf_family("channel_split resident", L, 1, 5200, run=_mf_resident, regimes=("noise", "int"))
+        _mf_family("channel_split", L, 1, 5200, takes=takes)
+        _mf_family("channel_split resident", L, 1, 5200, run=_mf_resident, regimes=("noise", "int"), takes=takes)
 
 
 @pytest.mark.parametrize("L", [300, 1100, 2065])
 def test_mf_long_template_kernels(L):
-    _mf_family("257 < L <= 2065", L, 1 if L != 1100 else 3, L + 7000)
+    # (the workgroup kernel's two register variants; 2065 is beyond its 2049 samples: the generic kernel)
+    takes = {300: dict(family="workgroup", maxr=20, maxt=5), 1100: dict(family="workgroup", maxr=24, maxt=9),
+             2065: dict(family="direct")}[L]
+    _mf_family("257 < L <= 2065", L, 1 if L != 1100 else 3, L + 7000, takes=takes)
 
 
 def test_mf_generic_kernel_long_templates_and_large_steps(hip_opts):
-    _mf_family("generic L > 2065", 2100, 1, 2100 + 5000)
-    _mf_family("generic step > max_mfma_step", 64, 70, 64 + 70 * 1500)
+    _mf_family("generic L > 2065", 2100, 1, 2100 + 5000, takes=dict(family="direct"))
+    _mf_family("generic step > max_mfma_step", 64, 70, 64 + 70 * 1500, takes=dict(family="direct"))
     hip_opts("mf.max_mfma_step", 0)
-    _mf_family("generic max_mfma_step=0", 200, 3, 6000)
+    _mf_family("generic max_mfma_step=0", 200, 3, 6000, takes=dict(family="direct"))
 
 
 def test_mf_host_call_small_batches_and_pieces(hip_opts):

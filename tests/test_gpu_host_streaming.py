@@ -8,6 +8,8 @@ oracle and with the same call made with streaming off."""
 import numpy as np
 import pytest
 
+from mf_launch import assert_takes
+
 pytestmark = pytest.mark.gpu
 
 
@@ -51,6 +53,9 @@ def test_mf_pieces_one_batch_and_short_templates(oracle_lib, hip_opts):
         hip_opts("mf.tiles_per_wave", ntile)
         for fused in (1, 0):
             hip_opts("mf.fused_prologue", fused)
+            # (3 templates over 17 lag blocks: one tile per wave by themselves; the pieces of the streamed batch are
+            # launches over ranges, which never split the channels)
+            assert_takes(tp.shape, N, family="wave", ntile=ntile or 1, fused=bool(fused) and ntile != 4)
             assert np.array_equal(matched_filter(tp, mv, w, d, 1, arch="gpu", device=0, check_zeros=False), want), (ntile, fused)
 
 

@@ -1,6 +1,7 @@
 """GPU: every kernel variant the dispatchers can pick, each bit-exact against the oracle.
 
-MF: staging-register variants (L <= 273 / 1041 / 2065), the generic kernel beyond, step > 1.
+MF: the wave kernel (L <= 257), the workgroup kernel's staging-register variants (L <= 1025 / 2049), the generic
+kernel beyond, step > 1; wherever an option selects the family, bpmf_mf_launch_info confirms it (mf_launch.py).
 BP: packed two-phase records, wave-per-source (<= 32 terms/source), readlane kernels with 1 / 2 / 4
 metadata blocks (up to 256 terms/source), tile fall-backs, P = 1 / 3 / 5.
 """
@@ -8,6 +9,8 @@ import os
 
 import numpy as np
 import pytest
+
+from mf_launch import assert_takes
 
 pytestmark = pytest.mark.gpu
 
@@ -35,19 +38,25 @@ def test_mf_template_length_variants(oracle_lib, L):
 
 @pytest.mark.parametrize("wave_kernel", [0, 1])
 def test_mf_both_mfma_kernels(oracle_lib, wave_kernel, hip_opts):
-    """L <= 257 defaults to the independent-wave kernel; the workgroup kernel must agree too."""
+    """L <= 257 defaults to the independent-wave kernel; the workgroup kernel (its variant with 20 / 5 staging
+    registers) must agree too, also at both ends of that range."""
     from seismic_bpmf_amd import matched_filter
     hip_opts("mf.wave_kernel", wave_kernel)
-    rng = np.random.default_rng(77)
-    T, S, C, L, N = 3, 5, 3, 200, 30_000
-    tp = rng.standard_normal((T, S, C, L)).astype(np.float32)
-    mv = rng.integers(-50, 900, (T, S, C)).astype(np.int32)
-    w = rng.random((T, S, C)).astype(np.float32)
-    w[1, 2] = 0.0
-    d = rng.standard_normal((S, C, N)).astype(np.float32)
-    for ns in (True, False):
-        _same(matched_filter(tp, mv, w, d, 1, check_zeros=False, network_sum=ns),
-              oracle_lib.matched_filter(tp, mv, w, d, 1, ns), f"wave_kernel={wave_kernel} ns={ns}")
+    for L in (200, 1, 257):
+        rng = np.random.default_rng(77 if L == 200 else 77 + L)
+        T, S, C, N = 3, 5, 3, 30_000
+        tp = rng.standard_normal((T, S, C, L)).astype(np.float32)
+        mv = rng.integers(-50, 900, (T, S, C)).astype(np.int32)
+        w = rng.random((T, S, C)).astype(np.float32)
+        w[1, 2] = 0.0
+        d = rng.standard_normal((S, C, N)).astype(np.float32)
+        for ns in (True, False):
+            if wave_kernel:
+                assert_takes(tp.shape, N, 1, ns, family="wave")
+            else:
+                assert_takes(tp.shape, N, 1, ns, family="workgroup", maxr=20, maxt=5)
+            _same(matched_filter(tp, mv, w, d, 1, check_zeros=False, network_sum=ns),
+                  oracle_lib.matched_filter(tp, mv, w, d, 1, ns), f"wave_kernel={wave_kernel} L={L} ns={ns}")
 
 
 @pytest.mark.parametrize("ntile", [1, 2, 4])
@@ -71,6 +80,7 @@ def test_mf_tiles_per_wave(oracle_lib, ntile, L, hip_opts):
         d = rng.standard_normal((S, C, N)).astype(np.float32)
         for step in (1, 3):
             for ns in (True, False):
+                assert_takes(tp.shape, N, step, ns, family="wave", ntile=ntile, maxr={1: 8, 2: 12, 4: 20}[ntile])
                 _same(matched_filter(tp, mv, w, d, step, check_zeros=False, network_sum=ns),
                       oracle_lib.matched_filter(tp, mv, w, d, step, ns), f"ntile={ntile} L={L} N={N} step={step} ns={ns}")
 
@@ -107,6 +117,8 @@ def test_mf_fused_prologue(oracle_lib, fused, ntile, hip_opts):
             for ns in (True, False):
                 if not ns and T * S * C * N > 3_000_000:
                     continue
+                in_kernel = bool(fused) and S * C <= 256
+                assert_takes(tp.shape, N, step, ns, family="wave", ntile=ntile, fused=in_kernel, prologue=not in_kernel)
                 _same(matched_filter(tp, mv, w, d, step, check_zeros=False, network_sum=ns),
                       oracle_lib.matched_filter(tp, mv, w, d, step, ns),
                       f"fused={fused} ntile={ntile} T={T} S={S} C={C} L={L} N={N} step={step} ns={ns}")
@@ -121,6 +133,7 @@ def test_mf_fused_prologue(oracle_lib, fused, ntile, hip_opts):
         with oracle_lib.compat(flag):
             want = oracle_lib.matched_filter(tp, mv, w, d, 1)
         hip_opts(opt, 1)
+        assert_takes(tp.shape, N, family="wave", ntile=ntile, fused=bool(fused), sqrt_norm=opt == "mf.compat_sqrt_norm")
         _same(matched_filter(tp, mv, w, d, 1, check_zeros=False), want, f"fused={fused} ntile={ntile} {opt}")
         hip_opts(opt, 0)
 
@@ -174,6 +187,11 @@ def test_mf_first_samples_of_the_trace_with_negative_moveouts(oracle_lib, L, fir
         hip_opts("mf.wave_kernel", wave)
         for step in (1, 2):
             for ns in (True, False):
+                if wave and L <= 257:
+                    assert_takes(tp.shape, N, step, ns, family="wave")
+                else:
+                    assert_takes(tp.shape, N, step, ns, family="workgroup", maxr=20 if L <= 1025 else 24,
+                                 maxt=5 if L <= 1025 else 9)
                 _same(matched_filter(tp, mv, w, d, step, check_zeros=False, network_sum=ns),
                       oracle_lib.matched_filter(tp, mv, w, d, step, ns),
                       f"first={first} L={L} wave={wave} step={step} ns={ns}")
@@ -715,15 +733,18 @@ def test_mf_channel_split_variant(oracle_lib, L, S, C, hip_opts):
     want = oracle_lib.matched_filter(tp, mv, w, d, 1)
     hip_opts("mf.channel_split", 1 << 20)
     hip_opts("mf.tiles_per_wave", 1)
+    assert_takes(tp.shape, N, family="wave", ntile=1, fused=True, csplit=True, lags_per_wg=256)
     got = matched_filter(tp, mv, w, d, 1, arch="gpu", device=0, check_zeros=False)
     assert np.array_equal(got, want)
     eng = MatchedFilterGPU(device=0)
     eng.set_data(d)
     assert np.array_equal(eng.run(tp, mv, w, 1).cpu().numpy(), want)
     hip_opts("mf.channel_split", 0)
+    assert_takes(tp.shape, N, family="wave", ntile=1, fused=True, csplit=False, lags_per_wg=1024)
     assert np.array_equal(eng.run(tp, mv, w, 1).cpu().numpy(), want)
     hip_opts("mf.channel_split", 1 << 20)
     hip_opts("mf.compat_sqrt_norm", 1)
+    assert_takes(tp.shape, N, family="wave", csplit=True, sqrt_norm=True)
     with oracle_lib.compat(oracle_lib.COMPAT_SQRT_NORM):
         want2 = oracle_lib.matched_filter(tp, mv, w, d, 1)
     assert np.array_equal(matched_filter(tp, mv, w, d, 1, arch="gpu", device=0, check_zeros=False), want2)

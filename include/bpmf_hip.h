@@ -241,6 +241,41 @@ int bpmf_bp_plan_info(const bpmf_bp_plan *plan, bpmf_bp_plan_stats *out);
 
 size_t bpmf_bp_workspace_bytes(const bpmf_bp_plan *plan, size_t N, size_t C);
 
+/* The plan that bpmf_bp_plan_create would build from these host tables under the current options, and the schedule
+ * of one run on it: the host side of planning alone (the counterpart of bpmf_mf_launch_info).  Needs no device,
+ * workspace or stream.  n_events = 0: one series of N samples as bpmf_bp_run_dev runs it with this `reduce`;
+ * n_events = E >= 1: a batch of E series as bpmf_bp_relocate_batch_dev runs their max-beams (reduce max only).
+ * out[BPMF_BP_LAUNCH_INFO_FIELDS]:
+ *   the plan
+ *   [0] K  [1] S  [2] P         [3] samples per thread of the general kernels (tile = 256 x it; 4 without LDS plan)
+ *   [4] padded (station, phase) terms per source    [5] padded stations of the packed records (P = 2), or 0
+ *   [6] padded terms of the per-term table, or 0    [7] dual (shifted) windows    [8] groups  [9] LDS bytes of the largest
+ *   [10] 0: an LDS plan; else why the grid takes bp_direct.hip: 1 a source's windows exceed the LDS, 2 more than 256
+ *        terms per source, 3 option bp.direct, 4 option bp.compat_strict_upper_only and a negative used moveout
+ *   [11] interior-tile classes in use   [12] the one class doubles as the general kernels' plan   [13] classes
+ *   [14 + 7 c ...] class c = 0..2: tile, multi-residency groups, residencies per group, group entries, LDS bytes,
+ *        sources, most weighted stations of a source
+ *   [35] [36] smallest and largest used moveout     [37] source id offset (0)
+ *   the schedule
+ *   [38] path: 0 bp_direct.hip, 1 class kernels on the interior samples [lo_s, hi_s) + the general kernel on the edge
+ *        samples, 2 the general kernel on every sample
+ *   [39] general kernel: 0 none (path 0), 1 packed records (bp_beam_wps2_kernel), 2 per-term table
+ *        (bp_beam_wps_kernel), 3 bp_beam_kernel;  its template arguments: [40] waves per workgroup [41] stations
+ *        [42] 8-byte gathers (family 1), [43] terms (family 2), [44] samples per thread [45] blocks of 64 terms (family 3)
+ *   [46] its samples per workgroup  [47] dynamic LDS bytes  [48] resident waves per CU  [49] bytes per gather
+ *   [50] group ranges per tile (path 1: of every class kernel; path 0: source ranges)  [51] ... of the general kernel
+ *        on the edge samples
+ *   [52] partial (beam, arg) rows per series; 1: the kernels write the outputs themselves, no merge launch
+ *   [53] lo_s  [54] hi_s (both 0 unless path 1)
+ *   [55] [56] [57] byte offsets in the workspace of the prestack(s), the partial beam rows and the partial arg rows
+ *        ([56] = [57] when [52] is 1)              [58] bytes of the workspace up to the end of the partial rows:
+ *        bpmf_bp_workspace_bytes for n_events = 0 (sized for either `reduce`)
+ *   [59 ... 77] what bpmf_bp_plan_info reports of the plan: n_groups, tile, lds_bytes, gather_bytes, stations_max,
+ *        waves_per_cu, n_classes, class_tile[3], class_sources[3], class_groups[3], class_stations_max[3] */
+#define BPMF_BP_LAUNCH_INFO_FIELDS 78
+int bpmf_bp_launch_info(const int32_t *moveouts, const float *w_sources, size_t K, size_t S, size_t P,
+                        size_t N, int reduce, size_t n_events, int64_t *out);
+
 int bpmf_bp_run_dev(const bpmf_bp_plan *plan, const float *d_features,
                     const float *d_w_phases, size_t N, size_t C, int out_of_bounds,
                     int reduce, void *d_workspace, size_t workspace_bytes,

@@ -57,6 +57,7 @@ SIGNATURES = {
     "bpmf_bp_plan_destroy": (None, [_vp]),
     "bpmf_bp_plan_info": (C.c_int, [_vp, C.POINTER(BpPlanStats)]),
     "bpmf_bp_workspace_bytes": (_sz, [_vp, _sz, _sz]),
+    "bpmf_bp_launch_info": (C.c_int, [_i, _f, _sz, _sz, _sz, _sz, C.c_int, _sz, C.POINTER(C.c_int64)]),
     "bpmf_bp_run_dev": (C.c_int, [_vp, _vp, _vp, _sz, _sz, C.c_int, C.c_int, _vp, _sz, _vp, _vp, _vp]),
     "bpmf_bp_run": (C.c_int, [_f, _i, _f, _f, _sz, _sz, _sz, _sz, _sz, C.c_int, C.c_int, C.c_int,
                               _f, _i]),
@@ -208,6 +209,49 @@ def mf_launch_info(step, L, N, T, n_stations, n_components, network_sum=True, fl
     info["family"] = MF_FAMILIES[info["family"]]
     info["refusal"] = MF_REFUSALS[info["refusal"]]
     return info
+
+
+BP_DIRECT_REASONS = (None, "windows exceed the LDS", "more than 256 terms per source", "bp.direct",
+                     "bp.compat_strict_upper_only with a negative used moveout")
+BP_PATHS = ("direct", "interior + edges", "general")
+BP_FAMILIES = (None, "wps2", "wps", "readlane")
+_BP_CLASS_FIELDS = ("tile", "halves", "n_pass", "n_groups", "lds_bytes", "n_sources", "max_stations")
+_BP_KERNEL_FIELDS = ("family", "wpb", "nsv", "b64", "ntv", "tpt", "nblk", "tile", "lds_bytes", "waves_per_cu", "gather_bytes")
+
+
+def bp_launch_info(moveouts, weights_sources, N, reduce="max", n_events=0):
+    """bpmf_bp_launch_info: the plan of these (K, S, P) moveouts and (K, S) source weights and the schedule of a run
+    of N samples on it under the current options (no device needed).  n_events = 0: bpmf_bp_run_dev; E >= 1: the
+    max-beams of a batch of E events (relocation).  Returns {"shape": ..., "schedule": ..., "plan_info": ...};
+    `plan_info` is what BeamformerGPU.plan_info() reports of the plan."""
+    import numpy as np
+    mv = np.ascontiguousarray(moveouts, dtype=np.int32)
+    ws = np.ascontiguousarray(weights_sources, dtype=np.float32)
+    if mv.ndim != 3 or ws.shape != mv.shape[:2]:
+        raise ValueError("moveouts must be (K, S, P) and weights_sources (K, S)")
+    K, S, P = mv.shape
+    out = (C.c_int64 * 78)()
+    check(lib().bpmf_bp_launch_info(mv.ctypes.data_as(_i), ws.ctypes.data_as(_f), K, S, P, int(N),
+                                    {"max": 0, "none": 1}[reduce], int(n_events), out), "bpmf_bp_launch_info")
+    v = [int(x) for x in out]
+    shape = dict(zip(("K", "S", "P", "tpt", "NT", "nsv", "ntv", "dual", "n_groups", "lds_bytes", "direct", "fast",
+                      "fast_shares_generic", "n_classes"), v[:14]))
+    for n in ("dual", "fast", "fast_shares_generic"):
+        shape[n] = bool(shape[n])
+    shape["direct"] = BP_DIRECT_REASONS[shape["direct"]]
+    shape["classes"] = [dict(zip(_BP_CLASS_FIELDS, v[14 + 7 * c:21 + 7 * c])) for c in range(shape["n_classes"])]
+    for cl in shape["classes"]:
+        cl["halves"] = bool(cl["halves"])
+    shape.update(tmin_all=v[35], tmax_all=v[36], id_offset=v[37])
+    kernel = dict(zip(_BP_KERNEL_FIELDS, v[39:50]))
+    kernel["family"] = BP_FAMILIES[kernel["family"]]
+    kernel["b64"] = bool(kernel["b64"])
+    sched = dict(path=BP_PATHS[v[38]], kernel=kernel)
+    sched.update(zip(("n_split", "n_split_edge", "rows", "lo_s", "hi_s", "o_prestack", "o_pbeam", "o_parg", "total"), v[50:59]))
+    info = dict(zip(("n_groups", "tile", "lds_bytes", "gather_bytes", "stations_max", "waves_per_cu", "n_classes"), v[59:66]))
+    for i, n in enumerate(("class_tile", "class_sources", "class_groups", "class_stations_max")):
+        info[n] = v[66 + 3 * i:69 + 3 * i]
+    return {"shape": shape, "schedule": sched, "plan_info": info}
 
 
 class options:

@@ -262,10 +262,6 @@ __global__ __launch_bounds__(BP_THREADS) void bp_beam_kernel(
 // and their fmas.  (Round 1 ruled scalar loads out here -- SMEM shares the lgkm counter with the
 // LDS gathers -- see the note above bp_beam_kernel; v_readlane broadcasting costs two more VALU
 // issues per term.)
-struct BpTermV {
-    int off_bytes;  // LDS byte offset of the term's window origin (+ moveout)
-    float beta;     // source weight of the term's station
-};
 
 template <int NTV>
 struct BpMetaV {
@@ -873,337 +869,8 @@ __global__ void bp_unpack_kernel(const unsigned long long* __restrict__ packed, 
 
 using namespace bpmf;
 
-// ----------------------------------------------------------------------- plan ---
+// ---------------------------------------------------------------- plan upload ---
 namespace {
-
-struct PlanHost {
-    std::vector<BpGroup> groups;
-    std::vector<BpChunk> chunks;
-    std::vector<BpSource> srcs;   // in processing order
-    std::vector<int> off;
-    std::vector<float> beta;
-    size_t lds_floats = 0;
-    int NT = 4;
-    int n_pass = 1;             // > 1: every group is n_pass consecutive entries of `groups` (LDS residencies)
-    int per = 0;                // n_pass > 1: weighted stations of a source per residency
-    int slots = 0;              // n_pass > 1: sources per wave of a group (6, or 9 when every weight is uniform)
-};
-
-// Processing order: recursive median bisection of the sources on the moveout column with
-// the largest spread (a kd-tree walk), so that consecutive sources have similar moveouts
-// on every station and a group's LDS windows stay short.
-void bisect_order(const int32_t* mv, size_t SP, std::vector<int>& idx, size_t lo, size_t hi,
-                  size_t leaf)
-{
-    if (hi - lo <= leaf) return;
-    size_t best_col = 0;
-    long long best_range = -1;
-    for (size_t c = 0; c < SP; ++c) {
-        int mn = mv[(size_t)idx[lo] * SP + c], mx = mn;
-        for (size_t i = lo + 1; i < hi; ++i) {
-            const int v = mv[(size_t)idx[i] * SP + c];
-            mn = std::min(mn, v);
-            mx = std::max(mx, v);
-        }
-        if ((long long)mx - mn > best_range) { best_range = (long long)mx - mn; best_col = c; }
-    }
-    if (best_range <= 0) return;
-    const size_t mid = lo + (hi - lo) / 2;
-    std::nth_element(idx.begin() + lo, idx.begin() + mid, idx.begin() + hi, [&](int a, int b) {
-        const int va = mv[(size_t)a * SP + best_col], vb = mv[(size_t)b * SP + best_col];
-        return va < vb || (va == vb && a < b);
-    });
-    bisect_order(mv, SP, idx, lo, mid, leaf);
-    bisect_order(mv, SP, idx, mid, hi, leaf);
-}
-
-// Extreme moveouts of one source for the strict bound test and the number of its used (station, phase)
-// terms: over the WEIGHTED stations (the build's convention, oracle/bpmf_oracle.c:bp_cpu), or -- option
-// bp.compat_range_all_stations -- over all stations of a source that has at least one weighted station.
-int source_tau_range(const int32_t* mv, const float* ws, size_t k, size_t S, size_t P, long long& lo, long long& hi)
-{
-    const bool all_stations = option(OPT_BP_COMPAT_RANGE_ALL_STATIONS) != 0;
-    int n = 0;
-    bool seen = false;
-    lo = hi = 0;
-    for (size_t s = 0; s < S; ++s) {
-        const bool used = ws[k * S + s] != 0.0f;
-        if (used) n += (int)P;
-        else if (!all_stations) continue;
-        for (size_t p = 0; p < P; ++p) {
-            const long long tau = mv[(k * S + s) * P + p];
-            if (!seen || tau < lo) lo = tau;
-            if (!seen || tau > hi) hi = tau;
-            seen = true;
-        }
-    }
-    if (n == 0) lo = hi = 0;
-    return n;
-}
-
-// Greedy grouping of consecutive sources (in processing order): a group is closed when the
-// next source would push the LDS need (zero slab + sum over used rows of tile + moveout
-// spread) past the soft budget.  Returns false if one source alone exceeds `hard_floats`.
-// dual: every window is staged twice, the second copy shifted by one sample, both at even
-// offsets; a term whose offset into the window is odd reads the shifted copy, so that ALL emitted
-// offsets are even (8-byte aligned pairs for the ds_read_b64 kernel).
-// `order_in`: the sources of this plan in processing order (all of them, or one station-count class).
-bool build_plan(const int32_t* mv, const float* ws, const std::vector<int>& order_in, size_t S, size_t P,
-                int tile, int chunk, size_t soft_floats, const size_t hard_floats, int max_group,
-                int32_t id_offset, bool dual, PlanHost& ph)
-{
-    // a window is staged in 16-byte lanes: its length is rounded up to a multiple of 4 floats
-    // (the extra samples are real data or zero fill, never addressed by a term)
-    auto row_len = [&](int spread) -> size_t { return ((size_t)tile + (size_t)spread + 3) & ~(size_t)3; };
-    auto row_cost = [&](int spread) -> size_t { return dual ? 2 * row_len(spread) : row_len(spread); };
-    const size_t SP = S * P;
-    std::vector<int> order = order_in;
-    const size_t K = order.size();
-    // the zero slab: one tile of the generic kernels, a fixed 512 floats in front of the
-    // descriptor slab of the dual plans (bp_fast.hip, any tile)
-    const size_t zero_slab = dual ? (size_t)BPF_ZERO_SLAB : (size_t)tile;
-
-    size_t max_terms = 1;
-    ph.srcs.resize(K);
-    auto src_of = [&](size_t k) {
-        long long lo = 0, hi = 0;
-        const int n = source_tau_range(mv, ws, k, S, P, lo, hi);
-        max_terms = std::max(max_terms, (size_t)n);
-        return BpSource{(int)((long long)k + id_offset), (int)lo, (int)hi,
-                        (n + chunk - 1) / chunk * chunk};
-    };
-    for (size_t q = 0; q < K; ++q) ph.srcs[q] = src_of((size_t)order[q]);
-    const int NT = (int)((max_terms + chunk - 1) / chunk * chunk);
-    ph.NT = NT;
-    // A source's own windows (terms x tile + the zero slab) must leave room for the moveout
-    // spread of a useful group.  When they do not even fit the soft budget with 16 samples of
-    // spread per row (dense station weights), use the whole LDS (one workgroup per CU) instead of
-    // degenerating to one source per group.  (Measured on cfg3 geometry, 10 / 15 / 20 used
-    // stations: 0.35 / 0.64 / 0.91 s.)
-    // dual plans (bp_fast.hip) keep 4 KB behind the zero slab for the next group's window descriptors
-    // (16 bytes per window; a group has at most 2 S P windows)
-    const size_t slab_extra = dual ? (size_t)4 * std::min<size_t>(BPF_DESC_MAX, (2 * S * P + 63) / 64 * 64) : 0;
-    const size_t base_need = zero_slab + slab_extra + max_terms * row_cost(0);
-    // More than 16 stations (P = 2: 32 terms): the packed kernel runs one 16-wave workgroup per CU.
-    if (base_need + max_terms * (row_cost(16) - row_cost(0)) > soft_floats || (P == 2 && max_terms > 32))
-        soft_floats = hard_floats;
-    ph.off.assign(K * (size_t)NT, 0);       // padded terms read the zero slab at offset 0
-    ph.beta.assign(K * (size_t)NT, 0.0f);
-
-    std::vector<int> gmin(SP), gmax(SP), base(SP);
-    std::vector<char> used(SP);
-    struct RowUpdate { size_t row; int lo, hi; };
-    std::vector<RowUpdate> upd;
-    upd.reserve(SP);
-    size_t first = 0;
-    while (first < K) {
-        std::fill(used.begin(), used.end(), 0);
-        size_t need = zero_slab + slab_extra, q = first;  // the zero slab (+ the descriptor slab)
-        for (; q < K && (int)(q - first) < max_group; ++q) {
-            const size_t k = (size_t)order[q];
-            size_t need2 = need;
-            upd.clear();
-            for (size_t s = 0; s < S; ++s) {
-                if (ws[k * S + s] == 0.0f) continue;
-                for (size_t p = 0; p < P; ++p) {
-                    const size_t r = s * P + p;
-                    const int tau = mv[(k * S + s) * P + p];
-                    int lo = tau, hi = tau;
-                    if (used[r]) {
-                        lo = std::min(lo, gmin[r]);
-                        hi = std::max(hi, gmax[r]);
-                        need2 += row_cost(hi - lo) - row_cost(gmax[r] - gmin[r]);
-                    } else {
-                        need2 += row_cost(0);
-                    }
-                    upd.push_back(RowUpdate{r, lo, hi});
-                }
-            }
-            const size_t limit = (q == first) ? hard_floats : soft_floats;
-            if (need2 > limit) {
-                if (q == first) return false;
-                break;
-            }
-            for (const RowUpdate& u : upd) {
-                used[u.row] = 1;
-                gmin[u.row] = u.lo;
-                gmax[u.row] = u.hi;
-            }
-            need = need2;
-        }
-        // close group [first, q): lay the windows out after the zero slab, cut them in chunks
-        BpGroup g{(int)first, (int)(q - first), (int)ph.chunks.size(), 0};
-        size_t o = zero_slab + slab_extra;
-        for (size_t r = 0; r < SP; ++r) {
-            base[r] = -1;
-            if (!used[r]) continue;
-            const int len = (int)row_len(gmax[r] - gmin[r]);
-            base[r] = (int)o;
-            for (int x0 = 0; x0 < len; x0 += BP_THREADS)
-                ph.chunks.push_back(BpChunk{(int)r, gmin[r] + x0, (int)o + x0,
-                                            std::min(BP_THREADS, len - x0)});
-            if (dual) {  // the copy shifted by one sample, right behind (both bases multiples of 4)
-                for (int x0 = 0; x0 < len; x0 += BP_THREADS)
-                    ph.chunks.push_back(BpChunk{(int)r, gmin[r] + 1 + x0, (int)o + len + x0,
-                                                std::min(BP_THREADS, len - x0)});
-            }
-            o += row_cost(gmax[r] - gmin[r]);
-        }
-        g.n_chunk = (int)ph.chunks.size() - g.first_chunk;
-        ph.lds_floats = std::max(ph.lds_floats, o);
-        if (dual) {  // ascending ids inside the group (see GLOCAL in bp_beam_wps2_kernel)
-            std::sort(order.begin() + first, order.begin() + q);
-            for (size_t qq = first; qq < q; ++qq) ph.srcs[qq] = src_of((size_t)order[qq]);
-        }
-        for (size_t qq = first; qq < q; ++qq) {
-            const size_t k = (size_t)order[qq];
-            size_t j = 0;
-            for (size_t s = 0; s < S; ++s) {
-                if (ws[k * S + s] == 0.0f) continue;
-                for (size_t p = 0; p < P; ++p, ++j) {
-                    const size_t r = s * P + p;
-                    const int rel = mv[(k * S + s) * P + p] - gmin[r];
-                    if (dual && (rel & 1))
-                        ph.off[qq * NT + j] = base[r] + (int)row_len(gmax[r] - gmin[r]) + rel - 1;
-                    else
-                        ph.off[qq * NT + j] = base[r] + rel;
-                    ph.beta[qq * NT + j] = ws[k * S + s];
-                }
-            }
-        }
-        ph.groups.push_back(g);
-        first = q;
-    }
-    return true;
-}
-
-// Multi-residency plan (bp_fast.hip, HALVES): dual windows at `tile`, groups of at most `max_group`
-// sources, the weighted stations of every source dealt to residencies of `per` stations each (in
-// station order: the first `per`, the next `per`, ...); a group is closed when any residency's windows
-// would exceed `hard_floats` of LDS.  Every group becomes ph.n_pass consecutive entries of ph.groups
-// (same sources, the chunks of one residency each); ph.off holds the offsets of a source's terms inside
-// the residency they belong to.
-bool build_plan_halves(const int32_t* mv, const float* ws, const std::vector<int>& order_in, size_t S, size_t P,
-                       int tile, int chunk, const size_t hard_floats, int max_group, int32_t id_offset,
-                       int per, int n_pass, int slots, PlanHost& ph)
-{
-    auto row_len = [&](int spread) -> size_t { return ((size_t)tile + (size_t)spread + 3) & ~(size_t)3; };
-    auto row_cost = [&](int spread) -> size_t { return 2 * row_len(spread); };
-    const size_t SP = S * P;
-    std::vector<int> order = order_in;
-    const size_t K = order.size();
-    const size_t zero_slab = (size_t)BPF_ZERO_SLAB;
-    const size_t slab_extra = (size_t)4 * std::min<size_t>(BPF_DESC_MAX, (2 * S * P + 63) / 64 * 64);
-    size_t max_terms = 1;
-    ph = PlanHost();
-    ph.n_pass = n_pass;
-    ph.per = per;
-    ph.slots = slots;
-    ph.srcs.resize(K);
-    auto src_of = [&](size_t k) {
-        long long lo = 0, hi = 0;
-        const int n = source_tau_range(mv, ws, k, S, P, lo, hi);
-        max_terms = std::max(max_terms, (size_t)n);
-        return BpSource{(int)((long long)k + id_offset), (int)lo, (int)hi, (n + chunk - 1) / chunk * chunk};
-    };
-    for (size_t q = 0; q < K; ++q) ph.srcs[q] = src_of((size_t)order[q]);
-    if (max_terms > (size_t)per * n_pass * P) return false;
-    const int NT = (int)((max_terms + chunk - 1) / chunk * chunk);
-    ph.NT = NT;
-    ph.off.assign(K * (size_t)NT, 0);
-    ph.beta.assign(K * (size_t)NT, 0.0f);
-    std::vector<std::vector<int>> gmin(n_pass, std::vector<int>(SP)), gmax(n_pass, std::vector<int>(SP)),
-        base(n_pass, std::vector<int>(SP));
-    std::vector<std::vector<char>> used(n_pass, std::vector<char>(SP));
-    struct RowUpdate { int h; size_t row; int lo, hi; };
-    std::vector<RowUpdate> upd;
-    std::vector<size_t> need(n_pass), need2(n_pass);
-    size_t first = 0;
-    while (first < K) {
-        for (int h = 0; h < n_pass; ++h) {
-            std::fill(used[h].begin(), used[h].end(), 0);
-            need[h] = zero_slab + slab_extra;
-        }
-        size_t q = first;
-        for (; q < K && (int)(q - first) < max_group; ++q) {
-            const size_t k = (size_t)order[q];
-            need2 = need;
-            upd.clear();
-            int ord = 0;
-            for (size_t s = 0; s < S; ++s) {
-                if (ws[k * S + s] == 0.0f) continue;
-                const int h = ord / per;
-                ++ord;
-                for (size_t p = 0; p < P; ++p) {
-                    const size_t r = s * P + p;
-                    const int tau = mv[(k * S + s) * P + p];
-                    int lo = tau, hi = tau;
-                    if (used[h][r]) {
-                        lo = std::min(lo, gmin[h][r]);
-                        hi = std::max(hi, gmax[h][r]);
-                        need2[h] += row_cost(hi - lo) - row_cost(gmax[h][r] - gmin[h][r]);
-                    } else {
-                        need2[h] += row_cost(0);
-                    }
-                    upd.push_back(RowUpdate{h, r, lo, hi});
-                    // (a row may appear in several residencies of a GROUP -- different sources count a
-                    // station differently -- but only once per residency)
-                }
-            }
-            bool fits = true;
-            for (int h = 0; h < n_pass; ++h) fits = fits && need2[h] <= hard_floats;
-            if (!fits) {
-                if (q == first) return false;
-                break;
-            }
-            for (const RowUpdate& u : upd) {
-                used[u.h][u.row] = 1;
-                gmin[u.h][u.row] = u.lo;
-                gmax[u.h][u.row] = u.hi;
-            }
-            need = need2;
-        }
-        std::sort(order.begin() + first, order.begin() + q);          // ascending ids inside the group
-        for (size_t qq = first; qq < q; ++qq) ph.srcs[qq] = src_of((size_t)order[qq]);
-        for (int h = 0; h < n_pass; ++h) {
-            BpGroup g{(int)first, (int)(q - first), (int)ph.chunks.size(), 0};
-            size_t o = zero_slab + slab_extra;
-            for (size_t r = 0; r < SP; ++r) {
-                base[h][r] = -1;
-                if (!used[h][r]) continue;
-                const int len = (int)row_len(gmax[h][r] - gmin[h][r]);
-                base[h][r] = (int)o;
-                for (int x0 = 0; x0 < len; x0 += BP_THREADS)
-                    ph.chunks.push_back(BpChunk{(int)r, gmin[h][r] + x0, (int)o + x0, std::min(BP_THREADS, len - x0)});
-                for (int x0 = 0; x0 < len; x0 += BP_THREADS)
-                    ph.chunks.push_back(BpChunk{(int)r, gmin[h][r] + 1 + x0, (int)o + len + x0, std::min(BP_THREADS, len - x0)});
-                o += row_cost(gmax[h][r] - gmin[h][r]);
-            }
-            g.n_chunk = (int)ph.chunks.size() - g.first_chunk;
-            ph.lds_floats = std::max(ph.lds_floats, o);
-            ph.groups.push_back(g);
-        }
-        for (size_t qq = first; qq < q; ++qq) {
-            const size_t k = (size_t)order[qq];
-            size_t j = 0;
-            int ord = 0;
-            for (size_t s = 0; s < S; ++s) {
-                if (ws[k * S + s] == 0.0f) continue;
-                const int h = ord / per;
-                ++ord;
-                for (size_t p = 0; p < P; ++p, ++j) {
-                    const size_t r = s * P + p;
-                    const int rel = mv[(k * S + s) * P + p] - gmin[h][r];
-                    ph.off[qq * NT + j] = (rel & 1) ? base[h][r] + (int)row_len(gmax[h][r] - gmin[h][r]) + rel - 1
-                                                    : base[h][r] + rel;
-                    ph.beta[qq * NT + j] = ws[k * S + s];
-                }
-            }
-        }
-        first = q;
-    }
-    return true;
-}
 
 // The tables of a plan travel through ONE pinned scratch buffer of the process (grow-only, under a mutex), not
 // straight from the std::vectors that hold them: a pageable source makes the runtime page-lock the vector's pages for
@@ -1249,244 +916,6 @@ int upload(const std::vector<Tv>& v, Tv** d)
     return 0;
 }
 
-}  // namespace
-
-namespace {
-
-// ---- interior-tile fast path: host-side tables of one station-count class (bp_fast.hip) ----
-struct FastHost {
-    std::vector<BpFastGroup> fg;
-    std::vector<BpRun> fr;
-    std::vector<BpWindow> fw;
-    std::vector<int> rec;
-    bool uniform = true;
-    int rec_dw = 0, max_sta = 0;
-    size_t n_sources = 0;
-};
-
-// A source of `n` (even-padded) stations as `nparts` records of `tp` stations for the kernel of
-// this tile: the smallest padded total + 2 per part, then the fewest parts.  Part sizes the kernels instantiate:
-// tile 512: 4..16 even, one part; tile 256: 6..16 even; tile 128: 8, 12, 16, 20, 24.
-bool fast_parts(int n, int tile, int& tp, int& nparts)
-{
-    static const int t512[] = {4, 6, 8, 10, 12, 14, 16}, t256[] = {6, 8, 10, 12, 14, 16}, t128[] = {8, 12, 16, 20, 24};
-    const int* opts = tile == 512 ? t512 : (tile == 256 ? t256 : t128);
-    const int n_opts = tile == 512 ? 7 : (tile == 256 ? 6 : 5);
-    // A part boundary costs about as much as two stations at tiles 512 / 256 (header, refill
-    // pipeline restart).  At tile 128 a unit is a whole quad of the record and the distance between
-    // the request of a quad and its first use is (quads per part - 3) units: short parts stall on
-    // the record loads (5 parts of 8 stations: 0.26 of the gather rate at cfg5's share) -- prefer
-    // the longest parts.
-    const int part_cost = tile == 128 ? 8 : 2;
-    int best_total = 1 << 30;
-    tp = 0;
-    nparts = 0;
-    for (int i = 0; i < n_opts; ++i) {
-        const int k = std::max(1, (n + opts[i] - 1) / opts[i]);
-        if (tile == 512 && k > 1) continue;
-        if (k > 16) continue;
-        const int total = k * opts[i] + part_cost * k;
-        if (total < best_total || (total == best_total && k < nparts)) {
-            best_total = total;
-            tp = opts[i];
-            nparts = k;
-        }
-    }
-    return tp != 0;
-}
-
-// Relative time per time sample of the interior kernel on this plan: every group pays one staging
-// round (two barriers, the window copies: ~6000 cycles measured at cfg3), every source its gathers
-// (64 lanes x 8 bytes per ds_read_b64 at ~0.7 x 256 B/clk/CU, a little less on the small tiles,
-// whose units carry more address arithmetic per byte), all of it amortised over `tile` samples.
-double plan_cost(const PlanHost& ph, int tile)
-{
-    const double eff = tile == 512 ? 0.70 : (tile == 256 ? 0.66 : 0.40);   // (tile 128: measured 0.35 at 40 stations, VALU-bound)
-    double cycles = 0.0;
-    for (const BpGroup& g : ph.groups) {
-        double terms = 0.0;
-        for (int q = g.first_src; q < g.first_src + g.n_src; ++q) terms += ph.srcs[q].nterm;
-        // an entry of a multi-residency plan is one residency: `per` stations of every source (padded
-        // records), and a short group is padded to 16 x BPF_HALVES_SLOTS sources; ~8800 cycles between the
-        // gathers of two entries were measured there (cfg5's share, 40 stations)
-        if (ph.n_pass > 1) terms = 2.0 * ph.per * 16 * ph.slots;
-        cycles += (ph.n_pass > 1 ? 8800.0 : 6000.0) + terms * (double)tile * 4.0 / (256.0 * eff);   // 4 gathered bytes per term and sample
-    }
-    return cycles / tile;
-}
-
-bool build_fast_host(const PlanHost& ph, int tile, bool allow_uniform, FastHost& fh)
-{
-    const int NT = ph.NT;
-    fh = FastHost();
-    fh.uniform = allow_uniform;
-    int tp_max = 4;
-    const size_t K = ph.srcs.size();
-    std::vector<int> tp_of(K, 0), np_of(K, 0);
-    for (size_t q = 0; q < K; ++q) {
-        const BpSource& sr = ph.srcs[q];
-        if (sr.nterm <= 0) continue;
-        ++fh.n_sources;
-        int tp, np;
-        if (!fast_parts(sr.nterm / 2, tile, tp, np)) return false;
-        tp_of[q] = tp;
-        np_of[q] = np;
-        tp_max = std::max(tp_max, tp);
-        fh.max_sta = std::max(fh.max_sta, sr.nterm / 2);
-        float w0 = 0.0f;
-        for (int j = 0; j < NT; j += 2) {
-            const float b = ph.beta[q * NT + j];
-            if (b == 0.0f) continue;
-            if (w0 == 0.0f) w0 = b;
-            else if (b != w0) fh.uniform = false;
-        }
-    }
-    if (fh.n_sources == 0) return false;
-    const int rec_dw = (2 + 2 * tp_max + 3) / 4 * 4;
-    fh.rec_dw = rec_dw;
-    std::vector<int> members;
-    for (const BpGroup& g : ph.groups) {
-        // the group's staging chunks (pieces of <= 256 floats), merged back into whole windows
-        BpFastGroup f{(int)fh.fr.size(), 0, (int)fh.fw.size(), 0};
-        for (int c = g.first_chunk; c < g.first_chunk + g.n_chunk; ++c) {
-            const BpChunk& ck = ph.chunks[c];
-            if ((int)fh.fw.size() > f.first_win && fh.fw.back().row == ck.row &&
-                fh.fw.back().gofs + fh.fw.back().len == ck.gofs && fh.fw.back().dst + fh.fw.back().len == ck.dst)
-                fh.fw.back().len += ck.n;
-            else
-                fh.fw.push_back(BpWindow{ck.row, ck.gofs, ck.dst, ck.n});
-        }
-        f.n_win = (int)fh.fw.size() - f.first_win;
-        if (f.n_win > BPF_DESC_MAX) return false;       // > 256 windows in a group: general kernel
-        // runs of equal (tp, nparts), ascending id inside a run (the plan lists a group's sources by
-        // ascending id); at most 16 x 16 combinations, most groups have one or two
-        for (int np = 1; np <= 16; ++np) {
-            for (int tp = 4; tp <= 24; tp += 2) {
-                members.clear();
-                for (int q = g.first_src; q < g.first_src + g.n_src; ++q)
-                    if (tp_of[q] == tp && np_of[q] == np) members.push_back(q);
-                if (members.empty()) continue;
-                const size_t first_rec = fh.rec.size() / rec_dw;
-                const size_t rounds = (members.size() + 15) / 16;
-                fh.rec.resize(fh.rec.size() + rounds * np * 16 * rec_dw, 0);
-                fh.fr.push_back(BpRun{(int)first_rec, (int)members.size(), tp, np});
-                ++f.n_run;
-                for (size_t m = 0; m < members.size(); ++m) {
-                    const int q = members[m];
-                    float w0 = 0.0f;
-                    for (int j = 0; j < NT && w0 == 0.0f; j += 2) w0 = ph.beta[(size_t)q * NT + j];
-                    for (int part = 0; part < np; ++part) {
-                        const size_t r0 = (first_rec + ((m / 16) * np + part) * 16 + m % 16) * rec_dw;
-                        fh.rec[r0] = ph.srcs[q].id;
-                        fh.rec[r0 + 1] = fh.uniform ? __builtin_bit_cast(int, w0) : 0;
-                        for (int i = 0; i < tp; ++i) {
-                            const int st = part * tp + i;
-                            const bool real = 2 * st + 1 < NT;  // beyond the term table: the zero slab, weight 0
-                            const int oP = real ? ph.off[(size_t)q * NT + 2 * st] : 0;
-                            const int oS = real ? ph.off[(size_t)q * NT + 2 * st + 1] : 0;
-                            if (fh.uniform) {                   // LDS byte addresses of the two windows
-                                fh.rec[r0 + 2 + 2 * i] = oP * 4;
-                                fh.rec[r0 + 3 + 2 * i] = oS * 4;
-                            } else {                            // {offs_P | offs_S << 16, weight}
-                                fh.rec[r0 + 2 + 2 * i] = (int)((unsigned)oP | ((unsigned)oS << 16));
-                                fh.rec[r0 + 3 + 2 * i] = real ? __builtin_bit_cast(int, ph.beta[(size_t)q * NT + 2 * st]) : 0;
-                            }
-                        }
-                    }
-                }
-            }
-        }
-        fh.fg.push_back(f);
-    }
-    fh.rec.resize(fh.rec.size() + (size_t)17 * rec_dw, 0);        // one round of records (+ 1: whole s_load_dwordx8): the prefetch past the last part
-    fh.fw.resize(fh.fw.size() + BPF_DESC_MAX, BpWindow{0, 0, 0, 0});   // the descriptor prefetch past the last group
-    return true;
-}
-
-// Tables of a multi-residency class (build_plan_halves): per group ph.n_pass BpFastGroup entries, each
-// with ONE run that lists all the group's sources (ascending id: wave w owns sources w, w + 16, ... in
-// every residency -- the slots of the kernel's `carry` registers) as exactly two records of ph.per / 2
-// stations.
-bool build_fast_host_halves(const PlanHost& ph, FastHost& fh, bool allow_uniform)
-{
-    const int NT = ph.NT;
-    fh = FastHost();
-    fh.uniform = allow_uniform;
-    const size_t K = ph.srcs.size();
-    for (size_t q = 0; q < K; ++q) {
-        const BpSource& sr = ph.srcs[q];
-        if (sr.nterm <= 0) return false;                  // (sources without stations are not in this class)
-        ++fh.n_sources;
-        fh.max_sta = std::max(fh.max_sta, sr.nterm / 2);
-        float w0 = 0.0f;
-        for (int j = 0; j < NT; j += 2) {
-            const float b = ph.beta[q * NT + j];
-            if (b == 0.0f) continue;
-            if (w0 == 0.0f) w0 = b;
-            else if (b != w0) fh.uniform = false;
-        }
-    }
-    const int tp = ph.per / 2, np = 2, WPB = 16, full = WPB * ph.slots;
-    if ((tp != 6 && tp != 8 && tp != 10) || fh.n_sources == 0) return false;
-    const int rec_dw = (2 + 2 * tp + 3) / 4 * 4;
-    fh.rec_dw = rec_dw;
-    for (size_t gi = 0; gi < ph.groups.size(); ++gi) {
-        const BpGroup& g = ph.groups[gi];
-        const int h = (int)(gi % (size_t)ph.n_pass);
-        if (g.n_src > full) return false;
-        const int flags = (h > 0 ? BPF_GROUP_LOAD : 0) | (h + 1 < ph.n_pass ? BPF_GROUP_STORE : 0);
-        BpFastGroup f{(int)fh.fr.size(), 1 | flags, (int)fh.fw.size(), 0};
-        for (int c = g.first_chunk; c < g.first_chunk + g.n_chunk; ++c) {
-            const BpChunk& ck = ph.chunks[c];
-            if ((int)fh.fw.size() > f.first_win && fh.fw.back().row == ck.row &&
-                fh.fw.back().gofs + fh.fw.back().len == ck.gofs && fh.fw.back().dst + fh.fw.back().len == ck.dst)
-                fh.fw.back().len += ck.n;
-            else
-                fh.fw.push_back(BpWindow{ck.row, ck.gofs, ck.dst, ck.n});
-        }
-        f.n_win = (int)fh.fw.size() - f.first_win;
-        if (f.n_win > BPF_DESC_MAX) return false;
-        const size_t first_rec = fh.rec.size() / rec_dw;
-        // every wave walks exactly ph.slots sources (the kernel's slots are straight-line code):
-        // a short group is padded with records of weight 0 at LDS offset 0 and id -1 (never a maximum)
-        const size_t n = (size_t)g.n_src, rounds = (size_t)ph.slots;
-        fh.rec.resize(fh.rec.size() + rounds * np * WPB * rec_dw, 0);
-        fh.fr.push_back(BpRun{(int)first_rec, full, tp, np});
-        for (size_t m = n; m < (size_t)full; ++m)
-            for (int part = 0; part < np; ++part) fh.rec[(first_rec + ((m / WPB) * np + part) * WPB + m % WPB) * rec_dw] = -1;
-        for (size_t m = 0; m < n; ++m) {
-            const int q = g.first_src + (int)m;
-            const int st_lo = h * ph.per, st_hi = std::min((h + 1) * ph.per, ph.srcs[q].nterm / 2);
-            float w0 = 0.0f;
-            for (int j = 0; j < NT && w0 == 0.0f; j += 2) w0 = ph.beta[(size_t)q * NT + j];
-            for (int part = 0; part < np; ++part) {
-                const size_t r0 = (first_rec + ((m / WPB) * np + part) * WPB + m % WPB) * rec_dw;
-                fh.rec[r0] = ph.srcs[q].id;
-                fh.rec[r0 + 1] = fh.uniform ? __builtin_bit_cast(int, w0) : 0;
-                for (int i = 0; i < tp; ++i) {
-                    const int st = st_lo + part * tp + i;
-                    const bool real = st < st_hi && 2 * st + 1 < NT;    // beyond this residency: the zero slab, weight 0
-                    const int oP = real ? ph.off[(size_t)q * NT + 2 * st] : 0;
-                    const int oS = real ? ph.off[(size_t)q * NT + 2 * st + 1] : 0;
-                    if (fh.uniform) {
-                        fh.rec[r0 + 2 + 2 * i] = oP * 4;
-                        fh.rec[r0 + 3 + 2 * i] = oS * 4;
-                    } else {
-                        fh.rec[r0 + 2 + 2 * i] = (int)((unsigned)oP | ((unsigned)oS << 16));
-                        fh.rec[r0 + 3 + 2 * i] = real ? __builtin_bit_cast(int, ph.beta[(size_t)q * NT + 2 * st]) : 0;
-                    }
-                }
-            }
-        }
-        fh.fg.push_back(f);
-    }
-    // one round of records behind the last one (the look-ahead past a wave's last part), and one more
-    // record: the kernel fetches a record in whole s_load_dwordx8 (24 dwords where rec_dw is 20)
-    fh.rec.resize(fh.rec.size() + (size_t)17 * rec_dw, 0);
-    fh.fw.resize(fh.fw.size() + BPF_DESC_MAX, BpWindow{0, 0, 0, 0});
-    return true;
-}
-
 void free_fast_class(BpFastClass& fc)
 {
     (void)hipFree(fc.d_groups);
@@ -1496,12 +925,69 @@ void free_fast_class(BpFastClass& fc)
     fc = BpFastClass();
 }
 
-struct ClassHost {
-    PlanHost ph;
-    FastHost fh;
-    int tile = 0;
-    bool halves = false;
-};
+// The device side of a plan: binds the device, copies the host tables as they are, takes the device's side
+// stream and creates the fork / join events.
+int bp_plan_upload(const BpPlanHost& h, int device, bpmf_bp_plan** plan_out)
+{
+    BPMF_BIND_DEVICE(device);
+    bpmf_bp_plan* pl = new bpmf_bp_plan();
+    pl->device = device;
+    pl->shape = h.shape;
+    const BpPlanShape& sh = h.shape;
+    auto tables = [&]() -> int {
+        int rc = 0;
+        if (sh.direct) {
+            (void)((rc = upload(h.dhdr, &pl->d_dhdr)) || (rc = upload(h.dfirst, &pl->d_dfirst)) ||
+                   (rc = upload(h.dterms, &pl->d_dterms)));
+            return rc;
+        }
+        if (sh.nsv && ((rc = upload(h.recs, &pl->d_recs)) || (rc = upload(h.hdr2, &pl->d_hdr2)))) return rc;
+        if (sh.ntv && (rc = upload(h.termsv, &pl->d_termsv))) return rc;
+        if (sh.fast) {
+            // interior-tile classes
+            for (int c = 0; c < sh.n_classes; ++c) {
+                const FastHost& fh = h.classes[c].fh;
+                const BpClassShape& cs = sh.cls[c];
+                BpFastClass& fc = pl->cls[c];
+                fc.tile = cs.tile;
+                fc.halves = cs.halves;
+                fc.n_pass = cs.n_pass;
+                fc.uniform = fh.uniform;
+                fc.rec_dw = fh.rec_dw;
+                fc.n_groups = cs.n_groups;
+                fc.lds_bytes = cs.lds_bytes;
+                fc.n_sources = cs.n_sources;
+                fc.max_stations = cs.max_stations;
+                fc.desc_waves = (int)std::min<size_t>(BPF_DESC_MAX, (2 * sh.S * sh.P + 63) / 64 * 64) / 64;
+                if ((rc = upload(fh.fg, &fc.d_groups)) || (rc = upload(fh.fr, &fc.d_runs)) ||
+                    (rc = upload(fh.fw, &fc.d_wins)) || (rc = upload(fh.rec, &fc.d_recs)))
+                    return rc;
+            }
+            // the side stream is the device's (context.h: created once per device, never destroyed);
+            // the fork / join events are the plan's own
+            pl->side_stream = device_side_stream(device);
+            if (!pl->side_stream) return -2;
+            hipError_t e2 = hipEventCreateWithFlags(&pl->ev_fork, hipEventDisableTiming);
+            hipError_t e3 = hipEventCreateWithFlags(&pl->ev_join, hipEventDisableTiming);
+            if (e2 != hipSuccess || e3 != hipSuccess) {
+                set_error("bpmf_bp_plan_create: fork / join events: %s",
+                          hipGetErrorString(e2 != hipSuccess ? e2 : e3));
+                return -2;
+            }
+        }
+        const PlanHost& ph = h.general();
+        (void)((rc = upload(ph.groups, &pl->d_groups)) || (rc = upload(ph.chunks, &pl->d_chunks)) ||
+               (rc = upload(ph.srcs, &pl->d_srcs)) || (rc = upload(ph.off, &pl->d_off)) ||
+               (rc = upload(ph.beta, &pl->d_beta)));
+        return rc;
+    };
+    if (const int rc = tables()) {
+        bpmf_bp_plan_destroy(pl);
+        return rc;
+    }
+    *plan_out = pl;
+    return 0;
+}
 
 }  // namespace
 
@@ -1509,296 +995,13 @@ extern "C" int bpmf_bp_plan_create(const int32_t* moveouts, const float* w_sourc
                                    size_t S, size_t P, int device, int32_t source_id_offset,
                                    bpmf_bp_plan** plan_out)
 {
-    if (!moveouts || !w_sources || !plan_out || K == 0 || S == 0 || P == 0) {
-        set_error("bpmf_bp_plan_create: bad argument");
+    const char* why = plan_out ? bp_plan_refusal(moveouts, w_sources, K, S, P) : "bad argument";
+    if (why) {
+        set_error("bpmf_bp_plan_create: %s", why);
         return -1;
     }
-    if (K > 0x7fffffffull || K * S * P > 0x7fffffffffull) {
-        set_error("bpmf_bp_plan_create: grid too large");
-        return -1;
-    }
-    // options (defaults chosen on MI355X)
-    const size_t soft_kb = (size_t)std::max(8, (int)option(OPT_BP_LDS_KB));
-    const int max_group = std::max(1, (int)option(OPT_BP_MAX_GROUP));
-    const int tpt_first = (int)option(OPT_BP_TPT);
-    const int chunk = 4;  // terms gathered side by side by the generic kernel (8 measured equal)
-    const bool reorder = option(OPT_BP_REORDER) != 0;
-    const bool verbose = option(OPT_BP_VERBOSE) != 0;
-    const size_t hard = BP_LDS_MAX / sizeof(float);
-    const size_t soft = std::min(hard, soft_kb * 1024 / sizeof(float));
-    const size_t SP = S * P;
-
-    // weighted stations per source, extreme used moveouts of the grid
-    std::vector<int> nsta(K, 0);
-    int max_sta = 0, tmin_all = 0, tmax_all = 0;
-    bool any_src = false;
-    for (size_t k = 0; k < K; ++k) {
-        long long lo = 0, hi = 0;
-        const int n = source_tau_range(moveouts, w_sources, k, S, P, lo, hi) / (int)P;
-        if (n > 0) {
-            if (!any_src || lo < tmin_all) tmin_all = (int)lo;
-            if (!any_src || hi > tmax_all) tmax_all = (int)hi;
-            any_src = true;
-        }
-        nsta[k] = n;
-        max_sta = std::max(max_sta, n);
-    }
-    // option bp.compat_strict_upper_only: "strict" tests t + tau_max < N only and a used term in front of
-    // sample 0 contributes nothing.  With every used moveout >= 0 (BPMF's tables: moveouts relative to the
-    // first arrival, template_search.py:212-214) that IS the default; a table with a negative used moveout
-    // takes the global-memory kernel of bp_direct.hip, the one that tests every term.
-    const bool upper_only = option(OPT_BP_COMPAT_STRICT_UPPER_ONLY) != 0;
-    const bool upper_only_direct = upper_only && any_src && tmin_all < 0;
-    // processing order of the whole grid (kd-tree walk); a class keeps its members in this order
-    std::vector<int> order(K);
-    for (size_t k = 0; k < K; ++k) order[k] = (int)k;
-    if (reorder) bisect_order(moveouts, SP, order, 0, K, 16);
-
-    // ---- Two-phase grids: the ds_read_b64 kernel on dual windows (bp_fast.hip).  The sources are
-    // sorted into classes by their number of weighted stations -- <= 16, 17..32, 33..64 -- and
-    // every class gets the largest tile (512 / 256 / 128 samples) at which the dual windows of its
-    // groups fit the LDS with the lowest modelled cost; one 17-station source no longer moves a
-    // whole grid off the fast path, and dense 20- or 40-station weights run it on the small tiles.
-    std::vector<ClassHost> classes;
-    const bool want_dual = P == 2 && option(OPT_BP_DUAL) && tpt_first == 2;
-    if (want_dual && any_src && max_sta <= 64) {
-        static const int bound[4] = {0, 16, 32, 64};
-        static const int cand[3][3] = {{512, 256, 128}, {256, 128, 0}, {128, 0, 0}};
-        bool ok = true;
-        std::vector<int> members;
-        for (int c = 0; c < 3 && ok; ++c) {
-            members.clear();
-            for (size_t q = 0; q < K; ++q) {
-                const int n = nsta[order[q]];
-                // sources without any station ride along with the first class when the whole grid is
-                // one class (they are skipped by the kernels; the shared plan must list every source)
-                if ((n > bound[c] && n <= bound[c + 1]) || (c == 0 && n == 0 && max_sta <= 16))
-                    members.push_back(order[q]);
-            }
-            if (members.empty()) continue;
-            ClassHost best;
-            double best_cost = 0.0;
-            const int forced_tile = (int)option(OPT_BP_FAST_TILE);
-            for (int i = 0; i < 3 && cand[c][i]; ++i) {
-                if (forced_tile && cand[c][i] != forced_tile) continue;
-                ClassHost ch;
-                ch.tile = cand[c][i];
-                if (!build_plan(moveouts, w_sources, members, S, P, ch.tile, chunk, hard, hard, max_group,
-                                source_id_offset, true, ch.ph))
-                    continue;
-                const double cost = plan_cost(ch.ph, ch.tile);
-                if (verbose)
-                    fprintf(stderr, "[bpmf] bp class %d (%zu sources, %d..%d stations) tile %d: %zu groups, cost %.1f\n",
-                            c, members.size(), bound[c] + 1, bound[c + 1], ch.tile, ch.ph.groups.size(), cost);
-                if (!best.tile || cost < best_cost) {
-                    best = std::move(ch);
-                    best_cost = cost;
-                }
-                // groups of hundreds of sources: a smaller tile cannot win
-                if ((double)members.size() / (double)best.ph.groups.size() >= 256.0 && best.tile == cand[c][i]) break;
-            }
-            // 33-64 stations: two LDS residencies per group at tile 256 (the station halves of every
-            // source, partial beams carried in registers) against one at tile 128
-            if (c == 2 && (!forced_tile || forced_tile == 256) && option(OPT_BP_HALVES) != 0) {
-                ClassHost ch;
-                ch.tile = 256;
-                ch.halves = true;
-                // 2-4 residencies of at most 20 stations, every source as two records of 6 / 8 / 10 stations in
-                // each of them
-                int cmax = 0;
-                for (int m : members) cmax = std::max(cmax, nsta[m]);
-                const int n_pass = std::max(2, (cmax + 19) / 20);
-                const int tp_h = std::max(6, (((cmax + n_pass - 1) / n_pass + 1) / 2 + 1) / 2 * 2), per = 2 * tp_h;
-                const int slots = BPF_HALVES_SLOTS;
-                if (tp_h <= 10 &&
-                    build_plan_halves(moveouts, w_sources, members, S, P, 256, chunk, hard,
-                                      std::min(max_group, 16 * slots), source_id_offset, per, n_pass, slots, ch.ph) &&
-                    build_fast_host_halves(ch.ph, ch.fh, option(OPT_BP_FAST_UNIFORM) != 0)) {
-                    const double cost = plan_cost(ch.ph, 256);
-                    if (verbose)
-                        fprintf(stderr, "[bpmf] bp class %d, %d residencies of %d stations at tile 256: %zu entries, cost %.1f\n",
-                                c, n_pass, per, ch.ph.groups.size(), cost);
-                    if (!best.tile || cost < best_cost || forced_tile == 256) {
-                        best = std::move(ch);
-                        best_cost = cost;
-                    }
-                }
-            }
-            if (!best.tile || (!best.halves && !build_fast_host(best.ph, best.tile, option(OPT_BP_FAST_UNIFORM) != 0, best.fh))) {
-                ok = false;
-                break;
-            }
-            classes.push_back(std::move(best));
-        }
-        if (!ok) classes.clear();
-    }
-    // A single class at tile 512 that lists every source doubles as the plan of the general kernels
-    // (their 8-byte-gather flavour): edge tiles and reduce="none" then gather 8 bytes too, and the
-    // grid is planned once.  Otherwise the general kernels get their own single-window plan.
-    const bool share = classes.size() == 1 && classes[0].tile == 512 && classes[0].ph.srcs.size() == K;
-    const bool use_fast = !classes.empty() && option(OPT_BP_FAST) != 0;
-    if (!share && !use_fast) classes.clear();
-
-    PlanHost ph_own;
-    int tpt = 0;
-    bool dual = false;
-    if (share) {
-        tpt = 2;
-        dual = true;
-    } else {
-        for (int cnd = tpt_first; cnd >= 1 && !tpt; --cnd) {   // tile 256 x bp.tpt, then 256
-            ph_own = PlanHost();
-            if (build_plan(moveouts, w_sources, order, S, P, BP_THREADS * cnd, chunk, soft, hard,
-                           max_group, source_id_offset, false, ph_own))
-                tpt = cnd;
-        }
-    }
-    PlanHost& ph = share ? classes[0].ph : ph_own;
-    BPMF_BIND_DEVICE(device);
-    bpmf_bp_plan* pl = new bpmf_bp_plan();
-    pl->device = device;
-    pl->K = K; pl->S = S; pl->P = P;
-    if (!tpt || ph.NT > 256 || option(OPT_BP_DIRECT) != 0 || upper_only_direct) {
-        // No LDS plan: one source's station-phase windows do not fit at the smallest tile, or a source has
-        // more than 256 (station, phase) terms (or option bp.direct asks for it: the tests).  The grid runs
-        // bp_direct.hip on compact term lists in the oracle's order.
-        std::vector<int4> hdr(K);
-        std::vector<long long> first(K + 1, 0);
-        std::vector<int4> terms;
-        for (size_t k = 0; k < K; ++k) {
-            long long lo = 0, hi = 0;
-            const int any = source_tau_range(moveouts, w_sources, k, S, P, lo, hi) > 0 ? 1 : 0;
-            first[k] = (long long)terms.size();
-            for (size_t s = 0; s < S; ++s) {
-                const float b = w_sources[k * S + s];
-                if (b == 0.0f) continue;
-                for (size_t p = 0; p < P; ++p)
-                    terms.push_back(make_int4((int)(s * P + p), moveouts[(k * S + s) * P + p], __builtin_bit_cast(int, b), 0));
-            }
-            // (strict-upper-only: the lower test always passes; the kernel drops a term in front of sample 0)
-            hdr[k] = make_int4(any, upper_only ? 0 : (int)lo, (int)hi, 0);
-        }
-        first[K] = (long long)terms.size();
-        if (terms.empty()) terms.push_back(make_int4(0, 0, 0, 0));
-        pl->direct = true;
-        pl->tpt = 4;
-        pl->NT = (int)std::min<size_t>(SP, 0x7fffffff);
-        pl->n_groups = 0;
-        pl->id_offset = source_id_offset;
-        pl->tmin_all = tmin_all;
-        pl->tmax_all = tmax_all;
-        if (verbose)
-            fprintf(stderr, "[bpmf] bp plan: K=%zu, no LDS plan (%s): global-memory gathers over %zu terms\n", K,
-                    !tpt ? "windows exceed the LDS" : (ph.NT > 256 ? "> 256 terms per source" : "bp.direct"),
-                    terms.size());
-        int rcd = 0;
-        if ((rcd = upload(hdr, &pl->d_dhdr)) || (rcd = upload(first, &pl->d_dfirst)) ||
-            (rcd = upload(terms, &pl->d_dterms))) {
-            bpmf_bp_plan_destroy(pl);
-            return rcd;
-        }
-        *plan_out = pl;
-        return 0;
-    }
-    pl->tpt = tpt;
-    pl->chunk = chunk;
-    pl->NT = ph.NT;
-    pl->n_groups = (int)ph.groups.size();
-    pl->lds_bytes = ph.lds_floats * sizeof(float);
-    pl->id_offset = source_id_offset;
-    pl->mean_group = (double)K / (double)ph.groups.size();
-    pl->dual = dual;
-    pl->tmin_all = tmin_all;
-    pl->tmax_all = tmax_all;
-    if (verbose)
-        fprintf(stderr, "[bpmf] bp plan: K=%zu groups=%d (mean %.1f src) tile=%d NT=%d chunk=%d lds=%zu B dual=%d classes=%zu\n",
-                K, pl->n_groups, pl->mean_group, BP_THREADS * tpt, pl->NT, chunk, pl->lds_bytes, (int)dual,
-                classes.size());
-    int rc = 0;
-    // packed per-station records for the two-phase kernel
-    if (P == 2 && ph.NT <= 64) {
-        const int nsta_max = ph.NT / 2;   // NT is a multiple of 4
-        const int opts[5] = {4, 8, 12, 16, 32};
-        for (int o = 0; o < 5 && !pl->nsv; ++o)
-            if (nsta_max <= opts[o]) pl->nsv = opts[o];
-    }
-    if (pl->nsv) {
-        std::vector<int4> recs(K * (size_t)(pl->nsv / 2), make_int4(0, 0, 0, 0));
-        std::vector<int4> hdr(K);
-        for (size_t q = 0; q < K; ++q) {
-            int* r = (int*)&recs[q * (pl->nsv / 2)];
-            const int nterm = ph.srcs[q].nterm;  // padded to the chunk (4): pairs of terms = stations
-            int nst = 0;
-            for (int j = 0; j + 1 < nterm; j += 2) {
-                const unsigned o0 = (unsigned)ph.off[q * ph.NT + j], o1 = (unsigned)ph.off[q * ph.NT + j + 1];
-                r[2 * nst] = (int)(o0 | (o1 << 16));
-                r[2 * nst + 1] = __builtin_bit_cast(int, ph.beta[q * ph.NT + j]);
-                ++nst;
-            }
-            hdr[q] = make_int4(ph.srcs[q].id, ph.srcs[q].tmin, ph.srcs[q].tmax, (nst + 1) / 2 * 2);
-        }
-        if ((rc = upload(recs, &pl->d_recs)) || (rc = upload(hdr, &pl->d_hdr2))) {
-            bpmf_bp_plan_destroy(pl);
-            return rc;
-        }
-    }
-    // the per-term table of bp_beam_wps_kernel (tile 512 without packed records, <= 32 terms per
-    // source): {byte offset, weight} pairs padded to ntv per source
-    if (tpt == 2 && !pl->nsv && ph.NT <= 32) {
-        pl->ntv = (ph.NT + 7) / 8 * 8;
-        std::vector<BpTermV> tv(K * (size_t)pl->ntv, BpTermV{0, 0.0f});
-        for (size_t q = 0; q < K; ++q)
-            for (int j = 0; j < ph.NT; ++j)
-                tv[q * pl->ntv + j] = BpTermV{ph.off[q * ph.NT + j] * 4, ph.beta[q * ph.NT + j]};
-        if ((rc = upload(tv, (BpTermV**)&pl->d_termsv))) { bpmf_bp_plan_destroy(pl); return rc; }
-    }
-    // interior-tile classes
-    if (use_fast) {
-        for (size_t c = 0; c < classes.size() && !rc; ++c) {
-            const ClassHost& ch = classes[c];
-            BpFastClass& fc = pl->cls[pl->n_classes];
-            fc.tile = ch.tile;
-            fc.halves = ch.halves;
-            fc.n_pass = ch.halves ? ch.ph.n_pass : 1;
-            fc.uniform = ch.fh.uniform;
-            fc.rec_dw = ch.fh.rec_dw;
-            fc.n_groups = (int)ch.fh.fg.size();
-            fc.lds_bytes = ch.ph.lds_floats * sizeof(float);
-            fc.n_sources = ch.fh.n_sources;
-            fc.max_stations = ch.fh.max_sta;
-            fc.desc_waves = (int)std::min<size_t>(BPF_DESC_MAX, (2 * S * P + 63) / 64 * 64) / 64;
-            ++pl->n_classes;
-            if ((rc = upload(ch.fh.fg, &fc.d_groups)) || (rc = upload(ch.fh.fr, &fc.d_runs)) ||
-                (rc = upload(ch.fh.fw, &fc.d_wins)) || (rc = upload(ch.fh.rec, &fc.d_recs)))
-                break;
-            if (verbose)
-                fprintf(stderr, "[bpmf] bp fast class %zu: tile %d, %zu sources (<= %d stations), %d groups, %zu runs, uniform=%d, rec=%d dwords\n",
-                        c, fc.tile, fc.n_sources, fc.max_stations, fc.n_groups, ch.fh.fr.size(), (int)fc.uniform, fc.rec_dw);
-        }
-        if (rc) { bpmf_bp_plan_destroy(pl); return rc; }
-        // the side stream is the device's (context.h: created once per device, never destroyed);
-        // the fork / join events are the plan's own
-        pl->side_stream = device_side_stream(device);
-        if (!pl->side_stream) { bpmf_bp_plan_destroy(pl); return -2; }
-        hipError_t e2 = hipEventCreateWithFlags(&pl->ev_fork, hipEventDisableTiming);
-        hipError_t e3 = hipEventCreateWithFlags(&pl->ev_join, hipEventDisableTiming);
-        if (e2 != hipSuccess || e3 != hipSuccess) {
-            set_error("bpmf_bp_plan_create: fork / join events: %s",
-                      hipGetErrorString(e2 != hipSuccess ? e2 : e3));
-            bpmf_bp_plan_destroy(pl);
-            return -2;
-        }
-        pl->fast = pl->n_classes > 0;
-        pl->fast_shares_generic = share;
-    }
-    if ((rc = upload(ph.groups, &pl->d_groups)) || (rc = upload(ph.chunks, &pl->d_chunks)) ||
-        (rc = upload(ph.srcs, &pl->d_srcs)) || (rc = upload(ph.off, &pl->d_off)) ||
-        (rc = upload(ph.beta, &pl->d_beta))) {
-        bpmf_bp_plan_destroy(pl);
-        return rc;
-    }
-    *plan_out = pl;
-    return 0;
+    // decided on the host (bp_plan.hip), then copied to the device as it is
+    return bp_plan_upload(bp_plan_host(moveouts, w_sources, K, S, P, source_id_offset), device, plan_out);
 }
 
 extern "C" void bpmf_bp_plan_destroy(bpmf_bp_plan* pl)
@@ -1821,117 +1024,12 @@ extern "C" void bpmf_bp_plan_destroy(bpmf_bp_plan* pl)
     delete pl;
 }
 
-extern "C" int bpmf_bp_plan_info(const bpmf_bp_plan* pl, bpmf_bp_plan_stats* out)
-{
-    if (!pl || !out) {
-        set_error("bpmf_bp_plan_info: bad argument");
-        return -1;
-    }
-    if (pl->direct) {               // no LDS plan: global-memory gathers (bp_direct.hip)
-        memset(out, 0, sizeof(*out));
-        out->tile = 1024;
-        out->gather_bytes = 4;
-        out->waves_per_cu = 8;
-        return 0;
-    }
-    out->n_groups = pl->n_groups;
-    out->tile = BP_THREADS * pl->tpt;
-    out->lds_bytes = (int32_t)pl->lds_bytes;
-    out->gather_bytes = pl->dual ? 8 : 4;
-    out->stations_max = pl->nsv;
-    const bool packed = pl->nsv && pl->tpt == 2;
-    out->waves_per_cu = !packed ? 8 : (pl->nsv > 16 ? 16 : (pl->dual ? 16 : 24));
-    // reduce="max": the interior tiles run the classes of bp_fast.hip (8-byte gathers, 16 waves per CU);
-    // tile / n_groups then describe the class that holds most sources
-    out->n_classes = pl->fast ? pl->n_classes : 0;
-    for (int c = 0; c < 3; ++c) {
-        const bool on = pl->fast && c < pl->n_classes;
-        out->class_tile[c] = on ? pl->cls[c].tile : 0;
-        out->class_sources[c] = on ? (int32_t)pl->cls[c].n_sources : 0;
-        out->class_groups[c] = on ? pl->cls[c].n_groups : 0;
-        out->class_stations_max[c] = on ? pl->cls[c].max_stations : 0;
-    }
-    if (pl->fast) {
-        int big = 0;
-        for (int c = 1; c < pl->n_classes; ++c)
-            if (pl->cls[c].n_sources > pl->cls[big].n_sources) big = c;
-        out->tile = pl->cls[big].tile;
-        out->n_groups = pl->cls[big].n_groups;
-        out->lds_bytes = (int32_t)pl->cls[big].lds_bytes;
-        out->gather_bytes = 8;
-        out->waves_per_cu = 16;
-    }
-    return 0;
-}
-
-namespace {
-// Group ranges per tile (gridDim.y of the beam kernels).  A workgroup owns a 512-sample tile and one
-// workgroup fills a CU, so a series of fewer than ~128 tiles -- the reference's event relocation
-// beamforms 1 500-3 000 samples over the whole grid (BPMF/dataset.py:2174-2216) -- leaves most of the
-// 256 CUs idle (and up to ~1000 tiles the last round of workgroups runs half empty): the groups of the
-// plan are then dealt to 1024 / tiles workgroups per tile.
-// option bp.split: 0/1 = off, n = force n ranges (tests), -1 = automatic.  Only the P = 2 packed kernels take it.
-bool generic_can_split(const bpmf_bp_plan* pl)
-{
-    return pl->tpt == 2 && pl->nsv && pl->n_groups >= 2;   // (dispatch_beam's packed kernels)
-}
-
-// `forced` = option bp.split as the CALLER read it (once per call: the size check of the workspace and the
-// launches must see the same value even if another thread sets the option in between)
-// `n_events`: series of N samples computed by one launch (a batch of events fills the chip with its events' tiles)
-long long split_wanted(size_t N, int forced, size_t n_events = 1)
-{
-    const long long n_tiles = (long long)((N + 511) / 512) * (long long)n_events;
-    // enough workgroups for ~4 rounds over the 256 CUs (a split costs one merge pass and nothing else:
-    // the ranges stage disjoint windows), none from 1024 tiles (N >= 524 288) on
-    long long want = n_tiles >= 1024 ? 1 : (1024 + n_tiles - 1) / n_tiles;
-    if (forced >= 0) want = forced < 1 ? 1 : forced;
-    return want;
-}
-
-// the general kernels alone (reduce="none", plans without interior classes)
-int bp_split_count(const bpmf_bp_plan* pl, size_t N, int forced, size_t n_events = 1)
-{
-    if (!pl || !generic_can_split(pl)) return 1;
-    return (int)std::max<long long>(1, std::min<long long>(split_wanted(N, forced, n_events), pl->n_groups));
-}
-
-// reduce="max" on a plan with interior classes: group ranges per tile of every class kernel, and of
-// the general kernel on the edge tiles (1 when that kernel cannot split)
-void bp_fast_split_counts(const bpmf_bp_plan* pl, size_t N, int forced, int& n_split, int& n_split_edge)
-{
-    long long want = split_wanted(N, forced);
-    for (int c = 0; c < pl->n_classes; ++c) {
-        want = std::min<long long>(want, pl->cls[c].n_groups / pl->cls[c].n_pass);   // (groups of sources, not entries)
-    }
-    const bool gsplit = generic_can_split(pl);
-    if (gsplit) want = std::min<long long>(want, pl->n_groups);
-    n_split = (int)std::max<long long>(1, want);
-    n_split_edge = gsplit ? n_split : 1;
-}
-}  // namespace
-
-namespace {
-// workspace of one call under bp.split = `forced`: the prestacked traces + the partial maxima, one row per
-// group range of a short series (bp_split_count) and per station-count class of the interior kernel
-size_t bp_workspace_bytes(const bpmf_bp_plan* pl, size_t N, int forced)
-{
-    size_t rows = pl->direct ? (size_t)direct_split_count(pl, N) : (size_t)bp_split_count(pl, N, forced);
-    if (pl->fast) {
-        int n_split, n_split_edge;
-        bp_fast_split_counts(pl, N, forced, n_split, n_split_edge);
-        rows = std::max(rows, (size_t)n_split * (size_t)pl->n_classes);
-    }
-    return align_up(pl->S * pl->P * N * sizeof(float), 256) +
-           (rows > 1 ? align_up(rows * N * (sizeof(float) + sizeof(int32_t)), 256) : 0);
-}
-}  // namespace
-
+// workspace of one call: the prestacked traces + the partial maxima (bp_schedule: sized for either `reduce`)
 extern "C" size_t bpmf_bp_workspace_bytes(const bpmf_bp_plan* pl, size_t N, size_t C)
 {
     (void)C;
     if (!pl) return 0;
-    return bp_workspace_bytes(pl, N, (int)option(OPT_BP_SPLIT));
+    return bp_schedule(pl->shape, N, BPMF_BP_REDUCE_MAX, (int)option(OPT_BP_SPLIT), 0).total;
 }
 
 namespace {
@@ -1998,11 +1096,11 @@ int with_oob_reduce(int oob, int reduce, F f)
                                  : f(IntC<BPMF_BP_FLEXIBLE>{}, IntC<BPMF_BP_REDUCE_NONE>{});
 }
 
-// The general kernel of a plan over lc's samples: packed per-station records (P = 2, tile 512), else the
-// per-term table (<= 32 terms per source, tile 512), else the readlane kernel (any plan, tile 256 x tpt).
-int dispatch_beam(const bpmf_bp_plan* pl, const float* U, size_t N, int oob, int reduce, const BpLaunch& lc,
-                  hipStream_t stream, float* beam, int32_t* arg)
+// The general kernel `k` of a plan (bp_general_kernel: the schedule's choice) over lc's samples.
+int dispatch_beam(const bpmf_bp_plan* pl, const BpKernel& k, const float* U, size_t N, int oob, int reduce,
+                  const BpLaunch& lc, hipStream_t stream, float* beam, int32_t* arg)
 {
+    const BpPlanShape& sh = pl->shape;
     return with_oob_reduce(oob, reduce, [&](auto oob_c, auto reduce_c) -> int {
         constexpr int OOB = decltype(oob_c)::value, REDUCE = decltype(reduce_c)::value;
         // a batch of series (lc.n_events > 1, reduce="max") runs the BATCH instantiation of the same kernel
@@ -2015,66 +1113,65 @@ int dispatch_beam(const bpmf_bp_plan* pl, const float* U, size_t N, int oob, int
             constexpr int WPB = decltype(wpb_c)::value;
             auto kern = bp_beam_wps2_kernel<WPB, decltype(nsv_c)::value, OOB, REDUCE, decltype(b64_c)::value,
                                             decltype(batch_c)::value>;
-            const size_t lds = std::max(pl->lds_bytes, (size_t)2 * WPB * 512 * sizeof(float));
-            return launch_general(kern, lds, 512, N, lc, stream, [&](long long tile_base, long long n_tiles) {
+            return launch_general(kern, k.lds_bytes, k.tile, N, lc, stream, [&](long long tile_base, long long n_tiles) {
                 // x: a multiple of 8 (XCD-aware tile order), y: group ranges
-                kern<<<dim3((unsigned)((n_tiles + 7) / 8 * 8), (unsigned)lc.n_split, (unsigned)lc.n_events), dim3(64 * WPB), lds,
-                       stream>>>(
-                    U, (long long)N, pl->d_groups, pl->n_groups, (const int4*)pl->d_chunks, pl->d_hdr2, pl->d_recs,
-                    pl->id_offset, beam, arg, tile_base, n_tiles, lc.split_stride, lc.best0, lc.u_estride, lc.out_estride);
+                kern<<<dim3((unsigned)((n_tiles + 7) / 8 * 8), (unsigned)lc.n_split, (unsigned)lc.n_events), dim3(64 * WPB),
+                       k.lds_bytes, stream>>>(
+                    U, (long long)N, pl->d_groups, sh.n_groups, (const int4*)pl->d_chunks, pl->d_hdr2, pl->d_recs,
+                    sh.id_offset, beam, arg, tile_base, n_tiles, lc.split_stride, lc.best0, lc.u_estride, lc.out_estride);
             });
         }); };
         auto wps = [&](auto ntv_c) -> int { return batched([&](auto batch_c) -> int {
             auto kern = bp_beam_wps_kernel<8, decltype(ntv_c)::value, OOB, REDUCE, decltype(batch_c)::value>;
-            // the end-of-kernel merge needs 2 * 4 * tile floats of LDS
-            const size_t lds = std::max(pl->lds_bytes, (size_t)8 * 512 * sizeof(float));
-            return launch_general(kern, lds, 512, N, lc, stream, [&](long long tile_base, long long n_tiles) {
-                kern<<<dim3((unsigned)n_tiles, 1, (unsigned)lc.n_events), dim3(BP_THREADS), lds, stream>>>(
-                    U, (long long)N, pl->d_groups, pl->n_groups, (const int4*)pl->d_chunks, (const int4*)pl->d_srcs,
-                    (const int4*)pl->d_termsv, pl->id_offset, beam, arg, tile_base, lc.best0, lc.u_estride, lc.out_estride);
+            return launch_general(kern, k.lds_bytes, k.tile, N, lc, stream, [&](long long tile_base, long long n_tiles) {
+                kern<<<dim3((unsigned)n_tiles, 1, (unsigned)lc.n_events), dim3(BP_THREADS), k.lds_bytes, stream>>>(
+                    U, (long long)N, pl->d_groups, sh.n_groups, (const int4*)pl->d_chunks, (const int4*)pl->d_srcs,
+                    (const int4*)pl->d_termsv, sh.id_offset, beam, arg, tile_base, lc.best0, lc.u_estride, lc.out_estride);
             });
         }); };
         auto readlane = [&](auto tpt_c, auto nblk_c) -> int { return batched([&](auto batch_c) -> int {
-            constexpr int TPT = decltype(tpt_c)::value;
-            auto kern = bp_beam_kernel<TPT, 4, decltype(nblk_c)::value, OOB, REDUCE, decltype(batch_c)::value>;
-            return launch_general(kern, pl->lds_bytes, (size_t)BP_THREADS * TPT, N, lc, stream,
-                                  [&](long long tile_base, long long n_tiles) {
-                kern<<<dim3((unsigned)n_tiles, 1, (unsigned)lc.n_events), dim3(BP_THREADS), pl->lds_bytes, stream>>>(
-                    U, (long long)N, pl->d_groups, pl->n_groups, (const int4*)pl->d_chunks, (const int*)pl->d_srcs,
-                    pl->d_off, pl->d_beta, pl->NT, pl->id_offset, beam, arg, tile_base, lc.best0, lc.u_estride,
+            auto kern = bp_beam_kernel<decltype(tpt_c)::value, 4, decltype(nblk_c)::value, OOB, REDUCE, decltype(batch_c)::value>;
+            return launch_general(kern, k.lds_bytes, k.tile, N, lc, stream, [&](long long tile_base, long long n_tiles) {
+                kern<<<dim3((unsigned)n_tiles, 1, (unsigned)lc.n_events), dim3(BP_THREADS), k.lds_bytes, stream>>>(
+                    U, (long long)N, pl->d_groups, sh.n_groups, (const int4*)pl->d_chunks, (const int*)pl->d_srcs,
+                    pl->d_off, pl->d_beta, sh.NT, sh.id_offset, beam, arg, tile_base, lc.best0, lc.u_estride,
                     lc.out_estride);
             });
         }); };
-        if (pl->tpt == 2) {
-            // Packed records of <= 16 stations keep a source's metadata in SGPRs: 16 waves per workgroup with
-            // the 8-byte gathers of a dual plan, 12 (2 workgroups, 24 waves per CU) with 4-byte gathers, which
-            // need >= 4 waves/SIMD to reach the LDS rate.  32 stations: one 16-wave workgroup per CU, the
-            // records gathered in two parts.
-            switch (pl->nsv) {
-                case 4: return pl->dual ? wps2(IntC<16>{}, IntC<4>{}, std::true_type{})
-                                        : wps2(IntC<12>{}, IntC<4>{}, std::false_type{});
-                case 8: return pl->dual ? wps2(IntC<16>{}, IntC<8>{}, std::true_type{})
-                                        : wps2(IntC<12>{}, IntC<8>{}, std::false_type{});
-                case 12: return pl->dual ? wps2(IntC<16>{}, IntC<12>{}, std::true_type{})
-                                         : wps2(IntC<12>{}, IntC<12>{}, std::false_type{});
-                case 16: return pl->dual ? wps2(IntC<16>{}, IntC<16>{}, std::true_type{})
-                                         : wps2(IntC<12>{}, IntC<16>{}, std::false_type{});
-                case 32: return wps2(IntC<16>{}, IntC<32>{}, std::false_type{});
+        // <= 16 stations: 16 waves with 8-byte gathers or 12 with 4-byte gathers
+        auto wps2_upto16 = [&](auto nsv_c) -> int {
+            if (k.wpb == 16 && k.b64) return wps2(IntC<16>{}, nsv_c, std::true_type{});
+            if (k.wpb == 12 && !k.b64) return wps2(IntC<12>{}, nsv_c, std::false_type{});
+            return -1;
+        };
+        int rc = -1;            // (stays -1: a kernel that is not compiled)
+        if (k.family == BP_FAMILY_WPS2) {
+            switch (k.nsv) {
+                case 4: rc = wps2_upto16(IntC<4>{}); break;
+                case 8: rc = wps2_upto16(IntC<8>{}); break;
+                case 12: rc = wps2_upto16(IntC<12>{}); break;
+                case 16: rc = wps2_upto16(IntC<16>{}); break;
+                case 32: if (k.wpb == 16 && !k.b64) rc = wps2(IntC<16>{}, IntC<32>{}, std::false_type{}); break;
                 default: break;
             }
-            switch (pl->ntv) {
-                case 8: return wps(IntC<8>{});
-                case 16: return wps(IntC<16>{});
-                case 24: return wps(IntC<24>{});
-                case 32: return wps(IntC<32>{});
+        } else if (k.family == BP_FAMILY_WPS) {
+            switch (k.ntv) {
+                case 8: rc = wps(IntC<8>{}); break;
+                case 16: rc = wps(IntC<16>{}); break;
+                case 24: rc = wps(IntC<24>{}); break;
+                case 32: rc = wps(IntC<32>{}); break;
+                default: break;
+            }
+        } else if (k.family == BP_FAMILY_READLANE && (k.tpt == 1 || k.tpt == 2)) {
+            const bool t1 = k.tpt == 1;
+            switch (k.nblk) {
+                case 1: rc = t1 ? readlane(IntC<1>{}, IntC<1>{}) : readlane(IntC<2>{}, IntC<1>{}); break;
+                case 2: rc = t1 ? readlane(IntC<1>{}, IntC<2>{}) : readlane(IntC<2>{}, IntC<2>{}); break;
+                case 4: rc = t1 ? readlane(IntC<1>{}, IntC<4>{}) : readlane(IntC<2>{}, IntC<4>{}); break;
                 default: break;
             }
         }
-        // blocks of 64 terms per source: 1, 2 or 4
-        const bool t1 = pl->tpt == 1;
-        if (pl->NT <= 64) return t1 ? readlane(IntC<1>{}, IntC<1>{}) : readlane(IntC<2>{}, IntC<1>{});
-        if (pl->NT <= 128) return t1 ? readlane(IntC<1>{}, IntC<2>{}) : readlane(IntC<2>{}, IntC<2>{});
-        return t1 ? readlane(IntC<1>{}, IntC<4>{}) : readlane(IntC<2>{}, IntC<4>{});
+        return rc;
     });
 }
 
@@ -2105,6 +1202,27 @@ struct BpFeed {
     virtual ~BpFeed() {}
 };
 
+// What every reduce="max" launch sequence does around its beam kernels: the kernels write `sch.rows` partial
+// (beam, arg) rows per series behind the prestack -- or, with one row, straight into the outputs --, one merge
+// launch folds them (interior samples [lo_s, hi_s) hold all the rows, the samples around them those of the edge
+// kernel; `n_series` series with their sets of rows one behind the other), then `finish(beam, arg)`.
+// launch(pbeam, parg, merge) enqueues the kernels.
+template <typename Launch, typename Finish>
+int with_partial_rows(const BpSchedule& sch, void* d_workspace, size_t N, size_t n_series, float* beam, int32_t* arg,
+                      hipStream_t stream, Launch launch, Finish finish)
+{
+    const bool merge = sch.rows > 1;
+    float* pbeam = merge ? (float*)((char*)d_workspace + sch.o_pbeam) : beam;
+    int32_t* parg = merge ? (int32_t*)((char*)d_workspace + sch.o_parg) : arg;
+    if (int rc = launch(pbeam, parg, merge)) return rc;
+    if (merge) {
+        bp_merge_splits_kernel<<<dim3((unsigned)((N + 255) / 256), (unsigned)n_series), dim3(256), 0, stream>>>(
+            pbeam, parg, sch.rows, sch.n_split_edge, sch.lo_s, sch.hi_s, N, beam, arg, (size_t)sch.rows * N);
+        BPMF_LAUNCH_CHECK();
+    }
+    return finish(beam, arg);
+}
+
 // bpmf_bp_run_dev, and a host-pointer call's run on the device: `feed` (not null: the day of features is still
 // arriving, see BpFeed) and `defer_finish` (option bp.compat_first_computed: samples without any computed beam
 // keep -inf; bpmf_bp_run_multi finishes them after the merge of all devices' shares)
@@ -2129,11 +1247,11 @@ int bp_run_dev(const bpmf_bp_plan* pl, const float* d_features, const float* d_w
         set_error("bpmf_bp_run_dev: N exceeds the int32 index range");
         return -1;
     }
-    // option bp.split is read ONCE: the size check and every launch below use this value
-    const int forced_split = (int)option(OPT_BP_SPLIT);
-    if (workspace_bytes < bp_workspace_bytes(pl, N, forced_split)) {
-        set_error("bpmf_bp_run_dev: workspace too small (%zu < %zu)", workspace_bytes,
-                  bp_workspace_bytes(pl, N, forced_split));
+    const BpPlanShape& sh = pl->shape;
+    // option bp.split is read ONCE: the size check and every launch below follow this schedule
+    const BpSchedule sch = bp_schedule(sh, N, reduce, (int)option(OPT_BP_SPLIT), 0);
+    if (workspace_bytes < sch.total) {
+        set_error("bpmf_bp_run_dev: workspace too small (%zu < %zu)", workspace_bytes, sch.total);
         return -1;
     }
     // option debug.poison_output (tests): a sample that no kernel writes comes back as NaN / -1 instead of
@@ -2142,15 +1260,15 @@ int bp_run_dev(const bpmf_bp_plan* pl, const float* d_features, const float* d_w
         BPMF_HIP_CHECK(hipMemsetAsync(d_beam_out, 0xFF, N * sizeof(float), stream));
         BPMF_HIP_CHECK(hipMemsetAsync(d_arg_out, 0xFF, N * sizeof(int32_t), stream));
     }
-    float* U = (float*)d_workspace;
-    const int P = (int)pl->P, S = (int)pl->S;
+    float* U = (float*)((char*)d_workspace + sch.o_prestack);
+    const int P = (int)sh.P, S = (int)sh.S;
     // A host-pointer call may stream its day of features in while the kernels run (BpFeed, bpmf_bp_run):
     // the feed uploads AND prestacks piece by piece; only the interior-tile path below consumes it in
     // pieces, every other path asks for the whole series first.
     // option bp.host_piece_samples: samples of the first piece (default 131 072 = one round of the chip at tile
     // 512; the tests shrink it), 0 = the whole day in front of the first kernel
     const long long piece0 = (long long)align_up((size_t)option(OPT_BP_HOST_PIECE_SAMPLES), 1024);
-    const bool feed_pieces = feed && pl->fast && !pl->direct && reduce == BPMF_BP_REDUCE_MAX && piece0 > 0;
+    const bool feed_pieces = feed && sch.path == BP_PATH_INTERIOR && piece0 > 0;
     if (feed && !feed_pieces)
         if (int rc = feed->need((long long)N, stream)) return rc;
     if (!feed)
@@ -2160,56 +1278,35 @@ int bp_run_dev(const bpmf_bp_plan* pl, const float* d_features, const float* d_w
     auto finish = [&](float* beam, int32_t* arg) -> int {
         if (first_computed && !defer_finish) {
             bp_finish_first_computed_kernel<<<dim3((unsigned)((N + 255) / 256)), dim3(256), 0, stream>>>(
-                beam, arg, N, pl->id_offset);
+                beam, arg, N, sh.id_offset);
             BPMF_LAUNCH_CHECK();
         }
         return 0;
     };
-    float* const beam_final = d_beam_out;
-    int32_t* const arg_final = d_arg_out;
-    char* const part = (char*)d_workspace + align_up((size_t)S * P * N * sizeof(float), 256);
-    if (pl->direct) {
-        // no LDS plan: global-memory gathers, ranges of sources per tile folded by the merge kernel
-        const int rows = reduce == BPMF_BP_REDUCE_MAX ? direct_split_count(pl, N) : 1;
-        float* pbeam = rows > 1 ? (float*)part : beam_final;
-        int32_t* parg = rows > 1 ? (int32_t*)(part + (size_t)rows * N * sizeof(float)) : arg_final;
+    if (sch.path == BP_PATH_DIRECT) {
+        // no LDS plan: global-memory gathers, ranges of sources per tile
         profile_mark(BPMF_KERNEL_BP_BEAM, 0, stream);
-        int rc = launch_beam_direct(pl, U, N, out_of_bounds, reduce, stream, pbeam, parg, rows, (long long)N, best0);
-        if (!rc && rows > 1) {
-            bp_merge_splits_kernel<<<dim3((unsigned)((N + 255) / 256)), dim3(256), 0, stream>>>(
-                pbeam, parg, rows, rows, 0, (long long)N, N, beam_final, arg_final, 0);
-            BPMF_LAUNCH_CHECK();
-        }
-        if (!rc && reduce == BPMF_BP_REDUCE_MAX) rc = finish(beam_final, arg_final);
+        const int rc = with_partial_rows(sch, d_workspace, N, 1, d_beam_out, d_arg_out, stream,
+                                         [&](float* pbeam, int32_t* parg, bool) -> int {
+            return launch_beam_direct(pl, U, N, out_of_bounds, reduce, stream, pbeam, parg, sch.n_split, (long long)N, best0);
+        }, finish);
         profile_mark(BPMF_KERNEL_BP_BEAM, 1, stream);
         return rc;
     }
-    if (pl->fast && reduce == BPMF_BP_REDUCE_MAX) {
-        // Samples on which no source can leave the trace -- t + tmin_all >= 0 and t + tmax_all (+ the
-        // staging slack of 8 samples) < N, rounded to multiples of 1024 (whole tiles of every kernel) --
-        // run the interior kernel of bp_fast.hip, once per station-count class, which is the same for
-        // strict and flexible; the few tiles at the ends of the day run the general kernel over all
-        // sources.  Several classes, or several group ranges per tile on a short series, write
-        // partial rows behind the prestack, folded by one merge launch (value, then lowest id).
-        int n_split, n_split_edge;
-        bp_fast_split_counts(pl, N, forced_split, n_split, n_split_edge);
-        const int rows = n_split * pl->n_classes;
-        long long lo_s = pl->tmin_all < 0 ? ((long long)(-pl->tmin_all) + 1023) / 1024 * 1024 : 0;
-        long long hi_s = ((long long)N - pl->tmax_all - 8) / 1024 * 1024;
-        if ((long long)N - pl->tmax_all - 8 < 0) hi_s = 0;
-        // The interior range ends at a WHOLE tile of every kernel inside the series.  (Rounds 2-3 clamped it
-        // to N: when every used moveout is negative -- tmax_all < -8 -- N - tmax_all - 8 exceeds N, the clamp
-        // left a bound that is no multiple of the tile, the interior launch stopped at the last whole tile
-        // below it and the edge launch, starting AT the bound, was empty: the samples of the last partial
-        // tile were never written.  Found by the 150 000-case session of round 4, seeds 15831 and 17025 of
-        // test_bp_random_shapes_signed_moveouts; pinned by test_bp_all_used_moveouts_negative.)
-        hi_s = std::min(hi_s, (long long)N / 1024 * 1024);
-        lo_s = std::min(lo_s, (long long)N);
-        hi_s = std::max(lo_s, hi_s);
-        float* pbeam = rows > 1 ? (float*)part : beam_final;
-        int32_t* parg = rows > 1 ? (int32_t*)(part + (size_t)rows * N * sizeof(float)) : arg_final;
-        std::lock_guard<std::mutex> enqueue_lock(pl->enqueue_mutex);
-        profile_mark(BPMF_KERNEL_BP_BEAM, 0, stream);
+    if (sch.path == BP_PATH_GENERAL)    // the general kernels over the whole series
+        return with_partial_rows(sch, d_workspace, N, 1, d_beam_out, d_arg_out, stream,
+                                 [&](float* pbeam, int32_t* parg, bool merge) -> int {
+            return dispatch_beam(pl, sch.kernel, U, N, out_of_bounds, reduce,
+                                 BpLaunch{0, -1, sch.n_split, merge ? (long long)N : 0, best0}, stream, pbeam, parg);
+        }, finish);
+    // The interior samples [lo_s, hi_s) run the class kernels of bp_fast.hip, the tiles at the ends of the day the
+    // general kernel over all sources (bp_schedule)
+    const int n_split = sch.n_split;
+    const long long lo_s = sch.lo_s, hi_s = sch.hi_s;
+    std::lock_guard<std::mutex> enqueue_lock(pl->enqueue_mutex);
+    profile_mark(BPMF_KERNEL_BP_BEAM, 0, stream);
+    const int rc_all = with_partial_rows(sch, d_workspace, N, 1, d_beam_out, d_arg_out, stream,
+                                         [&](float* pbeam, int32_t* parg, bool merge) -> int {
         int rc = 0;
         const bool have_edge = lo_s > 0 || hi_s < (long long)N;
         hipStream_t es = stream;          // edge tiles: on the side stream, beside the interior kernels
@@ -2220,8 +1317,8 @@ int bp_run_dev(const bpmf_bp_plan* pl, const float* d_features, const float* d_w
         }
         auto edge = [&](long long from, long long to) {
             if (to > from && !rc)
-                rc = dispatch_beam(pl, U, N, out_of_bounds, reduce,
-                                   BpLaunch{from, to, n_split_edge, rows > 1 ? (long long)N : 0, best0}, es, pbeam, parg);
+                rc = dispatch_beam(pl, sch.kernel, U, N, out_of_bounds, reduce,
+                                   BpLaunch{from, to, sch.n_split_edge, merge ? (long long)N : 0, best0}, es, pbeam, parg);
         };
         auto run_edges = [&]() {
             edge(0, lo_s);
@@ -2260,102 +1357,55 @@ int bp_run_dev(const bpmf_bp_plan* pl, const float* d_features, const float* d_w
                 if (hi_s - b < piece0) b = hi_s;          // no sliver at the end
                 piece = std::min<long long>(piece * 2, 4 * piece0);
                 if (b == hi_s) rc = edges_of_a_fed_day();
-                else rc = feed->need(std::min<long long>((long long)N, b + std::max(pl->tmax_all, 0) + 8 + 1024), stream);
+                else rc = feed->need(std::min<long long>((long long)N, b + std::max(sh.tmax_all, 0) + 8 + 1024), stream);
             }
-            for (int c = 0; c < pl->n_classes && !rc; ++c) {
+            for (int c = 0; c < sh.n_classes && !rc; ++c) {
                 const BpFastClass& fc = pl->cls[c];
-                rc = launch_beam_fast(fc, pl->id_offset, U, N, a / fc.tile, b / fc.tile, stream,
+                rc = launch_beam_fast(fc, sh.id_offset, U, N, a / fc.tile, b / fc.tile, stream,
                                       pbeam + (size_t)c * n_split * N, parg + (size_t)c * n_split * N, n_split,
-                                      rows > 1 ? (long long)N : 0, best0);
+                                      merge ? (long long)N : 0, best0);
             }
             a = b;
         }
         if (feed_pieces && !rc && !edges_done) rc = edges_of_a_fed_day();     // (no interior tile at all)
         if (!rc && es != stream) BPMF_HIP_CHECK(hipStreamWaitEvent(stream, pl->ev_join, 0));
-        if (!rc && rows > 1) {
-            bp_merge_splits_kernel<<<dim3((unsigned)((N + 255) / 256)), dim3(256), 0, stream>>>(
-                pbeam, parg, rows, n_split_edge, lo_s, hi_s, N, beam_final, arg_final, 0);
-            BPMF_LAUNCH_CHECK();
-        }
-        if (!rc) rc = finish(beam_final, arg_final);
-        profile_mark(BPMF_KERNEL_BP_BEAM, 1, stream);
         return rc;
-    }
-    // the general kernels over the whole series.  Short series: several group ranges per tile
-    // (bp_split_count); reduce="max" goes through partial rows and one merge launch
-    const int n_split = bp_split_count(pl, N, forced_split);
-    const bool merge = n_split > 1 && reduce == BPMF_BP_REDUCE_MAX;
-    if (merge) {
-        d_beam_out = (float*)part;
-        d_arg_out = (int32_t*)(part + (size_t)n_split * N * sizeof(float));
-    }
-    int rc = dispatch_beam(pl, U, N, out_of_bounds, reduce, BpLaunch{0, -1, n_split, merge ? (long long)N : 0, best0},
-                           stream, d_beam_out, d_arg_out);
-    if (!rc && merge) {
-        bp_merge_splits_kernel<<<dim3((unsigned)((N + 255) / 256)), dim3(256), 0, stream>>>(
-            d_beam_out, d_arg_out, n_split, n_split, 0, (long long)N, N, beam_final, arg_final, 0);
-        BPMF_LAUNCH_CHECK();
-    }
-    if (!rc && reduce == BPMF_BP_REDUCE_MAX) rc = finish(beam_final, arg_final);
-    return rc;
+    }, finish);
+    profile_mark(BPMF_KERNEL_BP_BEAM, 1, stream);
+    return rc_all;
 }
 
 }  // namespace
 
 // ---- a batch of short series (event relocation, bp_relocate.hip) ----
-// Partial rows behind the prestacks of `E` series: the group ranges of the general kernels count the tiles of the
-// WHOLE batch (a few hundred events fill the chip without any split); a plan without LDS windows runs its events
-// one after the other on the stream and folds each through the same rows.
-size_t bpmf::bp_max_batch_part_bytes(const bpmf_bp_plan* pl, size_t N, size_t E, int forced_split)
-{
-    if (pl->direct) {
-        const size_t rows = (size_t)direct_split_count(pl, N);
-        return rows > 1 ? align_up(rows * N * (sizeof(float) + sizeof(int32_t)), 256) : 0;
-    }
-    const size_t rows = (size_t)bp_split_count(pl, N, forced_split, E);
-    return rows > 1 ? align_up(E * rows * N * (sizeof(float) + sizeof(int32_t)), 256) : 0;
-}
-
 // reduce="max" of E series: event e reads the prestack U + e S P N and writes beam / arg + e N.  Always the general
 // kernel over every tile (series this short have next to no interior tiles), the build's conventions (running
-// maximum from (0, first id)).
-int bpmf::bp_max_batch(const bpmf_bp_plan* pl, const float* U, size_t N, size_t E, int out_of_bounds, int forced_split,
-                       void* d_part, hipStream_t stream, float* beam, int32_t* arg)
+// maximum from (0, first id)).  A plan without LDS windows runs its events one after the other on the stream and
+// folds each through the same rows.
+int bpmf::bp_max_batch(const bpmf_bp_plan* pl, const BpSchedule& sch, void* d_workspace, size_t N, size_t E,
+                       int out_of_bounds, hipStream_t stream, float* beam, int32_t* arg)
 {
-    const size_t u_estride = pl->S * pl->P * N;
-    const dim3 mgrid((unsigned)((N + 255) / 256), 1);
-    if (pl->direct) {
-        const int rows = direct_split_count(pl, N);
-        float* pbeam = (float*)d_part;
-        int32_t* parg = (int32_t*)((char*)d_part + (size_t)rows * N * sizeof(float));
+    const float* U = (const float*)((char*)d_workspace + sch.o_prestack);
+    const size_t u_estride = pl->shape.S * pl->shape.P * N;
+    auto finish = [](float*, int32_t*) -> int { return 0; };
+    if (sch.path == BP_PATH_DIRECT) {
         for (size_t e = 0; e < E; ++e) {
-            float* be = beam + e * N;
-            int32_t* ae = arg + e * N;
-            if (int rc = launch_beam_direct(pl, U + e * u_estride, N, out_of_bounds, BPMF_BP_REDUCE_MAX, stream,
-                                            rows > 1 ? pbeam : be, rows > 1 ? parg : ae, rows, (long long)N, 0.0f))
+            if (int rc = with_partial_rows(sch, d_workspace, N, 1, beam + e * N, arg + e * N, stream,
+                                           [&](float* pbeam, int32_t* parg, bool) -> int {
+                    return launch_beam_direct(pl, U + e * u_estride, N, out_of_bounds, BPMF_BP_REDUCE_MAX, stream, pbeam,
+                                              parg, sch.n_split, (long long)N, 0.0f);
+                }, finish))
                 return rc;
-            if (rows > 1) {
-                bp_merge_splits_kernel<<<mgrid, dim3(256), 0, stream>>>(pbeam, parg, rows, rows, 0, (long long)N, N, be, ae, 0);
-                BPMF_LAUNCH_CHECK();
-            }
         }
         return 0;
     }
-    const int n_split = bp_split_count(pl, N, forced_split, E);
-    const bool merge = n_split > 1;
-    float* pbeam = merge ? (float*)d_part : beam;
-    int32_t* parg = merge ? (int32_t*)((char*)d_part + E * (size_t)n_split * N * sizeof(float)) : arg;
-    BpLaunch lc{0, -1, n_split, merge ? (long long)N : 0, 0.0f};
-    lc.n_events = (int)E;
-    lc.u_estride = (long long)u_estride;
-    lc.out_estride = (long long)(merge ? (size_t)n_split * N : N);
-    if (int rc = dispatch_beam(pl, U, N, out_of_bounds, BPMF_BP_REDUCE_MAX, lc, stream, pbeam, parg)) return rc;
-    if (merge) {
-        bp_merge_splits_kernel<<<dim3(mgrid.x, (unsigned)E), dim3(256), 0, stream>>>(
-            pbeam, parg, n_split, n_split, 0, (long long)N, N, beam, arg, (size_t)n_split * N);
-        BPMF_LAUNCH_CHECK();
-    }
-    return 0;
+    return with_partial_rows(sch, d_workspace, N, E, beam, arg, stream, [&](float* pbeam, int32_t* parg, bool merge) -> int {
+        BpLaunch lc{0, -1, sch.n_split, merge ? (long long)N : 0, 0.0f};
+        lc.n_events = (int)E;
+        lc.u_estride = (long long)u_estride;
+        lc.out_estride = (long long)(merge ? (size_t)sch.rows * N : N);
+        return dispatch_beam(pl, sch.kernel, U, N, out_of_bounds, BPMF_BP_REDUCE_MAX, lc, stream, pbeam, parg);
+    }, finish);
 }
 
 extern "C" int bpmf_bp_run_dev(const bpmf_bp_plan* pl, const float* d_features,

@@ -17,7 +17,8 @@
 
 namespace bpmf {
 
-constexpr int BPD_THREADS = 256, BPD_TPT = 4, BPD_TILE = BPD_THREADS * BPD_TPT;
+constexpr int BPD_THREADS = 256, BPD_TPT = 4;
+static_assert(BPD_TILE == BPD_THREADS * BPD_TPT, "bp_plan.h: BPD_TILE");
 
 // gridDim.y: reduce="max": ranges of sources (partial rows `split_stride` apart, folded by
 // bp_merge_splits_kernel); reduce="none": one source per blockIdx.y (+ 65535 z)
@@ -95,14 +96,6 @@ __global__ __launch_bounds__(BPD_THREADS) void bp_beam_direct_kernel(
     }
 }
 
-// source ranges per tile of reduce="max": enough workgroups for ~4 rounds over the chip
-int direct_split_count(const bpmf_bp_plan* pl, size_t N)
-{
-    const long long tiles = (long long)((N + BPD_TILE - 1) / BPD_TILE);
-    long long want = tiles >= 1024 ? 1 : (1024 + tiles - 1) / tiles;
-    return (int)std::max<long long>(1, std::min<long long>({want, (long long)pl->K, 256}));
-}
-
 int launch_beam_direct(const bpmf_bp_plan* pl, const float* U, size_t N, int oob, int reduce,
                        hipStream_t stream, float* beam, int32_t* arg, int n_split, long long split_stride,
                        float best0)
@@ -112,12 +105,12 @@ int launch_beam_direct(const bpmf_bp_plan* pl, const float* U, size_t N, int oob
     if (reduce == BPMF_BP_REDUCE_MAX) {
         grid.y = (unsigned)n_split;
     } else {
-        grid.y = (unsigned)std::min<size_t>(pl->K, 65535);
-        grid.z = (unsigned)((pl->K + grid.y - 1) / grid.y);
+        grid.y = (unsigned)std::min<size_t>(pl->shape.K, 65535);
+        grid.z = (unsigned)((pl->shape.K + grid.y - 1) / grid.y);
     }
 #define BPD_LAUNCH(OOB, RED)                                                                       \
     bp_beam_direct_kernel<OOB, RED><<<grid, dim3(BPD_THREADS), 0, stream>>>(                       \
-        U, (long long)N, pl->d_dhdr, pl->d_dfirst, pl->d_dterms, (int)pl->K, pl->id_offset, beam, arg, \
+        U, (long long)N, pl->d_dhdr, pl->d_dfirst, pl->d_dterms, (int)pl->shape.K, pl->shape.id_offset, beam, arg, \
         split_stride, best0)
     if (oob == BPMF_BP_STRICT) {
         if (reduce == BPMF_BP_REDUCE_MAX) BPD_LAUNCH(BPMF_BP_STRICT, BPMF_BP_REDUCE_MAX);

@@ -1,10 +1,12 @@
-// Shared between bp.hip (plan builder, generic beam kernels, C ABI) and bp_fast.hip (the
-// interior-tile production kernel): device-side plan records and the host-side plan object.
+// Shared between bp_plan.hip (host-only planner and run schedule), bp.hip (generic beam kernels, upload, C ABI)
+// and bp_fast.hip (the interior-tile production kernel): device-side plan records, the host-side result of
+// planning, the schedule of a run and the plan object.
 #pragma once
 #include "common.h"
 #include "../../include/bpmf_hip.h"
 
 #include <mutex>
+#include <vector>
 
 namespace bpmf {
 
@@ -65,42 +67,149 @@ struct BpFastClass {
 };
 constexpr int BPF_MAX_CLASSES = 3;
 
+// one entry of the per-term table of bp_beam_wps_kernel (bp.hip)
+struct BpTermV {
+    int off_bytes;  // LDS byte offset of the term's window origin (+ moveout)
+    float beta;     // source weight of the term's station
+};
+
+constexpr int BPD_TILE = 1024;     // samples per workgroup of bp_direct.hip
+
+// ---- what bp_plan_host decides (bp_plan.hip: no HIP call, no device) ----
+// The scalar part of a plan: everything the schedule of a run (bp_schedule) and the diagnostics read.
+struct BpClassShape {
+    int tile = 0;                // 512 / 256 / 128 time samples per workgroup
+    bool halves = false;         // groups computed in 2-4 LDS residencies
+    int n_pass = 1;              // halves: consecutive group entries per group of sources
+    int n_groups = 0;            // group entries
+    size_t lds_bytes = 0;
+    size_t n_sources = 0;
+    int max_stations = 0;
+};
+// why a grid has no LDS plan (in this order of precedence)
+enum BpDirectReason { BP_LDS_PLAN = 0, BP_DIRECT_WINDOWS = 1 /* one source's windows exceed the LDS */,
+                      BP_DIRECT_TERMS = 2 /* > 256 terms per source */, BP_DIRECT_OPTION = 3 /* bp.direct */,
+                      BP_DIRECT_UPPER_ONLY = 4 /* bp.compat_strict_upper_only and a negative used moveout */ };
+struct BpPlanShape {
+    size_t K = 0, S = 0, P = 0;
+    int tpt = 2;           // time samples per thread -> tile = BP_THREADS * tpt
+    int NT = 4;            // padded number of (station, phase) terms per source
+    int nsv = 0;           // > 0: packed per-station records (P == 2), NSV stations padded
+    int ntv = 0;           // > 0: per-term table of NTV padded terms (tile 512 without packed records)
+    bool dual = false;     // dual (shifted) windows: every term offset is even
+    int n_groups = 0;
+    size_t lds_bytes = 0;  // largest group
+    // no LDS plan exists for this grid: bp_direct.hip gathers from global memory along compact per-source term lists
+    bool direct = false;
+    int direct_reason = BP_LDS_PLAN;
+    // interior-tile fast path: 1-3 station-count classes of sources, each with its own tile
+    bool fast = false;
+    bool fast_shares_generic = false;  // the single class was built from the generic (dual) plan: the
+                                       // edge tiles run the 8-byte-gather flavour of the generic kernel
+    int n_classes = 0;
+    BpClassShape cls[BPF_MAX_CLASSES];
+    int tmin_all = 0, tmax_all = 0;    // extreme used moveouts over all sources
+    int id_offset = 0;
+};
+
+struct PlanHost {               // the LDS plan of the general kernels, or of one station-count class
+    std::vector<BpGroup> groups;
+    std::vector<BpChunk> chunks;
+    std::vector<BpSource> srcs;   // in processing order
+    std::vector<int> off;
+    std::vector<float> beta;
+    size_t lds_floats = 0;
+    int NT = 4;
+    int n_pass = 1;             // > 1: every group is n_pass consecutive entries of `groups` (LDS residencies)
+    int per = 0;                // n_pass > 1: weighted stations of a source per residency
+    int slots = 0;              // n_pass > 1: sources per wave of a group (6, or 9 when every weight is uniform)
+};
+// interior-tile fast path: host-side tables of one station-count class (bp_fast.hip)
+struct FastHost {
+    std::vector<BpFastGroup> fg;
+    std::vector<BpRun> fr;
+    std::vector<BpWindow> fw;
+    std::vector<int> rec;
+    bool uniform = true;
+    int rec_dw = 0, max_sta = 0;
+    size_t n_sources = 0;
+};
+struct ClassHost {
+    PlanHost ph;
+    FastHost fh;
+    int tile = 0;
+    bool halves = false;
+};
+// Everything decided for one moveout table: the shape and the host tables that bp_plan_upload (bp.hip) copies
+// to the device as they are.
+struct BpPlanHost {
+    BpPlanShape shape;
+    std::vector<ClassHost> classes;     // the classes built (uploaded when shape.fast)
+    PlanHost own;                       // the general kernels' own single-window plan ...
+    bool general_is_class0 = false;     // ... unless class 0 doubles as their plan (dual windows)
+    const PlanHost& general() const { return general_is_class0 ? classes[0].ph : own; }
+    std::vector<int4> recs, hdr2;       // shape.nsv: packed per-station records [K, nsv/2], headers [K]
+    std::vector<BpTermV> termsv;        // shape.ntv: [K, ntv]
+    // shape.direct: {any station used, tmin, tmax, -} [K], first term of every source [K + 1],
+    // {row, moveout, weight bits, -}: stations ascending, phases inside
+    std::vector<int4> dhdr;
+    std::vector<long long> dfirst;
+    std::vector<int4> dterms;
+};
+// null, or why these arguments make no plan
+const char* bp_plan_refusal(const int32_t* moveouts, const float* w_sources, size_t K, size_t S, size_t P);
+BpPlanHost bp_plan_host(const int32_t* moveouts, const float* w_sources, size_t K, size_t S, size_t P,
+                        int32_t source_id_offset);
+
+// ---- the schedule of one run: which path, which kernel, how many partial rows and where they lie ----
+enum BpPath { BP_PATH_DIRECT = 0, BP_PATH_INTERIOR = 1 /* interior classes + edge tiles */, BP_PATH_GENERAL = 2 };
+enum BpFamily { BP_FAMILY_NONE = 0 /* direct plan */, BP_FAMILY_WPS2 = 1, BP_FAMILY_WPS = 2, BP_FAMILY_READLANE = 3 };
+// the general kernel of a plan (dispatch_beam of bp.hip instantiates exactly these)
+struct BpKernel {
+    int family = BP_FAMILY_NONE;
+    int wpb = 0, nsv = 0, b64 = 0;      // wps2: waves per workgroup, padded stations, 8-byte gathers
+    int ntv = 0;                        // wps: padded terms
+    int tpt = 0, nblk = 0;              // readlane: samples per thread, blocks of 64 terms
+    int tile = 0;                       // samples per workgroup
+    size_t lds_bytes = 0;               // dynamic LDS of the launch
+    int waves_per_cu = 0, gather_bytes = 0;
+};
+struct BpSchedule {
+    int path = BP_PATH_GENERAL;
+    BpKernel kernel;
+    int n_split = 1;                    // group (direct: source) ranges per tile; interior: of every class kernel
+    int n_split_edge = 1;               // ... of the general kernel on the samples outside [lo_s, hi_s)
+    int rows = 1;                       // partial (beam, arg) rows per series that the launches write; > 1: merged
+    long long lo_s = 0, hi_s = 0;       // BP_PATH_INTERIOR: the samples of the class kernels (else empty)
+    // byte offsets in the workspace: prestack(s), partial beam rows, partial arg rows; bytes of all of it
+    size_t o_prestack = 0, o_pbeam = 0, o_parg = 0, total = 0;
+};
+BpKernel bp_general_kernel(const BpPlanShape& sh);
+// `forced_split` = option bp.split as the CALLER read it (once per call: the size check of the workspace and the
+// launches must see the same value even if another thread sets the option in between).
+// `n_events` = 0: one series as bpmf_bp_run_dev runs it; E >= 1: a batch of E series of reduce="max" as
+// bp_max_batch runs it (always the general or the direct kernel over every tile, partial rows per event).
+BpSchedule bp_schedule(const BpPlanShape& sh, size_t N, int reduce, int forced_split, size_t n_events);
+// source ranges per tile of reduce="max" on a plan without LDS windows
+int direct_split_count(const BpPlanShape& sh, size_t N);
+
 }  // namespace bpmf
 
 struct bpmf_bp_plan {
     int device = 0;
-    size_t K = 0, S = 0, P = 0;
-    int tpt = 2;           // time samples per thread -> tile = BP_THREADS * tpt
-    int chunk = 4;         // terms gathered side by side
-    int NT = 4;            // padded number of (station, phase) terms per source
-    int n_groups = 0;
-    size_t lds_bytes = 0;  // largest group
-    bool dual = false;     // dual (shifted) windows: every term offset is even
-    int id_offset = 0;
-    double mean_group = 0; // diagnostics
+    bpmf::BpPlanShape shape;
     bpmf::BpGroup* d_groups = nullptr;
     bpmf::BpChunk* d_chunks = nullptr;
     bpmf::BpSource* d_srcs = nullptr;
     int* d_off = nullptr;
     float* d_beta = nullptr;
-    int nsv = 0;                 // > 0: packed per-station records (P == 2), NSV stations padded
-    int4* d_recs = nullptr;      // [K, nsv/2]
+    int4* d_recs = nullptr;      // shape.nsv: [K, nsv/2]
     int4* d_hdr2 = nullptr;      // [K] headers with the station count in .w
-    int ntv = 0;                 // > 0: per-term table of NTV padded terms (tile 512 without packed records)
-    void* d_termsv = nullptr;    // [K, ntv] BpTermV (bp.hip)
-    // interior-tile fast path: 1-3 station-count classes of sources, each with its own tile
-    bool fast = false;
-    int n_classes = 0;
-    bpmf::BpFastClass cls[bpmf::BPF_MAX_CLASSES];
-    bool fast_shares_generic = false;  // the single class was built from the generic (dual) plan: the
-                                       // edge tiles run the 8-byte-gather flavour of the generic kernel
-    int tmin_all = 0, tmax_all = 0;   // extreme used moveouts over all sources
-    // no LDS plan exists for this grid (a source's windows exceed the LDS, or > 256 terms per source):
-    // bp_direct.hip gathers from global memory along compact per-source term lists
-    bool direct = false;
-    int4* d_dhdr = nullptr;            // [K] {any station used, tmin, tmax, -}
-    long long* d_dfirst = nullptr;     // [K + 1] first term of every source
-    int4* d_dterms = nullptr;          // {row, moveout, weight bits, -}: stations ascending, phases inside
+    bpmf::BpTermV* d_termsv = nullptr;    // shape.ntv: [K, ntv]
+    bpmf::BpFastClass cls[bpmf::BPF_MAX_CLASSES];      // shape.fast: the device tables of shape.cls
+    int4* d_dhdr = nullptr;            // shape.direct: BpPlanHost::dhdr, dfirst, dterms
+    long long* d_dfirst = nullptr;
+    int4* d_dterms = nullptr;
     // the few edge tiles of a day run the general kernel on a side stream, beside the interior
     // kernel (fork / join through the two events): a serial launch of 3-6 workgroups would add the
     // full duration of one tile (5 ms at cfg3) to every call.  A plan serves one call at a time.
@@ -121,12 +230,11 @@ namespace bpmf {
 int bp_run_host(const float* features, const int32_t* moveouts, const float* w_phases, const float* w_sources,
                 size_t N, size_t K, size_t S, size_t C, size_t P, int out_of_bounds, int reduce, int device,
                 float* beam_out, int32_t* arg_out, bool defer_finish);
-// bp.hip: reduce="max" of a batch of E short series (bp_relocate.hip): prestacks S P N floats apart in U, results N
-// elements apart in beam / arg, partial rows of the group-range split in d_part (bp_max_batch_part_bytes);
-// `forced_split` = option bp.split as the caller read it
-size_t bp_max_batch_part_bytes(const bpmf_bp_plan* pl, size_t N, size_t E, int forced_split);
-int bp_max_batch(const bpmf_bp_plan* pl, const float* U, size_t N, size_t E, int out_of_bounds, int forced_split,
-                 void* d_part, hipStream_t stream, float* beam, int32_t* arg);
+// bp.hip: reduce="max" of a batch of E short series (bp_relocate.hip) under sch = bp_schedule(shape, N, max, bp.split,
+// E): prestacks S P N floats apart from d_workspace on, the partial rows of the split where sch says, results N
+// elements apart in beam / arg
+int bp_max_batch(const bpmf_bp_plan* pl, const BpSchedule& sch, void* d_workspace, size_t N, size_t E,
+                 int out_of_bounds, hipStream_t stream, float* beam, int32_t* arg);
 // bp_fast.hip: running (max, arg-max) over the sources of one class for its tiles [tile_lo, tile_hi)
 // (units of fc.tile samples), every one of which lies inside [-tmin_all, N - tmax_all) (no bounds
 // test per source).
@@ -134,7 +242,6 @@ int launch_beam_fast(const BpFastClass& fc, int id_offset, const float* U, size_
                      long long tile_hi, hipStream_t stream, float* beam, int32_t* arg,
                      int n_split = 1, long long split_stride = 0, float best0 = 0.0f);
 // bp_direct.hip: the whole series for a plan without LDS windows (pl->direct)
-int direct_split_count(const bpmf_bp_plan* pl, size_t N);
 int launch_beam_direct(const bpmf_bp_plan* pl, const float* U, size_t N, int oob, int reduce,
                        hipStream_t stream, float* beam, int32_t* arg, int n_split, long long split_stride,
                        float best0);

@@ -185,13 +185,14 @@ __global__ __launch_bounds__(1024) void bp_likelihood_kernel(const float* __rest
 
 namespace {
 struct RelocateLayout {
-    size_t o_part, o_beam, o_arg, total;
+    BpSchedule sch;         // prestacks and partial rows of the max-beams (bp_max_batch)
+    size_t o_beam, o_arg, total;
 };
 RelocateLayout relocate_layout(const bpmf_bp_plan* pl, size_t E, size_t N, int forced_split)
 {
     RelocateLayout l;
-    l.o_part = align_up(E * pl->S * pl->P * N * sizeof(float), 256);
-    l.o_beam = l.o_part + bp_max_batch_part_bytes(pl, N, E, forced_split);
+    l.sch = bp_schedule(pl->shape, N, BPMF_BP_REDUCE_MAX, forced_split, E);
+    l.o_beam = l.sch.total;
     l.o_arg = l.o_beam + align_up(E * N * sizeof(float), 256);
     l.total = l.o_arg + align_up(E * N * sizeof(int32_t), 256);
     return l;
@@ -231,7 +232,7 @@ extern "C" int bpmf_bp_relocate_batch_dev(const bpmf_bp_plan* pl, const float* d
     }
     if (E == 0) return 0;
     if (N == 0 || C == 0 || N > 0x7fffffffull || C > 0x7fffffffull || E > 65535 || row_stride < N ||
-        row_stride > 0x7fffffffffffull || pl->S * pl->P > 65535) {
+        row_stride > 0x7fffffffffffull || pl->shape.S * pl->shape.P > 65535) {
         set_error("bpmf_bp_relocate_batch_dev: bad argument (E=%zu N=%zu C=%zu row_stride=%zu; at most 65535 events "
                   "per call)", E, N, C, row_stride);
         return -1;
@@ -250,7 +251,7 @@ extern "C" int bpmf_bp_relocate_batch_dev(const bpmf_bp_plan* pl, const float* d
         set_error("bpmf_bp_relocate_batch_dev: workspace too small (%zu < %zu)", workspace_bytes, l.total);
         return -1;
     }
-    const int S = (int)pl->S, P = (int)pl->P, K = (int)pl->K;
+    const int S = (int)pl->shape.S, P = (int)pl->shape.P, K = (int)pl->shape.K;
     float* U = (float*)d_workspace;
     float* beam = spatial ? (float*)((char*)d_workspace + l.o_beam) : d_maxbeam;
     int32_t* arg = spatial ? (int32_t*)((char*)d_workspace + l.o_arg) : d_maxbeam_sources;
@@ -277,7 +278,7 @@ extern "C" int bpmf_bp_relocate_batch_dev(const bpmf_bp_plan* pl, const float* d
             d_features, event_stride, (long long)row_stride, (const long long*)d_starts, d_w_phases, (long long)N,
             (int)C, P, U);
     BPMF_LAUNCH_CHECK();
-    if (int rc = bp_max_batch(pl, U, N, E, out_of_bounds, forced_split, (char*)d_workspace + l.o_part, stream, beam, arg))
+    if (int rc = bp_max_batch(pl, l.sch, d_workspace, N, E, out_of_bounds, stream, beam, arg))
         return rc;
     if (spatial)
         bp_focus_kernel<true><<<dim3((unsigned)E), dim3(256), 0, stream>>>(beam, arg, (int)N, d_time_idx, d_src_idx, d_max_beam);

@@ -450,7 +450,7 @@ extern "C" int bpmf_bp_location_uncertainty_dev(const bpmf_bp_plan* pl, int meth
         return -1;
     }
     if (E == 0) return 0;
-    const size_t K = pl->K, n_terms = spatial ? K : N;
+    const size_t K = pl->shape.K, n_terms = spatial ? K : N;
     if (E > 65535 || K == 0 || K > 0x7fff0000ull || n_terms == 0 || n_terms > 0x7fff0000ull) {
         set_error("%s: bad argument (E=%zu K=%zu N=%zu; at most 65535 events per call)", me, E, K, N);
         return -1;
@@ -481,7 +481,7 @@ extern "C" int bpmf_bp_location_uncertainty_dev(const bpmf_bp_plan* pl, int meth
     int* cnt = (int*)((char*)d_workspace + l.o_cnt);
     int* base = (int*)((char*)d_workspace + l.o_base);
     float* cw = (float*)((char*)d_workspace + l.o_cw);
-    const UncTables T{d_tables, (int)K, pl->id_offset};
+    const UncTables T{d_tables, (int)K, pl->shape.id_offset};
     const dim3 grid(nb, (unsigned)E), wg(UNC_THREADS);
     const int nt = (int)n_terms;
     if (spatial)

@@ -350,6 +350,58 @@ def test_bp_plan_info_and_gather_width(oracle_lib, dual, S, S_used, gather, wave
     bf.close()
 
 
+def _launch_info_table(kind):
+    """Small (K = 48) tables of the plans the host-only planner distinguishes; `kind` -> (P, S, weighted stations)."""
+    P, S, used = {"sta16": (2, 18, [16, 9, 12]), "mix": (2, 44, [10, 20, 40]), "readlane": (3, 70, [45, 30, 38]),
+                  "direct": (3, 90, [90, 60, 75])}[kind]
+    rng = np.random.default_rng(len(kind) + S)
+    K = 48
+    tau = rng.integers(0, 20, (K, S, P)).astype(np.int32)
+    ws = np.zeros((K, S), np.float32)
+    for k in range(K):
+        ws[k, rng.choice(S, used[k % 3], replace=False)] = 1.0 + 0.5 * (k % 2)
+    return tau, ws, P, S
+
+
+@pytest.mark.parametrize("kind,family", [("sta16", "wps2"), ("mix", "readlane"), ("readlane", "readlane"), ("direct", None)])
+def test_bp_launch_info_is_the_plan_and_the_sizes_of_the_device_path(oracle_lib, kind, family):
+    """bpmf_bp_launch_info plans on the host alone; here the same tables go through bpmf_bp_plan_create, and the
+    plan on the device, its workspace and the workspace of a batch of 7 events must be what the info call said --
+    field for field.  (<= 16 stations: one shared class; 10 / 20 / 40 stations: three classes and a general plan of
+    80 terms; P = 3 with up to 45 of 70 stations, 135 terms: the readlane kernel in 4 blocks of 64 terms; P = 3 with
+    all 90 stations, 270 terms: no LDS plan.)"""
+    import torch
+    from seismic_bpmf_amd import BeamformerGPU, _lib
+    tau, ws, P, S = _launch_info_table(kind)
+    bf = BeamformerGPU(tau, ws)
+    plan_info = bf.plan_info()
+    rng = np.random.default_rng(3)
+    wp = np.ones((S, 3, P), np.float32)
+    for N in (700, 3000, 5000):
+        got = _lib.bp_launch_info(tau, ws, N)
+        print(kind, N, got["shape"]["direct"], got["schedule"])
+        assert got["plan_info"] == plan_info, (got["plan_info"], plan_info)
+        assert got["schedule"]["kernel"]["family"] == family and (got["shape"]["direct"] is not None) == (kind == "direct")
+        assert got["schedule"]["total"] == bf.lib.bpmf_bp_workspace_bytes(bf._plan, N, 3)
+        assert _lib.bp_launch_info(tau, ws, N, "none")["schedule"]["total"] == got["schedule"]["total"]
+        batch = _lib.bp_launch_info(tau, ws, N, "max", 7)["schedule"]
+        # (behind the partial rows: the (7, N) max-beam and arg-max rows of the spatial method, each padded to 256 bytes)
+        assert batch["total"] + 2 * ((7 * N * 4 + 255) // 256 * 256) == bf.relocation_workspace_bytes(7, N, 3)
+        if N == 3000:           # ... and the run along that schedule gives the oracle's result
+            f = rng.integers(0, 3, (S, 3, N)).astype(np.float32)
+            mb, ma = bf.run(torch.as_tensor(f), wp, "max", "strict")
+            ob, oa = oracle_lib.beamform(f, tau, wp, ws, "strict", "max")
+            _same(mb.cpu().numpy(), ob, f"{kind} maxbeam")
+            assert np.array_equal(ma.cpu().numpy(), oa)
+    if kind == "sta16":         # one class at tile 512, shared with the general kernels
+        assert got["shape"]["fast_shares_generic"] and got["schedule"]["kernel"]["b64"] and plan_info["class_tile"][0] == 512
+    if kind == "mix":
+        assert plan_info["n_classes"] == 3 and got["schedule"]["rows"] >= 3
+    if kind == "readlane":
+        assert got["schedule"]["kernel"]["nblk"] == 4 and got["schedule"]["kernel"]["tpt"] == 1
+    bf.close()
+
+
 def test_bp_huge_moveout_spread_falls_back_to_smaller_tiles(oracle_lib):
     """Moveouts spread over ~30 000 samples: windows only fit with the smallest tile."""
     rng = np.random.default_rng(7)

@@ -119,7 +119,8 @@ int bpmf_host_call_stats(double *out, int n);
  *     samples; a longer template runs the exact generic kernel, bit-identical to the oracle
  *     (tests/test_gpu_split16_anchor.py pins both sides); composes with the mf.compat_* switches; 1 leaves launches of fewer
  *     than 128 (template, 8192-lag block) pairs to the exact kernel (latency-bound there), 2 takes every launch; enlarges
- *     bpmf_mf_workspace_bytes and what a prepared day holds: set it before the day's first call)
+ *     bpmf_mf_workspace_bytes and what a prepared day holds: set it before the day's first call; does NOT apply to full
+ *     normalisation: a launch with BPMF_MF_NORMALIZE_FULL takes family 0, 1 or 2 whatever this option says)
  *   and the result-changing upstream-compatibility switches (off by default; every one has
  *   a variant of the CPU oracle and tools/diff_upstream.py tells which combination equals the real packages):
  *   mf.compat_exclusive_last_lag mf.compat_sqrt_norm mf.compat_range_all_channels mf.compat_sequential_csum
@@ -144,13 +145,40 @@ int bpmf_get_option(const char *name, long *value, long *default_value);
 /* flags of bpmf_mf_run_dev */
 #define BPMF_MF_DATA_PREPARED 1 /* workspace already holds this data's window energies */
 #define BPMF_MF_FORCE_DIRECT 2  /* use the generic (non-MFMA) kernel */
+/* Full normalisation (fast_matched_filter's normalize="full"): the window mean is removed, every per-channel value is
+ * the Pearson correlation
+ *   cc = sum (t - mean t)(x - mean x) / sqrt(sum (t - mean t)^2 * sum (x - mean x)^2),
+ * exactly +0 for a window of L equal samples (a zero- or constant-filled gap; every window when L = 1), for a flat
+ * template channel, and under the energy guard on the centred energies.  Lag ranges, weights, the network sum and
+ * network_sum == 0 are those of short mode.  A flag of bpmf_mf_run_dev, bpmf_mf_run, bpmf_mf_run_multi and
+ * bpmf_mf_launch_info.  The three main kernels are short mode's, run on a centred copy of the day and of the templates
+ * (csrc/mf_full.hip): the workspace is bpmf_mf_full_workspace_bytes, the per-day preparation
+ * bpmf_mf_prepare_data_full_dev.  BPMF_MF_DATA_PREPARED is accepted only on a workspace whose day was prepared for the
+ * same normalisation: with this flag on a day prepared by bpmf_mf_prepare_data_dev (or on another day), or without it on
+ * a day prepared by bpmf_mf_prepare_data_full_dev, the call fails with status -1.  Composes with
+ * mf.compat_exclusive_last_lag and mf.compat_range_all_channels; NOT defined under mf.compat_sqrt_norm or
+ * mf.compat_sequential_csum: every call with the flag then fails with status -1, bpmf_mf_launch_info included.
+ * Option mf.split16 does NOT apply: a launch with this flag takes family 0, 1 or 2 whatever that option says.
+ * The host-pointer calls upload the day whole before preparing it (the constant a channel is centred by is its mean
+ * over the whole day): mf.host_piece_lags has no effect there. */
+#define BPMF_MF_NORMALIZE_FULL 4
 
 size_t bpmf_mf_workspace_bytes(size_t L, size_t N, size_t T, size_t S, size_t C);
+/* The workspace of a call with BPMF_MF_NORMALIZE_FULL: the short-mode per-day arrays, then the centred day, a second
+ * prefix array and the flatness count (all per day, in front of everything that depends on T), then the per-batch
+ * arrays and the centred templates.  Independent of mf.split16. */
+size_t bpmf_mf_full_workspace_bytes(size_t L, size_t N, size_t T, size_t S, size_t C);
 
 /* Per-day, template-independent preparation (window energies of `data` for length L).
  * Implied by bpmf_mf_run_dev unless BPMF_MF_DATA_PREPARED is set. */
 int bpmf_mf_prepare_data_dev(const float *d_data, size_t L, size_t N, size_t S, size_t C,
                              void *d_workspace, size_t workspace_bytes, bpmf_stream_t stream);
+
+/* The same for BPMF_MF_NORMALIZE_FULL (a workspace of bpmf_mf_full_workspace_bytes): per channel the constant
+ * c = float32(float64 mean), d' = d - c, double prefix sums of d' and d'^2, the reciprocal norms of the centred window
+ * energies Q - P * P / L, +Inf for a window of L equal samples (decided from sample equality, not from the energy). */
+int bpmf_mf_prepare_data_full_dev(const float *d_data, size_t L, size_t N, size_t S, size_t C,
+                                  void *d_workspace, size_t workspace_bytes, bpmf_stream_t stream);
 
 int bpmf_mf_run_dev(const float *d_templates, const int32_t *d_moveouts,
                     const float *d_weights, const float *d_data, size_t step, size_t L,

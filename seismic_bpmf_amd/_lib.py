@@ -39,7 +39,9 @@ SIGNATURES = {
     "bpmf_device_memory_held": (C.c_int, [C.c_int, C.POINTER(_sz), C.POINTER(_sz)]),
     "bpmf_host_call_stats": (C.c_int, [C.POINTER(C.c_double), C.c_int]),
     "bpmf_mf_workspace_bytes": (_sz, [_sz, _sz, _sz, _sz, _sz]),
+    "bpmf_mf_full_workspace_bytes": (_sz, [_sz, _sz, _sz, _sz, _sz]),
     "bpmf_mf_prepare_data_dev": (C.c_int, [_vp, _sz, _sz, _sz, _sz, _vp, _sz, _vp]),
+    "bpmf_mf_prepare_data_full_dev": (C.c_int, [_vp, _sz, _sz, _sz, _sz, _vp, _sz, _vp]),
     "bpmf_mf_run_dev": (C.c_int, [_vp, _vp, _vp, _vp, _sz, _sz, _sz, _sz, _sz, _sz, _sz, C.c_int,
                                   C.c_int, _vp, _sz, _vp, _vp]),
     "bpmf_mf_launch_info": (C.c_int, [_sz, _sz, _sz, _sz, _sz, _sz, _sz, C.c_int, C.c_int, C.POINTER(C.c_int64)]),

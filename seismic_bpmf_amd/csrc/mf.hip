@@ -13,6 +13,7 @@
 #include "common.h"
 #include "context.h"
 #include "mf_split_api.h"
+#include "mf_full_api.h"
 #include <system_error>
 #include <thread>
 #include <chrono>
@@ -1167,6 +1168,40 @@ static MfWorkspace mf_carve(void* base, size_t L, size_t N, size_t T, size_t n_c
     return ws;
 }
 
+// The workspace of full normalisation (flag BPMF_MF_NORMALIZE_FULL, mf_full.hip): the per-day arrays of mf_carve --
+// `local` / `tot` / `off` hold the prefix sums of d'^2, `e_d` the reciprocal norms of the CENTRED window energies --, then
+// the per-day extras (d', the prefix sums of d', the flatness count), then everything that depends on T, closed by the
+// centred templates t'.  Option mf.split16 has no part in it.
+struct MfFullWorkspace {
+    MfWorkspace ws;
+    full::DayRegion day;
+    float* tprime;  // [T, n_ch, L]
+};
+
+static MfFullWorkspace mf_carve_full(void* base, size_t L, size_t N, size_t T, size_t n_ch)
+{
+    MfFullWorkspace f;
+    MfWorkspace& ws = f.ws;
+    const size_t nq = (N + CSUM_CHUNK - 1) / CSUM_CHUNK;
+    const size_t nwin = N >= L ? N - L + 1 : 0;
+    char* p = (char*)base;
+    size_t o = 0;
+    ws.local = (double*)(p + o); o += align_up(n_ch * N * sizeof(double), 256);
+    ws.tot = (double*)(p + o);   o += align_up(n_ch * nq * sizeof(double), 256);
+    ws.off = (double*)(p + o);   o += align_up(n_ch * nq * sizeof(double), 256);
+    o += 256;  // (the slack around the norms: mf_carve)
+    ws.e_d = (float*)(p + o);    o += align_up(n_ch * nwin * sizeof(float) + 64, 256);
+    ws.sp_day = nullptr;
+    ws.sp_batch = nullptr;
+    f.day = full::carve_day(p + o, N, n_ch); o += f.day.bytes;
+    ws.e_t = (float*)(p + o);    o += align_up(T * n_ch * sizeof(float), 256);
+    ws.range = (int2*)(p + o);   o += align_up(T * sizeof(int2), 256);
+    ws.chan_rec = (int4*)(p + o); o += align_up(T * (n_ch + 2) * sizeof(int4), 256);
+    f.tprime = (float*)(p + o);  o += full::batch_region_bytes(T, n_ch, L);
+    ws.bytes = o;
+    return f;
+}
+
 static int mf_check_sizes(size_t step, size_t L, size_t N, size_t T, size_t S, size_t C,
                           size_t n_corr)
 {
@@ -1199,28 +1234,63 @@ struct MfLaunch {
     bool first_piece = true;
 };
 
-// Which workspaces hold a day that was prepared WITH its fp16 split (option mf.split16): a caller of the *_dev entry
-// points that prepares a day with the option off and runs with it on (BPMF_MF_DATA_PREPARED) would otherwise correlate
-// whatever the split region holds.  Keyed by the workspace's base address; bpmf_mf_prepare_data_dev sets / clears it.
-static std::mutex g_split_days_mutex;
+// Which workspaces hold a day that was prepared in a way a later BPMF_MF_DATA_PREPARED call must be able to rely on, keyed
+// by the workspace's base address (the *_dev entry points keep no other state).  Two of them:
+//   g_split_days  days prepared WITH their fp16 split (option mf.split16): a caller that prepares a day with the option off
+//                 and runs with it on would otherwise correlate whatever the split region holds;
+//   g_full_days   days prepared by bpmf_mf_prepare_data_full_dev: the norm array holds the CENTRED window energies' norms,
+//                 the prefix sums are those of d'.  BPMF_MF_DATA_PREPARED with BPMF_MF_NORMALIZE_FULL on a workspace that
+//                 is not listed for this day, or without the flag on one that is listed, would correlate stale norms:
+//                 both fail.
+// Every per-day preparation sets / clears both.
 struct SplitDay { const void* data; size_t N, n_ch; };
-static std::vector<std::pair<const void*, SplitDay>> g_split_days;
+struct DayRegistry {
+    std::mutex mutex;
+    std::vector<std::pair<const void*, SplitDay>> days;
+    void note(const void* ws_base, const void* data, size_t N, size_t n_ch, bool listed)
+    {
+        std::lock_guard<std::mutex> g(mutex);
+        for (size_t i = 0; i < days.size(); ++i)
+            if (days[i].first == ws_base) { days.erase(days.begin() + i); break; }
+        if (listed) {
+            if (days.size() >= 64) days.erase(days.begin());
+            days.push_back({ws_base, {data, N, n_ch}});
+        }
+    }
+    // 0: this workspace is not listed; 1: listed for this day; -1: listed for another day
+    int known(const void* ws_base, const void* data, size_t N, size_t n_ch)
+    {
+        std::lock_guard<std::mutex> g(mutex);
+        for (auto& e : days)
+            if (e.first == ws_base) return e.second.data == data && e.second.N == N && e.second.n_ch == n_ch ? 1 : -1;
+        return 0;
+    }
+};
+static DayRegistry g_split_days, g_full_days;
 static void split_day_note(const void* ws_base, const void* data, size_t N, size_t n_ch, bool with_split)
 {
-    std::lock_guard<std::mutex> g(g_split_days_mutex);
-    for (size_t i = 0; i < g_split_days.size(); ++i)
-        if (g_split_days[i].first == ws_base) { g_split_days.erase(g_split_days.begin() + i); break; }
-    if (with_split) {
-        if (g_split_days.size() >= 64) g_split_days.erase(g_split_days.begin());
-        g_split_days.push_back({ws_base, {data, N, n_ch}});
-    }
+    g_split_days.note(ws_base, data, N, n_ch, with_split);
 }
 static bool split_day_known(const void* ws_base, const void* data, size_t N, size_t n_ch)
 {
-    std::lock_guard<std::mutex> g(g_split_days_mutex);
-    for (auto& e : g_split_days)
-        if (e.first == ws_base) return e.second.data == data && e.second.N == N && e.second.n_ch == n_ch;
-    return false;
+    return g_split_days.known(ws_base, data, N, n_ch) == 1;
+}
+static void full_day_note(const void* ws_base, const void* data, size_t N, size_t n_ch, bool is_full)
+{
+    g_full_days.note(ws_base, data, N, n_ch, is_full);
+}
+static int full_day_known(const void* ws_base, const void* data, size_t N, size_t n_ch)
+{
+    return g_full_days.known(ws_base, data, N, n_ch);
+}
+
+// Full normalisation is not defined under these two options (mf_direct_kernel<SQRT_NORM> recomputes E_d from the square
+// prefix sums itself; the sequential chain has no counterpart for the second prefix array)
+static const char* mf_full_refused_option()
+{
+    if (option(OPT_MF_COMPAT_SQRT_NORM) != 0) return "mf.compat_sqrt_norm";
+    if (option(OPT_MF_COMPAT_SEQUENTIAL_CSUM) != 0) return "mf.compat_sequential_csum";
+    return nullptr;
 }
 
 // ------------------------------------------------------------ choice of kernel ---
@@ -1279,7 +1349,8 @@ static MfVariant mf_choose(size_t step, size_t L, size_t N, size_t T, size_t n_c
     constexpr size_t SP_MIN_BLOCKS = 128;
     const size_t sp_blocks = (n_offsets + sp::LAGS_PER_WG - 1) / sp::LAGS_PER_WG;
     const bool sp_small = option(OPT_MF_SPLIT16) == 1 && T * sp_blocks < SP_MIN_BLOCKS;
-    if (option(OPT_MF_SPLIT16) != 0 && sp::usable(L, N) && !sp_small) {
+    // (full normalisation, BPMF_MF_NORMALIZE_FULL: the exact kernels, whatever mf.split16 says)
+    if (option(OPT_MF_SPLIT16) != 0 && sp::usable(L, N) && !sp_small && !(flags & BPMF_MF_NORMALIZE_FULL)) {
         v.family = MF_SPLIT16;
         v.lags_wg = sp::LAGS_PER_WG;
         v.grid = mf_grid(T, sp_blocks);
@@ -1336,6 +1407,11 @@ using namespace bpmf;
 extern "C" size_t bpmf_mf_workspace_bytes(size_t L, size_t N, size_t T, size_t S, size_t C)
 {
     return mf_carve(nullptr, L, N, T, S * C).bytes;
+}
+
+extern "C" size_t bpmf_mf_full_workspace_bytes(size_t L, size_t N, size_t T, size_t S, size_t C)
+{
+    return mf_carve_full(nullptr, L, N, T, S * C).ws.bytes;
 }
 
 // The per-day preparation for the samples [samp_lo, samp_hi) (multiples of CSUM_CHUNK, or the end of the
@@ -1404,8 +1480,32 @@ extern "C" int bpmf_mf_prepare_data_dev(const float* d_data, size_t L, size_t N,
     // option mf.split16: the day as fp16 (hi, lo) pairs, each channel scaled by a power of two (mf_split.h)
     const bool with_split = ws.sp_day && sp::usable(L, N);
     split_day_note(d_workspace, d_data, N, n_ch, with_split);
+    full_day_note(d_workspace, d_data, N, n_ch, false);
     if (with_split) return sp::prepare_day(d_data, N, n_ch, ws.sp_day, stream);
     return 0;
+}
+
+extern "C" int bpmf_mf_prepare_data_full_dev(const float* d_data, size_t L, size_t N, size_t S, size_t C,
+                                             void* d_workspace, size_t workspace_bytes, bpmf_stream_t stream_)
+{
+    hipStream_t stream = (hipStream_t)stream_;
+    const size_t n_ch = S * C;
+    if (!d_data || !d_workspace || N < L || L == 0 || n_ch == 0 || N > 0x7fffffffull) {
+        set_error("bpmf_mf_prepare_data_full_dev: bad argument");
+        return -1;
+    }
+    if (const char* opt = mf_full_refused_option()) {
+        set_error("bpmf_mf_prepare_data_full_dev: full normalisation is not defined under option %s", opt);
+        return -1;
+    }
+    const MfFullWorkspace f = mf_carve_full(d_workspace, L, N, 0, n_ch);
+    if (workspace_bytes < f.ws.bytes) {
+        set_error("bpmf_mf_prepare_data_full_dev: workspace too small (%zu < %zu)", workspace_bytes, f.ws.bytes);
+        return -1;
+    }
+    split_day_note(d_workspace, d_data, N, n_ch, false);
+    full_day_note(d_workspace, d_data, N, n_ch, true);
+    return full::prepare_day(d_data, L, N, n_ch, f.day, f.ws.local, f.ws.tot, f.ws.off, f.ws.e_d, stream);
 }
 
 namespace {
@@ -1434,14 +1534,36 @@ int mf_run_dev(const float* d_templates, const int32_t* d_moveouts, const float*
 {
     if (int rc = mf_check_sizes(step, L, N, T, S, C, n_corr)) return rc;
     const size_t n_ch = S * C;
-    MfWorkspace ws = mf_carve(d_workspace, L, N, T, n_ch);
+    const bool full_norm = (flags & BPMF_MF_NORMALIZE_FULL) != 0;
+    if (full_norm) {
+        if (const char* opt = mf_full_refused_option()) {
+            set_error("bpmf_mf_run_dev: full normalisation (BPMF_MF_NORMALIZE_FULL) is not defined under option %s", opt);
+            return -1;
+        }
+    }
+    const MfFullWorkspace fws = full_norm ? mf_carve_full(d_workspace, L, N, T, n_ch) : MfFullWorkspace();
+    const MfWorkspace ws = full_norm ? fws.ws : mf_carve(d_workspace, L, N, T, n_ch);
     if (workspace_bytes < ws.bytes) {
         set_error("bpmf_mf_run_dev: workspace too small (%zu < %zu)", workspace_bytes, ws.bytes);
         return -1;
     }
     if (!(flags & BPMF_MF_DATA_PREPARED)) {
-        if (int rc = bpmf_mf_prepare_data_dev(d_data, L, N, S, C, d_workspace, workspace_bytes, stream))
+        if (int rc = full_norm ? bpmf_mf_prepare_data_full_dev(d_data, L, N, S, C, d_workspace, workspace_bytes, stream)
+                               : bpmf_mf_prepare_data_dev(d_data, L, N, S, C, d_workspace, workspace_bytes, stream))
             return rc;
+    } else {
+        // the prepared day must be THIS day in THIS normalisation: never correlate stale norms
+        const int known = full_day_known(d_workspace, d_data, N, n_ch);
+        if (full_norm && known != 1) {
+            set_error("bpmf_mf_run_dev: BPMF_MF_NORMALIZE_FULL but the day in this workspace was prepared in short mode (or is "
+                      "another day): call bpmf_mf_prepare_data_full_dev again, or drop BPMF_MF_DATA_PREPARED");
+            return -1;
+        }
+        if (!full_norm && known != 0) {
+            set_error("bpmf_mf_run_dev: short normalisation but the day in this workspace was prepared by "
+                      "bpmf_mf_prepare_data_full_dev: call bpmf_mf_prepare_data_dev again, or drop BPMF_MF_DATA_PREPARED");
+            return -1;
+        }
     }
     const bool ranged = lc.off_hi >= 0;
     const MfVariant v = mf_choose(step, L, N, T, n_ch, n_corr, network_sum, flags, ranged);
@@ -1469,6 +1591,13 @@ int mf_run_dev(const float* d_templates, const int32_t* d_moveouts, const float*
     // (bit 0: mf.compat_exclusive_last_lag, bit 1: mf.compat_range_all_channels -- both only shape the valid lag range)
     const int exclusive_last = (option(OPT_MF_COMPAT_EXCLUSIVE_LAST_LAG) != 0 ? 1 : 0) |
                                (option(OPT_MF_COMPAT_RANGE_ALL_CHANNELS) != 0 ? 2 : 0);
+    if (full_norm) {
+        // full normalisation: everything below -- the prologue (fused or not) and the main kernel -- sees the centred
+        // templates and the centred day in place of the caller's
+        if (int rc = full::prepare_templates(d_templates, T * n_ch, L, fws.tprime, stream)) return rc;
+        d_templates = fws.tprime;
+        d_data = fws.day.dprime;
+    }
     if (v.prologue) {
         // template norms, lag ranges, channel records: one launch, one workgroup per template (also in front
         // of every later piece of a batch: the pieces of two batches alternate, and the records live in the
@@ -1565,6 +1694,12 @@ extern "C" int bpmf_mf_launch_info(size_t step, size_t L, size_t N, size_t T, si
         return -1;
     }
     if (int rc = mf_check_sizes(step, L, N, T, S, C, n_corr)) return rc;
+    if (flags & BPMF_MF_NORMALIZE_FULL) {
+        if (const char* opt = mf_full_refused_option()) {
+            set_error("bpmf_mf_launch_info: full normalisation (BPMF_MF_NORMALIZE_FULL) is not defined under option %s", opt);
+            return -1;
+        }
+    }
     const MfVariant v = mf_choose(step, L, N, T, S * C, n_corr, network_sum, flags, false);
     const int64_t fields[BPMF_MF_LAUNCH_INFO_FIELDS] = {
         v.family, v.maxr, v.maxt, v.ntile, v.fused, v.csplit, v.sqrt_norm, v.step1, v.prologue,
@@ -1617,6 +1752,13 @@ static int bpmf_mf_run_impl(const float* templates, const int32_t* moveouts, con
         return -1;
     }
     if (int rc = mf_check_sizes(step, L, N, T, S, C, n_corr)) return rc;
+    const bool full_norm = (flags & BPMF_MF_NORMALIZE_FULL) != 0;
+    if (full_norm) {
+        if (const char* opt = mf_full_refused_option()) {
+            set_error("bpmf_mf_run: full normalisation (BPMF_MF_NORMALIZE_FULL) is not defined under option %s", opt);
+            return -1;
+        }
+    }
     BPMF_BIND_DEVICE(device);
     t_call_stats = HostCallStats();
     const double t_call0 = host_now_ms();
@@ -1634,7 +1776,8 @@ static int bpmf_mf_run_impl(const float* templates, const int32_t* moveouts, con
     const size_t n_batch = bt.size() - 1;
     const size_t b_tp = T * n_ch * L * sizeof(float), b_mv = T * n_ch * sizeof(int32_t),
                  b_w = T * n_ch * sizeof(float), b_d = n_ch * N * sizeof(float),
-                 b_out = TB * row_bytes, b_ws = bpmf_mf_workspace_bytes(L, N, TB, S, C);
+                 b_out = TB * row_bytes,
+                 b_ws = full_norm ? bpmf_mf_full_workspace_bytes(L, N, TB, S, C) : bpmf_mf_workspace_bytes(L, N, TB, S, C);
     // streams, events, pinned pieces and the device working set are the device's (context.h): created
     // once, reused by every call, one call per device at a time -- nothing is created or destroyed here
     DeviceContext* ctx = device_context(device);
@@ -1685,9 +1828,10 @@ static int bpmf_mf_run_impl(const float* templates, const int32_t* moveouts, con
     }
     // option mf.host_piece_lags: samples of the first piece (default 131 072; the tests shrink it), 0 = off
     const size_t PIECE0 = align_up((size_t)option(OPT_MF_HOST_PIECE_LAGS), (size_t)MF_LAGS_PER_WG);
-    // (not under mf.split16: a channel's scale is its maximum over the WHOLE day)
+    // (not under mf.split16: a channel's scale is its maximum over the WHOLE day; not in full normalisation: so is the
+    // constant a channel is centred by)
     const bool pieces = !rc && !from_peer && use_mfma && option(OPT_MF_COMPAT_SEQUENTIAL_CSUM) == 0 &&
-                        option(OPT_MF_SPLIT16) == 0 && PIECE0 != 0 && N >= 8 * PIECE0;
+                        option(OPT_MF_SPLIT16) == 0 && !full_norm && PIECE0 != 0 && N >= 8 * PIECE0;
     auto launch_range = [&](size_t b, const MfLaunch& lc) {
         const size_t t0 = bt[b], nt = bt[b + 1] - bt[b];
         char* d_out = base + ((b & 1) ? o_out1 : o_out0);
@@ -1717,6 +1861,7 @@ static int bpmf_mf_run_impl(const float* templates, const int32_t* moveouts, con
         MF_TRY(hipEventRecord(ctx->ev_chunk[0], s_run), "event record");
         MF_TRY(hipStreamWaitEvent(s_copy, ctx->ev_chunk[0], 0), "wait event");
         const MfWorkspace wsd = mf_carve(base + o_ws, L, N, std::min(TB, T), n_ch);
+        full_day_note(base + o_ws, base + o_d, N, n_ch, false);     // (a short-mode day from here on, as bpmf_mf_prepare_data_dev notes it)
         size_t have = 0, piece = PIECE0;
         long long done[2] = {0, 0};
         int n_piece = 1;
@@ -1754,7 +1899,8 @@ static int bpmf_mf_run_impl(const float* templates, const int32_t* moveouts, con
             MF_TRY(hipStreamWaitEvent(s_run, ctx->ev_chunk[1], 0), "wait event");
         }
         if (!rc)
-            rc = bpmf_mf_prepare_data_dev((const float*)(base + o_d), L, N, S, C, base + o_ws, b_ws, s_run);
+            rc = full_norm ? bpmf_mf_prepare_data_full_dev((const float*)(base + o_d), L, N, S, C, base + o_ws, b_ws, s_run)
+                           : bpmf_mf_prepare_data_dev((const float*)(base + o_d), L, N, S, C, base + o_ws, b_ws, s_run);
     }
     auto launch = [&](size_t b) {
         if (b < n_streamed) return 0;                            // computed while the data arrived

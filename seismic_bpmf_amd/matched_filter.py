@@ -52,6 +52,8 @@ def require_gpu_arch(value, keyword):
 
 FLAG_DATA_PREPARED = 1
 FLAG_FORCE_DIRECT = 2
+FLAG_NORMALIZE_FULL = 4
+NORMALIZATIONS = ("short", "full")
 
 
 def n_corr_of(n_samples_data, n_samples_template, step):
@@ -130,8 +132,26 @@ def matched_filter(templates, moveouts, weights, data, step, arch="gpu", check_z
     """
     require_gpu_arch(arch, "arch")
     if normalize != "short":
-        raise NotImplementedError("only normalize='short' (no window-mean removal) is implemented; "
-                                  "it is the only mode the BPMF workflow uses")
+        raise NotImplementedError("this function serves normalize='short' (no window-mean removal), the only mode the "
+                                  "BPMF workflow uses; the full normalisation (window mean removed, the Pearson "
+                                  "correlation) is seismic_bpmf_amd.matched_filter_full")
+    return _matched_filter_host(templates, moveouts, weights, data, step, check_zeros, network_sum, device,
+                                FLAG_FORCE_DIRECT if force_direct else 0)
+
+
+def matched_filter_full(templates, moveouts, weights, data, step, arch="gpu", check_zeros="first",
+                        network_sum=True, device=None):
+    """:func:`matched_filter` with fast_matched_filter's ``normalize="full"``: the mean of every sliding window (and
+    of every template channel) is removed, each per-channel value is the Pearson correlation.  Exactly 0 where the
+    window is flat (a zero- or constant-filled gap), where the template channel is flat, and under the energy guard on
+    the centred energies.  Same arguments, layouts, lag ranges and multi-device behaviour; the same main kernels, run on
+    a centred copy of the day (flag BPMF_MF_NORMALIZE_FULL of include/bpmf_hip.h)."""
+    require_gpu_arch(arch, "arch")
+    return _matched_filter_host(templates, moveouts, weights, data, step, check_zeros, network_sum, device,
+                                FLAG_NORMALIZE_FULL)
+
+
+def _matched_filter_host(templates, moveouts, weights, data, step, check_zeros, network_sum, device, flags):
     step = int(step)
     if step < 1:
         raise ValueError("step must be a positive number of samples")
@@ -144,7 +164,6 @@ def matched_filter(templates, moveouts, weights, data, step, arch="gpu", check_z
     shape = (T, n_corr) if network_sum else (T, n_corr, S, Cc)
     out = np.empty(shape, dtype=np.float32)
     f, i = _lib._f, _lib._i
-    flags = FLAG_FORCE_DIRECT if force_direct else 0
     lib = _lib.lib()
 
     n_dev, dev_arr = _device_array(_device_list(device))
@@ -195,14 +214,18 @@ class MatchedFilterGPU:
             self._prepared_for = None
         return self._ws
 
-    def workspace_bytes(self, L, T):
+    def workspace_bytes(self, L, T, normalize="short"):
         S, Cc, N = self.data.shape
-        return self.lib.bpmf_mf_workspace_bytes(L, N, T, S, Cc)
+        size_of = self.lib.bpmf_mf_full_workspace_bytes if normalize == "full" else self.lib.bpmf_mf_workspace_bytes
+        return size_of(L, N, T, S, Cc)
 
     def run(self, templates, moveouts, weights, step=1, network_sum=True, out=None,
-            force_direct=False):
-        """CC of a batch of templates against the resident data.  Returns a device tensor."""
+            force_direct=False, normalize="short"):
+        """CC of a batch of templates against the resident data.  Returns a device tensor.  normalize="full": the
+        window mean removed (:func:`matched_filter_full`); the day is prepared again whenever the mode changes."""
         t = self.torch
+        if normalize not in NORMALIZATIONS:
+            raise ValueError(f"normalize must be one of {NORMALIZATIONS}, not {normalize!r}")
         if self.data is None:
             raise RuntimeError("call set_data() first")
         tp = self._dev(templates, t.float32)
@@ -218,13 +241,14 @@ class MatchedFilterGPU:
             out = t.empty(shape, dtype=t.float32, device=self.device)
         elif tuple(out.shape) != shape or out.dtype != t.float32 or not out.is_contiguous():
             raise ValueError(f"out must be a contiguous float32 tensor of shape {shape}")
-        nbytes = self.lib.bpmf_mf_workspace_bytes(L, N, T, S, Cc)
+        nbytes = (self.lib.bpmf_mf_full_workspace_bytes if normalize == "full" else self.lib.bpmf_mf_workspace_bytes)(
+            L, N, T, S, Cc)
         ws = self._workspace(nbytes)
-        flags = FLAG_FORCE_DIRECT if force_direct else 0
+        flags = (FLAG_FORCE_DIRECT if force_direct else 0) | (FLAG_NORMALIZE_FULL if normalize == "full" else 0)
         # (the prepared norm arrays hold energies under mf.compat_sqrt_norm, reciprocal norms otherwise; their
         # prefix sums are one chain under mf.compat_sequential_csum; under mf.split16 a prepared day also holds the
         # fp16 split of the data)
-        key = (self.data.data_ptr(), int(N), int(L), ws.data_ptr(), _lib.get_option("mf.compat_sqrt_norm")[0],
+        key = (self.data.data_ptr(), int(N), int(L), ws.data_ptr(), normalize, _lib.get_option("mf.compat_sqrt_norm")[0],
                _lib.get_option("mf.compat_sequential_csum")[0], _lib.get_option("mf.split16")[0])
         if self._prepared_for == key:
             flags |= FLAG_DATA_PREPARED

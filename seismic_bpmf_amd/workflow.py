@@ -310,8 +310,12 @@ def matched_filter_detections(templates, moveouts, weights, data, *, step=1, sr,
                               sanity_check=True, max_kurto=100.0, threshold_type="rms",
                               anomalous_cdf_at_mean_plus_1sig=0.0, window_for_validation_Tmax=100.0, min_freq_hz=None,
                               extract_peak_amplitudes=False, offset_win_peak_amp_sec=1.0,
-                              duration_win_peak_amp_sec=3.0, moveouts_peak_amp=None, data_norm=None):
+                              duration_win_peak_amp_sec=3.0, moveouts_peak_amp=None, data_norm=None,
+                              normalize="short"):
     """Matched-filter search of one day: returns ({template: cc indices}, cc device tensor).
+
+    `normalize`: "short" (the mode the reference uses) or "full" -- the window mean removed, for days whose windows are
+    not zero-mean (matched_filter_full); everything behind the CC matrix is the same.
 
     `extract_peak_amplitudes` (the reference's default, BPMF/similarity_search.py:733, 695-714; off here, so that
     the return value stays the pair): returns (detections, cc, amplitudes) with amplitudes = {row: (n_row, S, C)
@@ -339,7 +343,7 @@ def matched_filter_detections(templates, moveouts, weights, data, *, step=1, sr,
     weights = np.asarray(weights, dtype=np.float32)
     mf = MatchedFilterGPU(device=device)
     mf.set_data(data)
-    cc = mf.run(templates, moveouts, weights, step)
+    cc = mf.run(templates, moveouts, weights, step, normalize=normalize)
     out = cc_detections(cc, moveouts, weights, step=step, sr=sr, threshold_window_dur=threshold_window_dur,
                         minimum_interevent_time=minimum_interevent_time, n_dev=n_dev, overlap=overlap,
                         max_cc_threshold=max_cc_threshold, white_noise=white_noise, device=device,

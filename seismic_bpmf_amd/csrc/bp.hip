@@ -16,7 +16,8 @@
 //      (max, arg-max) per time sample: no atomics, no cross-workgroup merge, and the
 //      sequential source order gives the "lowest index wins ties" rule for free.
 #include "bp_plan.h"
-#include "context.h"
+#include "bp_plan_cache.h"
+#include "host_call.h"
 #include <mutex>
 #include <cstring>
 #include <type_traits>
@@ -1418,273 +1419,99 @@ extern "C" int bpmf_bp_run_dev(const bpmf_bp_plan* pl, const float* d_features,
 }
 
 namespace {
-// Plans kept by the host-pointer entry point, keyed by (device, shapes, both tables).  A hit
-// compares the tables themselves (host copies are kept while they are small; above 1 GiB a
-// second, independent 64-bit hash stands in).  One slot per visible device and one spare each, so
-// that a process driving every GPU of a node keeps all of its plans from one day to the next.
-struct PlanCacheEntry {
-    uint64_t key = 0, key2 = 0;
-    size_t K = 0, S = 0, P = 0;
-    int device = 0;
-    std::vector<int32_t> mv;    // empty: table too large to keep, (key, key2) decide
-    std::vector<float> ws;
-    bpmf_bp_plan* pl = nullptr;
-    uint64_t stamp = 0;         // last use (eviction = least recently used)
-};
-std::vector<PlanCacheEntry> g_plan_cache;
-uint64_t g_plan_cache_clock = 0;
-std::mutex g_plan_cache_mutex;
-constexpr size_t PLAN_KEEP_BYTES = (size_t)1 << 30;
-// 64-bit multiply-xorshift over the bytes of a table, 8 at a time (not cryptographic: a cache key)
-uint64_t hash_words(const void* p, size_t bytes, uint64_t seed)
+// the plans bpmf_bp_run keeps (bp_plan_cache.h); never destroyed: at process exit the runtime may be gone already
+BpPlanCache& plan_cache()
 {
-    const unsigned char* b = (const unsigned char*)p;
-    uint64_t h = seed ^ (bytes * 0x9e3779b97f4a7c15ull);
-    size_t i = 0;
-    for (; i + 8 <= bytes; i += 8) {
-        uint64_t w;
-        memcpy(&w, b + i, 8);
-        h = (h ^ w) * 0xff51afd7ed558ccdull;
-        h ^= h >> 32;
-    }
-    uint64_t w = 0;
-    if (i < bytes) memcpy(&w, b + i, bytes - i);
-    h = (h ^ w) * 0xc4ceb9fe1a85ec53ull;
-    return h ^ (h >> 29);
+    static BpPlanCache* c = new BpPlanCache(
+        [](void* pl) { bpmf_bp_plan_destroy((bpmf_bp_plan*)pl); },
+        [] { int n = 0; return device_counts(&n, nullptr) == hipSuccess ? n : 0; });
+    return *c;
 }
-size_t plan_cache_capacity()
-{
-    int n = 0;
-    if (device_counts(&n, nullptr) != hipSuccess || n < 1) n = 1;
-    return (size_t)std::max(4, 2 * n);
-}
-}  // namespace
 
-static int bpmf_bp_run_impl(const float* features, const int32_t* moveouts, const float* w_phases,
-                           const float* w_sources, size_t N, size_t K, size_t S, size_t C, size_t P,
-                           int out_of_bounds, int reduce, int device, float* beam_out,
-                           int32_t* arg_out, bool defer_finish)
+// The day of features of a host-pointer call, uploaded IN PIECES on the copy stream while the kernels of the pieces
+// that have arrived run (bp_run_dev asks for the samples it is about to read) -- the upload of a whole day in front
+// of the first kernel cost cfg3 a third of its time (201.7 ms end to end against 150.6 resident, round-4 bench;
+// BPMF makes exactly this call, template_search.py:549-558).
+struct HostFeed : BpFeed {
+    HostCall& hc; DayFeed& day; const float* host; float* d_feat; const float* d_wp; float* U;
+    size_t N, C; int S, P; long long have = 0;
+    HostFeed(HostCall& hc_, DayFeed& day_, const float* host_, float* d_feat_, const float* d_wp_, float* U_, size_t N_,
+             size_t C_, size_t S_, size_t P_)
+        : hc(hc_), day(day_), host(host_), d_feat(d_feat_), d_wp(d_wp_), U(U_), N(N_), C(C_), S((int)S_), P((int)P_) {}
+    int need(long long samp_end, hipStream_t stream) override
+    {
+        samp_end = std::min<long long>((samp_end + 1023) / 1024 * 1024, (long long)N);
+        if (samp_end <= have) return 0;
+        day.arrive(d_feat, host, (size_t)S * C, N, (size_t)have, (size_t)samp_end, stream);
+        if (!hc.ok()) return hc.rc;
+        const int rc = launch_prestack(d_feat, d_wp, N, C, S, P, U, have, samp_end, stream);
+        if (have == 0) t_call_stats.first_kernel_ms = host_now_ms() - hc.t0;      // the first kernels follow
+        have = samp_end;
+        return rc;
+    }
+};
+
+int bp_run_call(const float* features, const int32_t* moveouts, const float* w_phases, const float* w_sources, size_t N,
+                size_t K, size_t S, size_t C, size_t P, int out_of_bounds, int reduce, int device, float* beam_out,
+                int32_t* arg_out, bool defer_finish, FanoutScope& fan)
 {
     if (!features || !moveouts || !w_phases || !w_sources || !beam_out) {
         set_error("bpmf_bp_run: null pointer");
         return -1;
     }
-    // Every call binds its thread to `device` first: the plan cache below may skip
-    // bpmf_bp_plan_create, and a fresh host thread starts on device 0.
-    BPMF_BIND_DEVICE(device);
-    t_call_stats = HostCallStats();
-    const double t_call0 = host_now_ms();
-    // One host-pointer call per device at a time, on the device's own streams and working set
-    // (context.h): nothing is created or destroyed per call, nothing runs on the null stream.
-    DeviceContext* ctx = device_context(device);
-    if (!ctx) return -2;
-    std::lock_guard<std::mutex> call_lock(ctx->call_mutex);
-    FanoutScope fan;      // (behind the lock: a source waits for its peers before another call may touch its data)
-    // BPMF calls beamform once per day with the same moveout table and source weights
-    // (template_search.py:549-558); building the plan costs 0.04 s for 50 000 sources but 3 s for a
-    // million, so the last plans are kept.
-    bpmf_bp_plan* pl = nullptr;
-    const size_t b_mv = K * S * P * sizeof(int32_t), b_wsrc = K * S * sizeof(float);
-    // (the plan generation is part of the key: a plan is built under the options of its creation,
-    // and bpmf_set_option must not leave a plan of the previous settings in use)
-    // (tables small enough to be kept are COMPARED on a hit: their keys only pre-select, and hash one 8-byte word
-    // in 64 -- 24 MB of hashing per cfg3 call were 4 ms of a 160 ms call; larger tables are hashed in full, twice)
-    const bool keep_tables = b_mv + b_wsrc <= PLAN_KEEP_BYTES;
-    auto table_hash = [&](const void* p, size_t bytes, uint64_t seed) -> uint64_t {
-        if (!keep_tables || bytes < 4096) return hash_words(p, bytes, seed);
-        uint64_t h = seed ^ bytes;
-        const unsigned char* b = (const unsigned char*)p;
-        for (size_t i = 0; i + 8 <= bytes; i += 512) {
-            uint64_t w8;
-            memcpy(&w8, b + i, 8);
-            h = (h ^ w8) * 0xff51afd7ed558ccdull;
-            h ^= h >> 32;
-        }
-        return h ^ hash_words(b + bytes - 64, 64, seed);
-    };
-    const uint64_t key = table_hash(moveouts, b_mv, 0x9e3779b97f4a7c15ull ^ (K * 31 + S * 7 + P)) ^
-                         table_hash(w_sources, b_wsrc, 0xc2b2ae3d27d4eb4full) ^
-                         (option_generation() * 0xd6e8feb86659fd93ull);
-    const uint64_t key2 = keep_tables ? key * 0x9e3779b97f4a7c15ull
-                                      : hash_words(moveouts, b_mv, 0x165667b19e3779f9ull) +
-                                        hash_words(w_sources, b_wsrc, 0x27d4eb2f165667c5ull);
-    {
-        std::lock_guard<std::mutex> g(g_plan_cache_mutex);
-        for (auto& e : g_plan_cache) {
-            if (!e.pl || e.key != key || e.key2 != key2 || e.K != K || e.S != S || e.P != P ||
-                e.device != device)
-                continue;
-            if (!e.mv.empty() && (memcmp(e.mv.data(), moveouts, b_mv) != 0 ||
-                                  memcmp(e.ws.data(), w_sources, b_wsrc) != 0))
-                continue;
-            pl = e.pl;
-            e.pl = nullptr;            // taken out while in use; put back below
-            e.stamp = ~0ull;           // ... into this very slot (marks it as reserved)
-            break;
-        }
-    }
+    HostCall hc("bpmf_bp_run", device, fan);
+    if (!hc.ok()) return hc.rc;
+    DeviceContext* ctx = hc.ctx;
+    BpPlanCache::Ticket ticket;
+    bpmf_bp_plan* pl = (bpmf_bp_plan*)plan_cache().take(device, K, S, P, moveouts, w_sources, option_generation(), &ticket);
     if (!pl)
         if (int rc = bpmf_bp_plan_create(moveouts, w_sources, K, S, P, device, 0, &pl)) return rc;
-    t_call_stats.plan_ms = host_now_ms() - t_call0;
-    auto release_plan = [&]() {
-        std::lock_guard<std::mutex> g(g_plan_cache_mutex);
-        const size_t cap = plan_cache_capacity();
-        PlanCacheEntry* slot = nullptr;
-        for (auto& e : g_plan_cache)   // the slot this plan came from still holds its tables
-            if (!e.pl && e.stamp == ~0ull && e.key == key && e.key2 == key2 && e.device == device &&
-                e.K == K && e.S == S && e.P == P) {
-                e.pl = pl;
-                e.stamp = ++g_plan_cache_clock;
-                return;
-            }
-        for (auto& e : g_plan_cache)
-            if (!e.pl && e.stamp != ~0ull) { slot = &e; break; }
-        if (!slot && g_plan_cache.size() < cap) {
-            g_plan_cache.emplace_back();
-            slot = &g_plan_cache.back();
-        }
-        if (!slot) {
-            // the least recently used plan OF THIS DEVICE goes (its calls are serialised by the
-            // context mutex this thread holds, so nobody can be about to take it); a cache filled
-            // by other devices' plans is left alone
-            for (auto& e : g_plan_cache)
-                if (e.pl && e.device == device && (!slot || e.stamp < slot->stamp)) slot = &e;
-            if (!slot) {
-                bpmf_bp_plan_destroy(pl);
-                return;
-            }
-            bpmf_bp_plan_destroy(slot->pl);
-        }
-        slot->key = key; slot->key2 = key2;
-        slot->K = K; slot->S = S; slot->P = P;
-        slot->device = device;
-        slot->pl = pl;
-        slot->stamp = ++g_plan_cache_clock;
-        if (keep_tables) {
-            slot->mv.assign(moveouts, moveouts + K * S * P);
-            slot->ws.assign(w_sources, w_sources + K * S);
-        } else {
-            slot->mv.clear(); slot->mv.shrink_to_fit();
-            slot->ws.clear(); slot->ws.shrink_to_fit();
-        }
-    };
+    t_call_stats.plan_ms = host_now_ms() - hc.t0;
+    hc.also_drain = pl->side_stream;
     const size_t b_f = S * C * N * sizeof(float), b_wp = S * C * P * sizeof(float),
                  b_ws = bpmf_bp_workspace_bytes(pl, N, C),
                  b_beam = (reduce == BPMF_BP_REDUCE_MAX ? N : K * N) * sizeof(float),
                  b_arg = N * sizeof(int32_t);
-    const size_t o_f = 0, o_wp = o_f + align_up(b_f, 256), o_ws = o_wp + align_up(b_wp, 256),
-                 o_beam = o_ws + align_up(b_ws, 256), o_arg = o_beam + align_up(b_beam, 256),
-                 total = o_arg + b_arg;
-    const double t_res0 = host_now_ms();
-    char* base = ctx->reserve_device(total);
-    if (!base || ctx->reserve_pinned(std::min<size_t>((size_t)64 << 20, std::max<size_t>(b_f, 4096)))) {
-        release_plan();
-        return -2;
-    }
-    t_call_stats.reserve_ms = host_now_ms() - t_res0;
-    int rc = 0;
+    const size_t o_f = hc.add(b_f), o_wp = hc.add(b_wp), o_ws = hc.add(b_ws), o_beam = hc.add(b_beam), o_arg = hc.add(b_arg);
     hipStream_t stream = ctx->s_run;
     hipError_t e = hipSuccess;
-    auto fail = [&](hipError_t err, const char* what) {
-        set_error("bpmf_bp_run: %s failed: %s", what, hipGetErrorString(err));
-        rc = -2;
-    };
-    // (pageable memory through the runtime's own staging, on the private stream: a hand-made pipeline through
-    // the context's pinned pieces filled by 8 host threads measured SLOWER -- cfg3 end to end 194 ms against
-    // 176 ms -- the host-side memcpy into the pinned pieces is the bottleneck on the 16 CPUs a box grants)
-    // The day of features.  A peer of a multi-device call copies it from the first device.  Everybody else
-    // uploads it from the host IN PIECES on the copy stream while the kernels of the pieces that have arrived
-    // run (HostFeed: bpmf_bp_run_dev asks for the samples it is about to read) -- the upload of a whole day
-    // in front of the first kernel cost cfg3 a third of its time (201.7 ms end to end against 150.6 resident,
-    // round-4 bench; BPMF makes exactly this call, template_search.py:549-558).  The pieces travel through the
-    // context's pinned buffers (staged_upload_rows, context.h).
-    struct HostFeed : BpFeed {
-        DeviceContext* ctx; FanoutScope* fan; const float* host; char* d_feat; const float* d_wp; float* U;
-        size_t N, C; int S, P; long long have = 0; int n_piece = 0; hipError_t err = hipSuccess; const char* what = "";
-        bool published = false;
-        double t_call0 = 0.0;
-        int need(long long samp_end, hipStream_t stream) override
-        {
-            samp_end = std::min<long long>((samp_end + 1023) / 1024 * 1024, (long long)N);
-            if (samp_end <= have) return 0;
-            const size_t rows = (size_t)S * C;
-            what = "H2D features";
-            // rows x [have, samp_end), through the context's pinned pieces (context.h: staged_upload_rows)
-            err = staged_upload_rows(ctx, (float*)d_feat, host, rows, N, (size_t)have, (size_t)samp_end, ctx->s_copy);
-            hipEvent_t ev = ctx->ev_chunk[n_piece++ % DeviceContext::CHUNK_EVENTS];
-            if (err == hipSuccess) { what = "event record"; err = hipEventRecord(ev, ctx->s_copy); }
-            if (err == hipSuccess) { what = "wait event"; err = hipStreamWaitEvent(stream, ev, 0); }
-            if (err == hipSuccess && samp_end == (long long)N && !published) {
-                published = true;               // the whole day is on its way: the other devices may copy it
-                what = "event record";
-                err = fanout_publish(*fan, ctx, d_feat, ctx->s_copy);
-            }
-            if (err != hipSuccess) {
-                set_error("bpmf_bp_run: %s failed: %s", what, hipGetErrorString(err));
-                return -2;
-            }
-            const int rc = launch_prestack((const float*)d_feat, d_wp, N, C, S, P, U, have, samp_end, stream);
-            if (have == 0) t_call_stats.first_kernel_ms = host_now_ms() - t_call0;      // the first kernels follow
-            have = samp_end;
-            return rc;
+    if (char* base = hc.reserve(std::min<size_t>((size_t)64 << 20, std::max<size_t>(b_f, 4096)))) {
+        // The day of features: a peer of a multi-device call copies it from the first device, everybody else feeds it
+        // from the host while the kernels run.  The weights go through the pinned pieces as well.
+        DayFeed day(hc, "H2D features");
+        const bool from_peer = day.from_peer(base + o_f, b_f, stream);
+        if (hc.ok() && (e = staged_upload_rows(ctx, (float*)(base + o_wp), w_phases, 1, b_wp / 4, 0, b_wp / 4, stream)) != hipSuccess)
+            hc.fail(e, "H2D weights_phases");
+        if (hc.ok() && reduce == BPMF_BP_REDUCE_NONE && (e = hipMemsetAsync(base + o_beam, 0, b_beam, stream)) != hipSuccess)
+            hc.fail(e, "memset");
+        if (hc.ok()) {
+            HostFeed host_feed(hc, day, features, (float*)(base + o_f), (const float*)(base + o_wp), (float*)(base + o_ws), N, C, S, P);
+            if (from_peer) t_call_stats.first_kernel_ms = host_now_ms() - hc.t0;
+            hc.note(bp_run_dev(pl, (const float*)(base + o_f), (const float*)(base + o_wp), N, C, out_of_bounds, reduce,
+                               base + o_ws, b_ws, stream, (float*)(base + o_beam), (int32_t*)(base + o_arg),
+                               from_peer ? nullptr : &host_feed, defer_finish));
         }
-    } host_feed;
-    bool from_peer = false;
-    {
-        const char* what = "";
-        from_peer = fanout_peer_copy(fan, ctx, base + o_f, b_f, stream, &e, &what);
-        if (from_peer && e != hipSuccess) fail(e, what);
+        // The results' way back, through the pinned pieces (staged_download: the runtime's pageable path page-locks a
+        // destination it has not seen before, and a result array is a new allocation on every call)
+        hc.wait_since = host_now_ms();
+        if (hc.ok() && (e = staged_download(ctx, beam_out, base + o_beam, b_beam, stream)) != hipSuccess) hc.fail(e, "D2H beam");
+        if (hc.ok() && reduce == BPMF_BP_REDUCE_MAX && arg_out &&
+            (e = staged_download(ctx, arg_out, base + o_arg, b_arg, stream)) != hipSuccess) hc.fail(e, "D2H argmax");
     }
-    if (!rc && (e = staged_upload_rows(ctx, (float*)(base + o_wp), w_phases, 1, b_wp / 4, 0, b_wp / 4, stream)) != hipSuccess) fail(e, "H2D weights_phases");
-    if (!rc && reduce == BPMF_BP_REDUCE_NONE &&
-        (e = hipMemsetAsync(base + o_beam, 0, b_beam, stream)) != hipSuccess) fail(e, "memset");
-    if (!rc) {
-        host_feed.ctx = ctx; host_feed.fan = &fan; host_feed.host = features; host_feed.d_feat = base + o_f;
-        host_feed.d_wp = (const float*)(base + o_wp); host_feed.U = (float*)(base + o_ws);
-        host_feed.N = N; host_feed.C = C; host_feed.S = (int)S; host_feed.P = (int)P; host_feed.t_call0 = t_call0;
-        if (from_peer) t_call_stats.first_kernel_ms = host_now_ms() - t_call0;
-        rc = bp_run_dev(pl, (const float*)(base + o_f), (const float*)(base + o_wp), N, C, out_of_bounds, reduce,
-                        base + o_ws, b_ws, stream, (float*)(base + o_beam), (int32_t*)(base + o_arg),
-                        from_peer ? nullptr : &host_feed, defer_finish);
-    }
-    // The results' way back, through the pinned pieces (staged_download: the runtime's pageable path page-locks a
-    // destination it has not seen before, and a result array is a new allocation on every call)
-    const double t_enqueued = host_now_ms();
-    if (!rc && (e = staged_download(ctx, beam_out, base + o_beam, b_beam, stream)) != hipSuccess) fail(e, "D2H beam");
-    if (!rc && reduce == BPMF_BP_REDUCE_MAX && arg_out &&
-        (e = staged_download(ctx, arg_out, base + o_arg, b_arg, stream)) != hipSuccess) fail(e, "D2H argmax");
-    // (always drained, also after a failure: the working set and the plan go back to their caches)
-    hipError_t es = hipStreamSynchronize(stream);
-    (void)hipStreamSynchronize(ctx->s_copy);
-    if (pl->side_stream) (void)hipStreamSynchronize(pl->side_stream);
-    t_call_stats.device_wait_ms = host_now_ms() - t_enqueued;
-    t_call_stats.total_ms = host_now_ms() - t_call0;
-    if (!rc && es != hipSuccess) fail(es, "synchronize");
-    release_plan();
-    copy_pool_quiesce();  // no host thread of the copy pool still reads the caller's arrays (a straggler of an idempotent fill) when the call returns
-    fan.finish();         // a source's peers are through with its copy of the day before the working set may go
-    ctx->trim_after_call();
-    return rc;
+    hc.finish();        // (the plan's streams are drained: it may go back to the cache, or be destroyed)
+    plan_cache().give_back(ticket, pl, moveouts, w_sources);
+    return hc.rc;
 }
+}  // namespace
 
 int bpmf::bp_run_host(const float* features, const int32_t* moveouts, const float* w_phases,
                       const float* w_sources, size_t N, size_t K, size_t S, size_t C, size_t P, int out_of_bounds,
-                      int reduce, int device, float* beam_out, int32_t* arg_out, bool defer_finish)
+                      int reduce, int device, float* beam_out, int32_t* arg_out, bool defer_finish, FanoutScope& fan)
 {
-    // nothing may cross the C boundary as an exception (std::bad_alloc from the host-side planning, a
-    // std::system_error): it becomes status -3 with its text
-    try {
-        return bpmf_bp_run_impl(features, moveouts, w_phases, w_sources, N, K, S, C, P, out_of_bounds, reduce, device,
-                                beam_out, arg_out, defer_finish);
-    } catch (const std::exception& e) {
-        copy_pool_quiesce();      // (no pool thread may still read the caller's arrays)
-        set_error("bpmf_bp_run: exception: %s", e.what());
-        return -3;
-    } catch (...) {
-        copy_pool_quiesce();
-        set_error("bpmf_bp_run: unknown exception");
-        return -3;
-    }
+    return guarded("bpmf_bp_run", [&] {
+        return bp_run_call(features, moveouts, w_phases, w_sources, N, K, S, C, P, out_of_bounds, reduce, device,
+                           beam_out, arg_out, defer_finish, fan);
+    });
 }
 
 extern "C" int bpmf_bp_run(const float* features, const int32_t* moveouts, const float* w_phases,
@@ -1692,8 +1519,9 @@ extern "C" int bpmf_bp_run(const float* features, const int32_t* moveouts, const
                            int out_of_bounds, int reduce, int device, float* beam_out,
                            int32_t* arg_out)
 {
+    FanoutScope nobody;
     return bp_run_host(features, moveouts, w_phases, w_sources, N, K, S, C, P, out_of_bounds, reduce, device,
-                       beam_out, arg_out, false);
+                       beam_out, arg_out, false, nobody);
 }
 
 extern "C" int bpmf_bp_pack_max_dev(const float* d_beam, const int32_t* d_arg, size_t N,

@@ -224,12 +224,6 @@ struct bpmf_bp_plan {
 };
 
 namespace bpmf {
-// bp.hip: bpmf_bp_run, and with `defer_finish` one device's share of bpmf_bp_run_multi under option
-// bp.compat_first_computed -- the share keeps -inf where it computed no beam, and the host finishes
-// (0, first id) after the merge of all shares (a finished share could not be told from a real 0)
-int bp_run_host(const float* features, const int32_t* moveouts, const float* w_phases, const float* w_sources,
-                size_t N, size_t K, size_t S, size_t C, size_t P, int out_of_bounds, int reduce, int device,
-                float* beam_out, int32_t* arg_out, bool defer_finish);
 // bp.hip: reduce="max" of a batch of E short series (bp_relocate.hip) under sch = bp_schedule(shape, N, max, bp.split,
 // E): prestacks S P N floats apart from d_workspace on, the partial rows of the split where sch says, results N
 // elements apart in beam / arg

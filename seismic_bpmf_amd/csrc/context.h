@@ -60,7 +60,7 @@ struct DeviceContext {
     int reserve_pinned(size_t bytes);
     // Frees the device working set and the pinned pieces (the streams and events stay).
     void release_memory();
-    // End of a host-pointer call (its streams drained, call_mutex held): option host.cache_limit_mb -- a working
+    // End of a host-pointer call (HostCall::finish: its streams drained, call_mutex held): option host.cache_limit_mb -- a working
     // set above the limit goes back to the allocator right away (a workflow that makes ONE large host-pointer call
     // and then runs on torch-allocated tensors would otherwise strand it outside torch's allocator).
     void trim_after_call();
@@ -138,21 +138,17 @@ private:
     bool published = false, failed = false;
     int pending;
 };
-// the hand-over the calling thread's NEXT host-pointer call takes part in (set by *_run_multi around the
-// first block of every distinct device; nullptr otherwise) and its role in it
-extern thread_local DataFanout* t_fanout;
-extern thread_local int t_fanout_role;
-// RAII of a participant: whatever happens inside the call, the source cancels an unpublished hand-over
-// and waits for its peers, a peer reports that it is through
+// A participant of a hand-over, or nobody (the default: a single-device call).  *_run_multi makes one per block and
+// passes it down to the host-pointer call of that block (host_call.h), whose end settles it; the destructor
+// settles it whether or not a call took it (an empty block, an argument error, an exception): the source cancels
+// an unpublished hand-over and waits for its peers, a peer reports that it is through.
 struct FanoutScope {
     DataFanout* f;
     int role;
-    FanoutScope() : f(t_fanout), role(t_fanout_role) { t_fanout = nullptr; t_fanout_role = DataFanout::NONE; }
+    explicit FanoutScope(DataFanout* f_ = nullptr, int role_ = DataFanout::NONE)
+        : f(role_ != DataFanout::NONE ? f_ : nullptr), role(f ? role_ : (int)DataFanout::NONE) {}
     ~FanoutScope() { finish(); }
-    // Settles the participant's part once (idempotent).  A SOURCE must call this BEFORE anything that may free
-    // the buffer it published -- DeviceContext::trim_after_call() under option host.cache_limit_mb -- because its
-    // peers copy from that buffer until they report peer_done (the destructor alone runs at function return,
-    // behind the trim: round-5 advisor finding).
+    // settles the participant's part once (idempotent)
     void finish()
     {
         if (!f) return;
@@ -163,39 +159,15 @@ struct FanoutScope {
     FanoutScope(const FanoutScope&) = delete;
     FanoutScope& operator=(const FanoutScope&) = delete;
 };
-// *_run_multi, around one block: hands the role to the host-pointer call the thread makes next and
-// settles it if that call never got as far as taking it (an empty block, an argument error)
-struct FanoutArm {
-    FanoutArm(DataFanout* f, int role)
-    {
-        t_fanout = (f && role != DataFanout::NONE) ? f : nullptr;
-        t_fanout_role = t_fanout ? role : (int)DataFanout::NONE;
-    }
-    ~FanoutArm()
-    {
-        if (t_fanout) {
-            if (t_fanout_role == DataFanout::SOURCE) t_fanout->cancel();
-            else if (t_fanout_role == DataFanout::PEER) t_fanout->peer_done();
-        }
-        t_fanout = nullptr;
-        t_fanout_role = DataFanout::NONE;
-    }
-    FanoutArm(const FanoutArm&) = delete;
-    FanoutArm& operator=(const FanoutArm&) = delete;
-};
 // one hand-over at a time per process (*_run_multi try-locks it; a second concurrent multi-device call
 // simply uploads from the host on every device): a source waits for its peers under its device's call
 // mutex, and two hand-overs with crossed device orders would wait for each other
 extern std::mutex g_fanout_mutex;
 
-// Enqueues "the day of data -> d_dst on this thread's current device" on `stream`: from the hand-over when
-// the thread is a peer of one that got published (device -> device), from `host` otherwise; a source
-// publishes behind its upload.  hipSuccess or the failing call's error (`what` names it).
-hipError_t fanout_upload(FanoutScope& scope, DeviceContext* ctx, void* d_dst, const void* host, size_t bytes,
-                         hipStream_t stream, const char** what);
-// The two halves of it, for a caller that uploads in pieces: a PEER's device-to-device copy (true = enqueued
-// or failed with *err set; false = not a peer, or the hand-over was cancelled: upload from the host), and a
-// SOURCE's publication behind the last piece it enqueued on `stream` (a no-op for anybody else).
+// The two halves of the hand-over on a participant's side: a PEER's device-to-device copy of the day into `d_dst`
+// on `stream` (true = enqueued or failed with *err set and `what` naming the call; false = not a peer, or the
+// hand-over was cancelled or refused: upload from the host), and a SOURCE's publication behind the last piece it
+// enqueued on `stream` (a no-op for anybody else).
 bool fanout_peer_copy(FanoutScope& scope, DeviceContext* ctx, void* d_dst, size_t bytes, hipStream_t stream,
                       hipError_t* err, const char** what);
 hipError_t fanout_publish(FanoutScope& scope, DeviceContext* ctx, const void* d_src, hipStream_t stream);
@@ -204,8 +176,12 @@ hipError_t fanout_publish(FanoutScope& scope, DeviceContext* ctx, const void* d_
 void parallel_copy(char* dst, const char* src, size_t bytes);
 // every host thread of the copy pool has finished what it was doing (context.hip: CopyPool)
 void copy_pool_quiesce();
-// device memory -> the caller's pageable array through the pinned pieces; blocks until `host` holds the bytes
-hipError_t staged_download(DeviceContext* ctx, void* host, const void* d_src, size_t bytes, hipStream_t stream);
+// device memory -> the caller's pageable array through the pinned pieces, in pieces of `piece` bytes (0 = the pinned
+// capacity), enqueued on `stream` behind `after` when one is given; blocks until `host` holds the bytes.  `times`:
+// adds the time spent waiting for pieces and copying them out.
+struct DownloadTimes { double wait_ms = 0.0, copy_ms = 0.0; };
+hipError_t staged_download(DeviceContext* ctx, void* host, const void* d_src, size_t bytes, hipStream_t stream,
+                           size_t piece = 0, hipEvent_t after = nullptr, DownloadTimes* times = nullptr);
 
 // rows x [c0, c1) of a (rows, N) float32 array in PAGEABLE host memory -> the same rows and samples of the
 // device array `d_dst`, through the context's two pinned pieces: host threads fill one piece (row segments

@@ -309,11 +309,13 @@ void parallel_copy(char* dst, const char* src, size_t bytes)
 // array is a new allocation on every call -- and took 40 ms for the 35 MB of a cfg3 day's (max-beam, arg-max)
 // on the second call of a process (tools/probe_bp_e2e.py, profiles/r06_bp_e2e.txt) where the copy itself is
 // 0.7 ms.  Blocks until `host` holds the bytes.  Needs reserve_pinned() first.
-hipError_t staged_download(DeviceContext* ctx, void* host, const void* d_src, size_t bytes, hipStream_t stream)
+hipError_t staged_download(DeviceContext* ctx, void* host, const void* d_src, size_t bytes, hipStream_t stream,
+                           size_t piece, hipEvent_t after, DownloadTimes* times)
 {
     if (bytes == 0) return hipSuccess;
     const size_t cap = ctx->pinned_cap.load();
     if (cap == 0) return hipErrorInvalidValue;
+    piece = piece ? std::min(piece, cap) : cap;
     hipError_t e = hipSuccess;
     // (the pieces may still be read by this call's last uploads)
     for (int i = 0; i < 2; ++i)
@@ -321,20 +323,27 @@ hipError_t staged_download(DeviceContext* ctx, void* host, const void* d_src, si
             if ((e = hipEventSynchronize(ctx->ev_piece[i])) != hipSuccess) return e;
             ctx->upload_inflight[i] = false;
         }
+    // The results come down through the pieces the day went up through: a copy-pool thread still finishing a block
+    // of one of the day's last fills (the fill returned without it, CopyPool::run) would write day bytes over
+    // result bytes that have already landed.  Every such straggler is done before the first D2H.
     copy_pool_quiesce();
-    const size_t n_piece = (bytes + cap - 1) / cap;
+    if (after && (e = hipStreamWaitEvent(stream, after, 0)) != hipSuccess) return e;
+    const size_t n_piece = (bytes + piece - 1) / piece;
     auto enqueue = [&](size_t q) {
-        const size_t o = q * cap, len = std::min(cap, bytes - o);
+        const size_t o = q * piece, len = std::min(piece, bytes - o);
         e = hipMemcpyAsync(ctx->pinned[q & 1], (const char*)d_src + o, len, hipMemcpyDeviceToHost, stream);
         if (e == hipSuccess) e = hipEventRecord(ctx->ev_piece[q & 1], stream);
     };
     enqueue(0);
     for (size_t q = 0; q < n_piece && e == hipSuccess; ++q) {
+        const double t0 = host_now_ms();
         if ((e = hipEventSynchronize(ctx->ev_piece[q & 1])) != hipSuccess) break;
-        if (q + 1 < n_piece) enqueue(q + 1);
+        const double t1 = host_now_ms();
+        if (q + 1 < n_piece) enqueue(q + 1);        // into the other pinned piece
         if (e != hipSuccess) break;
-        const size_t o = q * cap, len = std::min(cap, bytes - o);
+        const size_t o = q * piece, len = std::min(piece, bytes - o);
         parallel_copy((char*)host + o, ctx->pinned[q & 1], len);
+        if (times) { times->wait_ms += t1 - t0; times->copy_ms += host_now_ms() - t1; }
     }
     return e;
 }
@@ -479,8 +488,6 @@ DeviceContext* device_context(int device)
 }
 
 std::mutex g_fanout_mutex;
-thread_local DataFanout* t_fanout = nullptr;
-thread_local int t_fanout_role = DataFanout::NONE;
 
 namespace {
 // peer access src -> dst enabled once per ordered pair (a direct xGMI copy instead of one staged through
@@ -570,17 +577,6 @@ hipError_t fanout_publish(FanoutScope& scope, DeviceContext* ctx, const void* d_
     if (e != hipSuccess) return e;
     scope.f->publish(d_src, ctx->physical, ctx->ev_data);
     return hipSuccess;
-}
-
-hipError_t fanout_upload(FanoutScope& scope, DeviceContext* ctx, void* d_dst, const void* host, size_t bytes,
-                         hipStream_t stream, const char** what)
-{
-    hipError_t e;
-    if (fanout_peer_copy(scope, ctx, d_dst, bytes, stream, &e, what)) return e;
-    *what = "H2D data";
-    if ((e = hipMemcpyAsync(d_dst, host, bytes, hipMemcpyHostToDevice, stream)) != hipSuccess) return e;
-    *what = "event record";
-    return fanout_publish(scope, ctx, d_dst, stream);
 }
 
 hipStream_t device_side_stream(int device)

@@ -12,7 +12,7 @@
 // subtraction, square in double, float accumulator), so the result equals the single-threaded
 // reference bit for bit (tests/golden/similar_sources.npz).
 #include "common.h"
-#include "context.h"
+#include "host_call.h"
 #include "../../include/bpmf_hip.h"
 
 #include <algorithm>
@@ -193,64 +193,62 @@ extern "C" int bpmf_find_similar_sources(const float* moveouts, const float* sou
                   n_stations_for_diff, method);
         return -1;
     }
-    BPMF_BIND_DEVICE(device);
     // threshold^2 * n_diff exactly as the reference: (float)n * pow(threshold, 2) -> float
     const float thr2 = (float)((double)(float)n_stations_for_diff * ((double)threshold * (double)threshold));
-    // the device's private stream and working set (context.h): nothing allocated or freed per call,
-    // nothing on the null stream; calls on one device take turns
-    DeviceContext* ctx = device_context(device);
-    if (!ctx) return -2;
-    std::lock_guard<std::mutex> call_lock(ctx->call_mutex);
-    hipStream_t stream = ctx->s_run;
-    const size_t scratch_floats = method == 0 ? std::max<size_t>((size_t)FS_BATCH * FS_BATCH, (K + 255) / 256 * 256) * S : 1;
-    size_t total = 0;
-    auto carve = [&](size_t bytes) { const size_t o = total; total += align_up(std::max<size_t>(bytes, 1), 256); return o; };
-    const size_t o_mv = carve(K * S * sizeof(float)), o_order = carve(K * S * sizeof(int)),
-                 o_red = carve(K * sizeof(int)), o_sub = carve(K * sizeof(int)), o_st = carve(sizeof(FsState)),
-                 o_batch = carve(FS_BATCH * sizeof(int)), o_close = carve((size_t)FS_BATCH * FS_BATCH),
-                 o_alive = carve(FS_BATCH), o_scratch = carve(scratch_floats * sizeof(float));
-    char* base = ctx->reserve_device(total);
-    if (!base) return -2;
-    float* d_mv = (float*)(base + o_mv); int* d_order = (int*)(base + o_order); int* d_red = (int*)(base + o_red);
-    int* d_sub = (int*)(base + o_sub); FsState* d_st = (FsState*)(base + o_st); int* d_batch = (int*)(base + o_batch);
-    unsigned char* d_close = (unsigned char*)(base + o_close); unsigned char* d_alive = (unsigned char*)(base + o_alive);
-    float* d_scratch = (float*)(base + o_scratch);
-    int rc = 0;
-    auto run = [&]() -> int {
-        BPMF_HIP_CHECK(hipMemcpyAsync(d_mv, moveouts, K * S * sizeof(float), hipMemcpyHostToDevice, stream));
-        BPMF_HIP_CHECK(hipMemsetAsync(d_red, 0, K * sizeof(int), stream));
-        BPMF_HIP_CHECK(hipMemsetAsync(d_close, 0, FS_BATCH * FS_BATCH, stream));
-        if (method == 1) {
-            fs_argsort_kernel<<<dim3((unsigned)((K + 63) / 64)), dim3(64), 0, stream>>>(d_mv, K, (int)S, d_order);
-            BPMF_LAUNCH_CHECK();
-        }
-        // first pass: pairs inside the same (longitude, latitude) cell, cell by cell
-        std::vector<int> sub;
-        for (size_t i = 0; i < n_cells_longitude; ++i)
-            for (size_t j = 0; j < n_cells_latitude; ++j) {
-                sub.clear();
-                for (size_t k = 0; k < K; ++k)
-                    if (!(source_longitude[k] < cell_longitude[i] || source_longitude[k] >= cell_longitude[i + 1] ||
-                          source_latitude[k] < cell_latitude[j] || source_latitude[k] >= cell_latitude[j + 1]))
-                        sub.push_back((int)k);
-                if (sub.size() < 2) continue;
-                BPMF_HIP_CHECK(hipMemcpyAsync(d_sub, sub.data(), sub.size() * sizeof(int), hipMemcpyHostToDevice, stream));
-                BPMF_HIP_CHECK(hipStreamSynchronize(stream));  // `sub` is reused by the next cell
-                int r = method == 1
-                    ? fs_greedy<1>(d_mv, d_order, (int)S, (int)n_stations_for_diff, thr2, d_sub, (int)sub.size(), d_st, d_batch, d_close, d_alive, d_scratch, d_red, stream)
-                    : fs_greedy<0>(d_mv, d_order, (int)S, (int)n_stations_for_diff, thr2, d_sub, (int)sub.size(), d_st, d_batch, d_close, d_alive, d_scratch, d_red, stream);
-                if (r) return r;
+    return guarded("bpmf_find_similar_sources", [&]() -> int {
+        // the device's private stream and working set (host_call.h): nothing allocated or freed per call,
+        // nothing on the null stream; calls on one device take turns
+        FanoutScope nobody;
+        HostCall hc("bpmf_find_similar_sources", device, nobody);
+        if (!hc.ok()) return hc.rc;
+        hipStream_t stream = hc.ctx->s_run;
+        const size_t scratch_floats = method == 0 ? std::max<size_t>((size_t)FS_BATCH * FS_BATCH, (K + 255) / 256 * 256) * S : 1;
+        const size_t o_mv = hc.add(K * S * sizeof(float)), o_order = hc.add(K * S * sizeof(int)),
+                     o_red = hc.add(K * sizeof(int)), o_sub = hc.add(K * sizeof(int)), o_st = hc.add(sizeof(FsState)),
+                     o_batch = hc.add(FS_BATCH * sizeof(int)), o_close = hc.add((size_t)FS_BATCH * FS_BATCH),
+                     o_alive = hc.add(FS_BATCH), o_scratch = hc.add(scratch_floats * sizeof(float));
+        char* base = hc.reserve(0);
+        if (!base) return hc.rc;
+        float* d_mv = (float*)(base + o_mv); int* d_order = (int*)(base + o_order); int* d_red = (int*)(base + o_red);
+        int* d_sub = (int*)(base + o_sub); FsState* d_st = (FsState*)(base + o_st); int* d_batch = (int*)(base + o_batch);
+        unsigned char* d_close = (unsigned char*)(base + o_close); unsigned char* d_alive = (unsigned char*)(base + o_alive);
+        float* d_scratch = (float*)(base + o_scratch);
+        auto run = [&]() -> int {
+            BPMF_HIP_CHECK(hipMemcpyAsync(d_mv, moveouts, K * S * sizeof(float), hipMemcpyHostToDevice, stream));
+            BPMF_HIP_CHECK(hipMemsetAsync(d_red, 0, K * sizeof(int), stream));
+            BPMF_HIP_CHECK(hipMemsetAsync(d_close, 0, FS_BATCH * FS_BATCH, stream));
+            if (method == 1) {
+                fs_argsort_kernel<<<dim3((unsigned)((K + 63) / 64)), dim3(64), 0, stream>>>(d_mv, K, (int)S, d_order);
+                BPMF_LAUNCH_CHECK();
             }
-        // second pass: all remaining pairs
-        int r = method == 1
-            ? fs_greedy<1>(d_mv, d_order, (int)S, (int)n_stations_for_diff, thr2, nullptr, (int)K, d_st, d_batch, d_close, d_alive, d_scratch, d_red, stream)
-            : fs_greedy<0>(d_mv, d_order, (int)S, (int)n_stations_for_diff, thr2, nullptr, (int)K, d_st, d_batch, d_close, d_alive, d_scratch, d_red, stream);
-        if (r) return r;
-        BPMF_HIP_CHECK(hipMemcpyAsync(redundant_sources, d_red, K * sizeof(int), hipMemcpyDeviceToHost, stream));
-        BPMF_HIP_CHECK(hipStreamSynchronize(stream));
-        return 0;
-    };
-    rc = run();
-    (void)hipStreamSynchronize(stream);   // (also after a failure: the working set goes back to its cache)
-    return rc;
+            // first pass: pairs inside the same (longitude, latitude) cell, cell by cell
+            std::vector<int> sub;
+            for (size_t i = 0; i < n_cells_longitude; ++i)
+                for (size_t j = 0; j < n_cells_latitude; ++j) {
+                    sub.clear();
+                    for (size_t k = 0; k < K; ++k)
+                        if (!(source_longitude[k] < cell_longitude[i] || source_longitude[k] >= cell_longitude[i + 1] ||
+                              source_latitude[k] < cell_latitude[j] || source_latitude[k] >= cell_latitude[j + 1]))
+                            sub.push_back((int)k);
+                    if (sub.size() < 2) continue;
+                    BPMF_HIP_CHECK(hipMemcpyAsync(d_sub, sub.data(), sub.size() * sizeof(int), hipMemcpyHostToDevice, stream));
+                    BPMF_HIP_CHECK(hipStreamSynchronize(stream));  // `sub` is reused by the next cell
+                    int r = method == 1
+                        ? fs_greedy<1>(d_mv, d_order, (int)S, (int)n_stations_for_diff, thr2, d_sub, (int)sub.size(), d_st, d_batch, d_close, d_alive, d_scratch, d_red, stream)
+                        : fs_greedy<0>(d_mv, d_order, (int)S, (int)n_stations_for_diff, thr2, d_sub, (int)sub.size(), d_st, d_batch, d_close, d_alive, d_scratch, d_red, stream);
+                    if (r) return r;
+                }
+            // second pass: all remaining pairs
+            int r = method == 1
+                ? fs_greedy<1>(d_mv, d_order, (int)S, (int)n_stations_for_diff, thr2, nullptr, (int)K, d_st, d_batch, d_close, d_alive, d_scratch, d_red, stream)
+                : fs_greedy<0>(d_mv, d_order, (int)S, (int)n_stations_for_diff, thr2, nullptr, (int)K, d_st, d_batch, d_close, d_alive, d_scratch, d_red, stream);
+            if (r) return r;
+            BPMF_HIP_CHECK(hipMemcpyAsync(redundant_sources, d_red, K * sizeof(int), hipMemcpyDeviceToHost, stream));
+            BPMF_HIP_CHECK(hipStreamSynchronize(stream));
+            return 0;
+        };
+        hc.note(run());
+        hc.finish();
+        return hc.rc;
+    });
 }

@@ -11,7 +11,7 @@
 // evaluated with the exact-fp32 v_mfma_f32_16x16x4_f32 (a k-ordered fmaf chain; the band's
 // zeros add exact zeros), so every numerator equals the scalar chain of the oracle.
 #include "common.h"
-#include "context.h"
+#include "host_call.h"
 #include "mf_split_api.h"
 #include "mf_full_api.h"
 #include <system_error>
@@ -1742,10 +1742,9 @@ static std::vector<size_t> mf_batch_starts(size_t T, size_t TB)
     return bt;
 }
 
-static int bpmf_mf_run_impl(const float* templates, const int32_t* moveouts, const float* weights,
-                           const float* data, size_t step, size_t L, size_t N, size_t T, size_t S,
-                           size_t C, size_t n_corr, int network_sum, int flags, int device,
-                           float* cc_out)
+static int mf_run_call(const float* templates, const int32_t* moveouts, const float* weights, const float* data,
+                       size_t step, size_t L, size_t N, size_t T, size_t S, size_t C, size_t n_corr, int network_sum,
+                       int flags, int device, float* cc_out, FanoutScope& fan)
 {
     if (!templates || !moveouts || !weights || !data || !cc_out) {
         set_error("bpmf_mf_run: null pointer");
@@ -1759,9 +1758,9 @@ static int bpmf_mf_run_impl(const float* templates, const int32_t* moveouts, con
             return -1;
         }
     }
-    BPMF_BIND_DEVICE(device);
-    t_call_stats = HostCallStats();
-    const double t_call0 = host_now_ms();
+    HostCall hc("bpmf_mf_run", device, fan);
+    if (!hc.ok()) return hc.rc;
+    DeviceContext* ctx = hc.ctx;
     const size_t n_ch = S * C;
     const size_t row_bytes = n_corr * (network_sum ? 1 : n_ch) * sizeof(float);   // per template
     // options mf.host_batch_kb / mf.host_piece_kb: sizes of a batch's output and of a pinned piece
@@ -1778,39 +1777,27 @@ static int bpmf_mf_run_impl(const float* templates, const int32_t* moveouts, con
                  b_w = T * n_ch * sizeof(float), b_d = n_ch * N * sizeof(float),
                  b_out = TB * row_bytes,
                  b_ws = full_norm ? bpmf_mf_full_workspace_bytes(L, N, TB, S, C) : bpmf_mf_workspace_bytes(L, N, TB, S, C);
-    // streams, events, pinned pieces and the device working set are the device's (context.h): created
-    // once, reused by every call, one call per device at a time -- nothing is created or destroyed here
-    DeviceContext* ctx = device_context(device);
-    if (!ctx) return -2;
-    std::lock_guard<std::mutex> call_lock(ctx->call_mutex);
-    FanoutScope fan;      // (behind the lock: a source waits for its peers before another call may touch its data)
-    size_t o_tp = 0, o_mv = o_tp + align_up(b_tp, 256), o_w = o_mv + align_up(b_mv, 256),
-           o_d = o_w + align_up(b_w, 256), o_out0 = o_d + align_up(b_d, 256),
-           o_out1 = o_out0 + align_up(b_out, 256),
-           o_ws = o_out1 + (n_batch > 1 ? align_up(b_out, 256) : 0), total = o_ws + b_ws;
-    char* base = ctx->reserve_device(total);
-    if (!base) return -2;
+    const size_t o_tp = hc.add(b_tp), o_mv = hc.add(b_mv), o_w = hc.add(b_w), o_d = hc.add(b_d);
+    const size_t o_out[2] = {hc.add(b_out), hc.add(n_batch > 1 ? b_out : 0)};       // (a second one only when two batches overlap)
+    const size_t o_ws = hc.add(b_ws);
     // (a pinned piece never needs to be larger than one batch of output)
     // (... nor, for the upload of the day through the same pieces, than the day of data)
-    if (int prc = ctx->reserve_pinned(std::max(std::min(PIECE, std::max<size_t>(b_out, 4096)),
-                                               std::min<size_t>((size_t)64 << 20, std::max<size_t>(b_d, 4096)))))
-        return prc;
-    char* const* pinned = ctx->pinned;
-    hipStream_t s_run = ctx->s_run, s_copy = ctx->s_copy;
-    hipEvent_t* ev_batch = ctx->ev_batch;
-    hipEvent_t* ev_piece = ctx->ev_piece;
-    int rc = 0;
-    auto fail = [&](hipError_t e, const char* what) {
-        if (!rc) set_error("bpmf_mf_run: %s failed: %s", what, hipGetErrorString(e));
-        rc = -2;
-    };
-#define MF_TRY(expr, what) do { hipError_t e_ = (expr); if (e_ != hipSuccess) fail(e_, what); } while (0)
+    char* base = hc.reserve(std::max(std::min(PIECE, std::max<size_t>(b_out, 4096)),
+                                     std::min<size_t>((size_t)64 << 20, std::max<size_t>(b_d, 4096))));
+    if (!base) return hc.rc;
+    hipStream_t s_run = ctx->s_run;
+    float* const d_data = (float*)(base + o_d);
     // (through the pinned pieces, like the day: a pageable source makes the runtime page-lock the caller's pages for the
     // copy, and arrays that are temporaries of the Python wrapper -- the int32 moveouts, the broadcast weights -- are
-    // freed when the call returns: the NEXT call's first copy then stalls for tens of milliseconds, bp.hip: upload())
-    if (!rc) MF_TRY(staged_upload_rows(ctx, (float*)(base + o_tp), templates, 1, b_tp / 4, 0, b_tp / 4, s_run), "H2D templates");
-    if (!rc) MF_TRY(staged_upload_rows(ctx, (float*)(base + o_mv), (const float*)moveouts, 1, b_mv / 4, 0, b_mv / 4, s_run), "H2D moveouts");
-    if (!rc) MF_TRY(staged_upload_rows(ctx, (float*)(base + o_w), weights, 1, b_w / 4, 0, b_w / 4, s_run), "H2D weights");
+    // freed when the call returns: the NEXT call's first copy then stalls for tens of milliseconds)
+    auto upload = [&](size_t o, const void* host, size_t bytes, const char* what) {
+        if (!hc.ok()) return;
+        const hipError_t e = staged_upload_rows(ctx, (float*)(base + o), (const float*)host, 1, bytes / 4, 0, bytes / 4, s_run);
+        if (e != hipSuccess) hc.fail(e, what);
+    };
+    upload(o_tp, templates, b_tp, "H2D templates");
+    upload(o_mv, moveouts, b_mv, "H2D moveouts");
+    upload(o_w, weights, b_w, "H2D weights");
     // ---- The day of data.  A peer of a multi-device call copies it from the first device; a small problem
     // uploads it in one go.  A day-long series arrives IN PIECES on the copy stream while the first
     // template batch is computed on the lags whose windows have arrived (launches of mf_run_dev over
@@ -1819,25 +1806,30 @@ static int bpmf_mf_run_impl(const float* templates, const int32_t* moveouts, con
     // similarity_search.py:526-533).
     const bool use_mfma = mf_choose(step, L, N, std::min(TB, T), n_ch, n_corr, network_sum, flags, true).family != MF_DIRECT;
     const size_t n_offsets = (n_corr - 1) * step + 1;
-    bool from_peer = false;
-    if (!rc) {
-        const char* what = "";
-        hipError_t e_ = hipSuccess;
-        from_peer = fanout_peer_copy(fan, ctx, base + o_d, b_d, s_run, &e_, &what);
-        if (from_peer && e_ != hipSuccess) fail(e_, what);
-    }
+    DayFeed feed(hc, "H2D data");
+    const bool from_peer = feed.from_peer(d_data, b_d, s_run);
     // option mf.host_piece_lags: samples of the first piece (default 131 072; the tests shrink it), 0 = off
     const size_t PIECE0 = align_up((size_t)option(OPT_MF_HOST_PIECE_LAGS), (size_t)MF_LAGS_PER_WG);
     // (not under mf.split16: a channel's scale is its maximum over the WHOLE day; not in full normalisation: so is the
     // constant a channel is centred by)
-    const bool pieces = !rc && !from_peer && use_mfma && option(OPT_MF_COMPAT_SEQUENTIAL_CSUM) == 0 &&
+    const bool pieces = hc.ok() && !from_peer && use_mfma && option(OPT_MF_COMPAT_SEQUENTIAL_CSUM) == 0 &&
                         option(OPT_MF_SPLIT16) == 0 && !full_norm && PIECE0 != 0 && N >= 8 * PIECE0;
+    auto first_kernel = [&] {
+        if (t_call_stats.first_kernel_ms == 0.0) t_call_stats.first_kernel_ms = host_now_ms() - hc.t0;
+    };
+    // lag blocks `lc` of batch b into its output buffer, and the event behind the batch's last launch
     auto launch_range = [&](size_t b, const MfLaunch& lc) {
+        if (!hc.ok()) return;
         const size_t t0 = bt[b], nt = bt[b + 1] - bt[b];
-        char* d_out = base + ((b & 1) ? o_out1 : o_out0);
-        return mf_run_dev((const float*)(base + o_tp) + t0 * n_ch * L, (const int32_t*)(base + o_mv) + t0 * n_ch,
-                          (const float*)(base + o_w) + t0 * n_ch, (const float*)(base + o_d), step, L, N, nt, S, C,
-                          n_corr, network_sum, flags | BPMF_MF_DATA_PREPARED, base + o_ws, b_ws, s_run, (float*)d_out, lc);
+        hc.note(mf_run_dev((const float*)(base + o_tp) + t0 * n_ch * L, (const int32_t*)(base + o_mv) + t0 * n_ch,
+                           (const float*)(base + o_w) + t0 * n_ch, d_data, step, L, N, nt, S, C, n_corr, network_sum,
+                           flags | BPMF_MF_DATA_PREPARED, base + o_ws, b_ws, s_run, (float*)(base + o_out[b & 1]), lc));
+        first_kernel();
+    };
+    auto batch_enqueued = [&](size_t b) {
+        if (!hc.ok()) return;
+        const hipError_t e = hipEventRecord(ctx->ev_batch[b & 1], s_run);
+        if (e != hipSuccess) hc.fail(e, "event record");
     };
     size_t n_streamed = 0;            // batches computed while the data arrived (their events are recorded)
     if (pieces) {
@@ -1846,119 +1838,77 @@ static int bpmf_mf_run_impl(const float* templates, const int32_t* moveouts, con
         // idle device in the kernel trace of a cfg2 call; one batch of ~1 GB of output computes for longer than the
         // day takes to arrive, so it hides the whole upload, and batch 1 follows it without a gap)
         n_streamed = 1;
-        // largest moveout of a weighted channel per streamed batch: lag block [.., B) reads data up to
+        // largest moveout of a weighted channel of the streamed batch: lag block [.., B) reads data up to
         // B + mv_max + L (+ the staging slack of its last wave)
-        long long mv_max[2] = {0, 0};
-        for (size_t b = 0; b < n_streamed; ++b) {
-            const size_t t0 = bt[b], nt = bt[b + 1] - bt[b];
-            bool any = false;
-            for (size_t i = t0 * n_ch; i < (t0 + nt) * n_ch; ++i)
-                if (weights[i] != 0.0f && (!any || moveouts[i] > mv_max[b])) { mv_max[b] = moveouts[i]; any = true; }
-            mv_max[b] = std::max<long long>(mv_max[b], 0);
-        }
+        long long mv_max = 0;
+        for (size_t i = 0; i < bt[1] * n_ch; ++i)
+            if (weights[i] != 0.0f) mv_max = std::max<long long>(mv_max, moveouts[i]);
         // (what no piece has brought yet reads as zeros -- finite -- for the loads that run past a lag block's own windows)
-        MF_TRY(hipMemsetAsync(base + o_d, 0, b_d, s_run), "memset");
-        MF_TRY(hipEventRecord(ctx->ev_chunk[0], s_run), "event record");
-        MF_TRY(hipStreamWaitEvent(s_copy, ctx->ev_chunk[0], 0), "wait event");
+        const hipError_t e = hipMemsetAsync(d_data, 0, b_d, s_run);
+        if (e != hipSuccess) hc.fail(e, "memset");
+        feed.fork_from(s_run);
         const MfWorkspace wsd = mf_carve(base + o_ws, L, N, std::min(TB, T), n_ch);
         full_day_note(base + o_ws, base + o_d, N, n_ch, false);     // (a short-mode day from here on, as bpmf_mf_prepare_data_dev notes it)
         size_t have = 0, piece = PIECE0;
-        long long done[2] = {0, 0};
-        int n_piece = 1;
-        while (have < N && !rc) {
+        long long done = 0;
+        while (have < N && hc.ok()) {
             size_t upto = std::min(N, have + piece);
             if (N - upto < PIECE0) upto = N;                      // no sliver at the end
             piece = std::min(piece * 2, (size_t)8 * PIECE0);      // 0.13 M, 0.26 M, 0.5 M, then 1 M samples
-            MF_TRY(staged_upload_rows(ctx, (float*)(base + o_d), data, n_ch, N, have, upto, s_copy), "H2D data");
-            hipEvent_t ev = ctx->ev_chunk[n_piece++ % DeviceContext::CHUNK_EVENTS];
-            MF_TRY(hipEventRecord(ev, s_copy), "event record");
-            MF_TRY(hipStreamWaitEvent(s_run, ev, 0), "wait event");
-            if (upto == N) MF_TRY(fanout_publish(fan, ctx, base + o_d, s_copy), "event record");
-            if (!rc) rc = mf_prepare_range((const float*)(base + o_d), L, N, n_ch, wsd, s_run, have, upto);
+            feed.arrive(d_data, data, n_ch, N, have, upto, s_run);
+            if (hc.ok()) hc.note(mf_prepare_range(d_data, L, N, n_ch, wsd, s_run, have, upto));
             have = upto;
-            for (size_t b = 0; b < n_streamed && !rc; ++b) {
-                long long hi = have == N ? (long long)n_offsets
-                                         : ((long long)have - mv_max[b] - (long long)L - 2 * MF_LAGS_PER_WG) / MF_LAGS_PER_WG * MF_LAGS_PER_WG;
-                hi = std::min<long long>(hi, (long long)n_offsets);
-                if (hi <= done[b]) continue;
-                rc = launch_range(b, MfLaunch{done[b], hi, done[b] == 0});
-                if (t_call_stats.first_kernel_ms == 0.0) t_call_stats.first_kernel_ms = host_now_ms() - t_call0;
-                done[b] = hi;
-            }
+            long long hi = have == N ? (long long)n_offsets
+                                     : ((long long)have - mv_max - (long long)L - 2 * MF_LAGS_PER_WG) / MF_LAGS_PER_WG * MF_LAGS_PER_WG;
+            hi = std::min<long long>(hi, (long long)n_offsets);
+            if (hi <= done) continue;
+            launch_range(0, MfLaunch{done, hi, done == 0});
+            done = hi;
         }
-        for (size_t b = 0; b < n_streamed && !rc; ++b) MF_TRY(hipEventRecord(ev_batch[b & 1], s_run), "event record");
+        batch_enqueued(0);
     } else {
-        if (!rc && !from_peer) {
-            // (through the pinned pieces on the copy stream: the runtime's own path page-locks a host region it
-            // has not seen before -- a new day is a new array -- at a third of the rate, context.h)
-            MF_TRY(hipEventRecord(ctx->ev_chunk[0], s_run), "event record");        // behind the small uploads above
-            MF_TRY(hipStreamWaitEvent(s_copy, ctx->ev_chunk[0], 0), "wait event");
-            MF_TRY(staged_upload_rows(ctx, (float*)(base + o_d), data, n_ch, N, 0, N, s_copy), "H2D data");
-            if (!rc) MF_TRY(fanout_publish(fan, ctx, base + o_d, s_copy), "event record");
-            MF_TRY(hipEventRecord(ctx->ev_chunk[1], s_copy), "event record");
-            MF_TRY(hipStreamWaitEvent(s_run, ctx->ev_chunk[1], 0), "wait event");
+        if (!from_peer) {
+            feed.fork_from(s_run);                                // behind the small uploads above
+            feed.arrive(d_data, data, n_ch, N, 0, N, s_run);
         }
-        if (!rc)
-            rc = full_norm ? bpmf_mf_prepare_data_full_dev((const float*)(base + o_d), L, N, S, C, base + o_ws, b_ws, s_run)
-                           : bpmf_mf_prepare_data_dev((const float*)(base + o_d), L, N, S, C, base + o_ws, b_ws, s_run);
+        if (hc.ok())
+            hc.note(full_norm ? bpmf_mf_prepare_data_full_dev(d_data, L, N, S, C, base + o_ws, b_ws, s_run)
+                              : bpmf_mf_prepare_data_dev(d_data, L, N, S, C, base + o_ws, b_ws, s_run));
     }
     auto launch = [&](size_t b) {
-        if (b < n_streamed) return 0;                            // computed while the data arrived
-        int r = launch_range(b, MfLaunch());
-        if (!r) MF_TRY(hipEventRecord(ev_batch[b & 1], s_run), "event record");
-        return r;
+        if (b < n_streamed) return;                               // computed while the data arrived
+        launch_range(b, MfLaunch());
+        batch_enqueued(b);
     };
-    const bool verbose = option(OPT_MF_VERBOSE) != 0;
-    auto now = [] { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
-    const double t_start = now();
-    double t_wait = 0.0, t_copy = 0.0;
-    if (!rc) rc = launch(0);
-    if (t_call_stats.first_kernel_ms == 0.0) t_call_stats.first_kernel_ms = host_now_ms() - t_call0;
-    // The CC matrix comes down through the pieces the day went up through: a copy-pool thread still finishing a
-    // block of one of the day's last fills (the fill returned without it, context.hip: CopyPool::run) would write
-    // day bytes over CC bytes that have already landed.  Every such straggler is done before the first D2H (as in
-    // staged_download).
-    copy_pool_quiesce();
-    for (size_t b = 0; b < n_batch && !rc; ++b) {
-        if (b + 1 < n_batch) rc = launch(b + 1);   // its buffer was drained one iteration ago
-        if (rc) break;
-        const size_t t0 = bt[b], nt = bt[b + 1] - bt[b], bytes = nt * row_bytes;
-        const char* d_out = base + ((b & 1) ? o_out1 : o_out0);
-        char* h_out = (char*)cc_out + t0 * row_bytes;
-        MF_TRY(hipStreamWaitEvent(s_copy, ev_batch[b & 1], 0), "wait event");
-        const size_t n_piece = (bytes + PIECE - 1) / PIECE;
-        auto enqueue = [&](size_t q) {
-            const size_t o = q * PIECE, len = std::min(PIECE, bytes - o);
-            MF_TRY(hipMemcpyAsync(pinned[q & 1], d_out + o, len, hipMemcpyDeviceToHost, s_copy), "D2H cc");
-            MF_TRY(hipEventRecord(ev_piece[q & 1], s_copy), "event record");
-        };
-        if (!rc && n_piece) enqueue(0);
-        for (size_t q = 0; q < n_piece && !rc; ++q) {
-            const double t0w = now();
-            MF_TRY(hipEventSynchronize(ev_piece[q & 1]), "event sync");
-            const double t1w = now();
-            if (q + 1 < n_piece && !rc) enqueue(q + 1);   // into the other pinned buffer
-            if (!rc) {
-                const size_t o = q * PIECE, len = std::min(PIECE, bytes - o);
-                parallel_copy(h_out + o, pinned[q & 1], len);
-            }
-            t_wait += t1w - t0w;
-            t_copy += now() - t1w;
-        }
+    const double t_start = host_now_ms();
+    DownloadTimes times;
+    launch(0);
+    first_kernel();
+    for (size_t b = 0; b < n_batch && hc.ok(); ++b) {
+        if (b + 1 < n_batch) launch(b + 1);        // its buffer was drained one iteration ago
+        if (!hc.ok()) break;
+        const size_t t0 = bt[b], nt = bt[b + 1] - bt[b];
+        const hipError_t e = staged_download(ctx, (char*)cc_out + t0 * row_bytes, base + o_out[b & 1], nt * row_bytes,
+                                             ctx->s_copy, PIECE, ctx->ev_batch[b & 1], &times);
+        if (e != hipSuccess) hc.fail(e, "D2H cc");
     }
-    // (always drained, also after a failure: the working set goes back to its cache)
-    (void)hipStreamSynchronize(s_run);
-    (void)hipStreamSynchronize(s_copy);
-    t_call_stats.device_wait_ms = t_wait * 1e3;      // (waiting for drained pieces of the CC matrix)
-    t_call_stats.total_ms = host_now_ms() - t_call0;
-    if (verbose)
+    t_call_stats.device_wait_ms = times.wait_ms;     // (waiting for drained pieces of the CC matrix)
+    hc.finish();
+    if (option(OPT_MF_VERBOSE) != 0)
         fprintf(stderr, "[bpmf] mf_run: %zu batches of at most %zu templates, %.3f s after setup: waiting for the "
-                        "device %.3f s, host copies %.3f s\n", n_batch, TB, now() - t_start, t_wait, t_copy);
-#undef MF_TRY
-    copy_pool_quiesce();  // no host thread of the copy pool still reads the caller's arrays (a straggler of an idempotent fill) when the call returns
-    fan.finish();         // a source's peers are through with its copy of the day before the working set may go
-    ctx->trim_after_call();
-    return rc;
+                        "device %.3f s, host copies %.3f s\n", n_batch, TB, (host_now_ms() - t_start) * 1e-3,
+                times.wait_ms * 1e-3, times.copy_ms * 1e-3);
+    return hc.rc;
+}
+
+int bpmf::mf_run_host(const float* templates, const int32_t* moveouts, const float* weights, const float* data,
+                      size_t step, size_t L, size_t N, size_t T, size_t S, size_t C, size_t n_corr, int network_sum,
+                      int flags, int device, float* cc_out, FanoutScope& fan)
+{
+    return guarded("bpmf_mf_run", [&] {
+        return mf_run_call(templates, moveouts, weights, data, step, L, N, T, S, C, n_corr, network_sum, flags, device,
+                           cc_out, fan);
+    });
 }
 
 extern "C" int bpmf_mf_run(const float* templates, const int32_t* moveouts, const float* weights,
@@ -1966,19 +1916,9 @@ extern "C" int bpmf_mf_run(const float* templates, const int32_t* moveouts, cons
                            size_t C, size_t n_corr, int network_sum, int flags, int device,
                            float* cc_out)
 {
-    // nothing may cross the C boundary as an exception (std::bad_alloc from the host-side planning, a
-    // std::system_error): it becomes status -3 with its text
-    try {
-        return bpmf_mf_run_impl(templates, moveouts, weights, data, step, L, N, T, S, C, n_corr, network_sum, flags, device, cc_out);
-    } catch (const std::exception& e) {
-        copy_pool_quiesce();      // (no pool thread may still read the caller's arrays)
-        set_error("bpmf_mf_run: exception: %s", e.what());
-        return -3;
-    } catch (...) {
-        copy_pool_quiesce();
-        set_error("bpmf_mf_run: unknown exception");
-        return -3;
-    }
+    FanoutScope nobody;
+    return bpmf::mf_run_host(templates, moveouts, weights, data, step, L, N, T, S, C, n_corr, network_sum, flags, device,
+                             cc_out, nobody);
 }
 
 #ifdef BPMF_PHASE_CYCLES

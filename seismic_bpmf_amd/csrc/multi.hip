@@ -14,8 +14,7 @@
 //                   reduce="none": device d writes rows [k_d, k_{d+1}) of the (K, N) beam.
 #include "common.h"
 #include "../../include/bpmf_hip.h"
-#include "bp_plan.h"
-#include "context.h"
+#include "host_call.h"
 
 #include <algorithm>
 #include <cstring>
@@ -108,8 +107,9 @@ std::vector<size_t> block_bounds(size_t n, size_t parts)
 //
 // `share_data`: the blocks all read the same day of data from the host; with more than one distinct
 // device (and option multi.peer_fanout) the first device uploads it and the others copy it device ->
-// device (DataFanout, context.h) -- the first block of every distinct device takes part, fn(i) of those
-// blocks runs with the role armed for the host-pointer call it makes.
+// device (DataFanout, context.h) -- the first block of every distinct device takes part: fn(i, part) gets the
+// block's part in the hand-over and passes it to the host-pointer call it makes; the part is settled when the
+// block is over, whether or not a call took it.
 template <typename Fn>
 int run_blocks(const std::vector<int>& dev, Fn fn, bool share_data = false)
 {
@@ -135,11 +135,11 @@ int run_blocks(const std::vector<int>& dev, Fn fn, bool share_data = false)
     auto work = [&](size_t q) {
         for (size_t i : blocks_of[q]) {
             const bool first = i == blocks_of[q][0];
-            bpmf::FanoutArm arm(fan.get(), !first ? bpmf::DataFanout::NONE
-                                                  : (q == 0 ? bpmf::DataFanout::SOURCE : bpmf::DataFanout::PEER));
+            bpmf::FanoutScope part(fan.get(), !first ? bpmf::DataFanout::NONE
+                                                     : (q == 0 ? bpmf::DataFanout::SOURCE : bpmf::DataFanout::PEER));
             try {
                 bpmf::last_error_buf()[0] = 0;
-                rc[i] = fn(i);
+                rc[i] = fn(i, part);
                 // (a status-0 block may leave a NOTE -- the peer copy of the day fell back to host uploads,
                 // context.hip -- which the caller's thread passes on)
                 if (rc[i] || strncmp(bpmf_last_error(), "note:", 5) == 0) msg[i] = bpmf_last_error();
@@ -201,12 +201,12 @@ extern "C" int bpmf_mf_run_multi(const float* templates, const int32_t* moveouts
     const size_t n_ch = S * C;
     const std::vector<size_t> b = weighted_bounds(weights, T, n_ch, dev.size());
     const size_t row = n_corr * (network_sum ? 1 : n_ch);   // floats of output per template
-    return run_blocks(dev, [&](size_t i) -> int {
+    return run_blocks(dev, [&](size_t i, bpmf::FanoutScope& part) -> int {
         const size_t t0 = b[i], nt = b[i + 1] - b[i];
         if (nt == 0) return 0;
-        return bpmf_mf_run(templates + t0 * n_ch * L, moveouts + t0 * n_ch, weights + t0 * n_ch, data,
-                           step, L, N, nt, S, C, n_corr, network_sum, flags, dev[i],
-                           cc_out + t0 * row);
+        return bpmf::mf_run_host(templates + t0 * n_ch * L, moveouts + t0 * n_ch, weights + t0 * n_ch, data,
+                                 step, L, N, nt, S, C, n_corr, network_sum, flags, dev[i],
+                                 cc_out + t0 * row, part);
     }, true);
 }
 
@@ -241,17 +241,17 @@ extern "C" int bpmf_bp_run_multi(const float* features, const int32_t* moveouts,
     if (int rc = resolve_devices(n_devices, devices, K, dev, "bpmf_bp_run_multi")) return rc;
     const std::vector<size_t> b = block_bounds(K, dev.size());
     if (reduce != BPMF_BP_REDUCE_MAX) {
-        return run_blocks(dev, [&](size_t i) -> int {
+        return run_blocks(dev, [&](size_t i, bpmf::FanoutScope& part) -> int {
             const size_t k0 = b[i], nk = b[i + 1] - b[i];
             if (nk == 0) return 0;
-            return bpmf_bp_run(features, moveouts + k0 * S * P, w_phases, w_sources + k0 * S, N, nk, S,
-                               C, P, out_of_bounds, reduce, dev[i], beam_out + k0 * N, nullptr);
+            return bpmf::bp_run_host(features, moveouts + k0 * S * P, w_phases, w_sources + k0 * S, N, nk, S,
+                                     C, P, out_of_bounds, reduce, dev[i], beam_out + k0 * N, nullptr, false, part);
         }, true);
     }
     if (dev.size() == 1)   // (through run_blocks: its exception barrier)
-        return run_blocks(dev, [&](size_t) -> int {
-            return bpmf_bp_run(features, moveouts, w_phases, w_sources, N, K, S, C, P, out_of_bounds,
-                               reduce, dev[0], beam_out, arg_out);
+        return run_blocks(dev, [&](size_t, bpmf::FanoutScope& part) -> int {
+            return bpmf::bp_run_host(features, moveouts, w_phases, w_sources, N, K, S, C, P, out_of_bounds,
+                                     reduce, dev[0], beam_out, arg_out, false, part);
         });
     // option bp.compat_first_computed: every share keeps -inf where it computed no beam (a finished
     // share's (0, first id) could not be told from a real 0); the host finishes after the merge
@@ -260,12 +260,12 @@ extern "C" int bpmf_bp_run_multi(const float* features, const int32_t* moveouts,
     std::vector<std::vector<float>> pb(dev.size());
     std::vector<std::vector<int32_t>> pa(dev.size());
     for (size_t i = 1; i < dev.size(); ++i) { pb[i].resize(N); pa[i].resize(N); }
-    int rc = run_blocks(dev, [&](size_t i) -> int {
+    int rc = run_blocks(dev, [&](size_t i, bpmf::FanoutScope& part) -> int {
         const size_t k0 = b[i], nk = b[i + 1] - b[i];
         if (nk == 0) return 0;
         return bpmf::bp_run_host(features, moveouts + k0 * S * P, w_phases, w_sources + k0 * S, N, nk, S, C,
                                  P, out_of_bounds, reduce, dev[i], i ? pb[i].data() : beam_out,
-                                 i ? pa[i].data() : arg_out, first_computed);
+                                 i ? pa[i].data() : arg_out, first_computed, part);
     }, true);
     if (rc) return rc;
     // Ascending source blocks and a strict >: block 0 carries the (0, source 0) starting point of

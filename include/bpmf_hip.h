@@ -560,6 +560,48 @@ int bpmf_templates_from_events_dev(const float *d_data, size_t S, size_t C, size
                                    int normalize, int64_t noise_offset, size_t noise_samples, bpmf_stream_t stream,
                                    float *d_templates, float *d_norm, uint8_t *d_flags, float *d_snr_or_null);
 
+/* The running Z-score in front of the deep-learning phase picker (picker.hip; the reference: utils.normalize_batch,
+ * BPMF/utils.py:1966-2036, called on every event by Event.pick_PS_phases, BPMF/dataset.py:1706-1927, through the
+ * ml_picker of tutorial/notebooks/6_relocate.ipynb).  Row (r, c), r < n_rows, c < C, is
+ *     x[i] = d_data[r % S, c, d_start[r] + i] where 0 <= d_start[r] + i < N, else +0.0        (i = 0 .. n_samples-1)
+ * -- the windows of E events x S stations of a day in HBM (n_rows = E * S), or an already cut (R, C, n) tensor
+ * (S = n_rows, N = n_samples, d_start_or_null NULL: every start 0).  Each row is reflect-padded by `shift`; the
+ * float32 np.mean / np.std of its windows of `window` samples at the multiples of `shift` (a trailing partial window
+ * dropped; the first window takes the second's statistics and the last the last but one's; std 0 becomes 1) are
+ * interpolated in float64 to every sample from the n_windows abscissae d_nodes as np.interp does, and
+ *     d_out[r, c, i] = ((double) x[i] - mean(i)) / std(i)
+ * is stored as float64 (out_f64 != 0) or as its (float).  The results equal postprocess.normalize_batch_host bit for
+ * bit (NaN samples included; infinite samples are out of scope).  shift = int((1 - overlap) * window) and
+ * d_nodes = np.linspace(shift, n_samples - shift, n_windows) are the caller's (postprocess.normalize_batch_plan).
+ *   d_data (S, C, N) f32; d_start_or_null (n_rows) i64, clamped to +-2^40; d_nodes (n_windows) f64;
+ *   d_out (n_rows, C, n_samples) f32 or f64.  Every element of the output is written.
+ * Returns -1 for a null pointer, S * C == 0, N == 0 or above 2^40, n_rows * C >= 2^31, window < 2 or > 8192 (the
+ * length NumPy sums in one pairwise tree), shift < 1 or > n_samples - 1, fewer than 2 windows, n_windows other than
+ * (n_samples + 2 shift - window) / shift + 1, or a row that does not fit in LDS:
+ * n_samples + 2 shift + window + 2 n_windows must be at most 38400 floats (n_samples = 16384 with window = 3000 and
+ * shift = 1500 takes 22406).  n_rows == 0 launches nothing and returns 0. */
+int bpmf_normalize_batch_dev(const float *d_data, size_t S, size_t C, size_t N, size_t n_rows,
+                             const int64_t *d_start_or_null, size_t n_samples, size_t window, size_t shift,
+                             const double *d_nodes, size_t n_windows, int out_f64, bpmf_stream_t stream, void *d_out);
+
+/* The picks of every probability series the picker returns (picker.hip; the reference: utils.find_picks,
+ * BPMF/utils.py:2039-2094, called per station and phase by Event.pick_PS_phases, BPMF/dataset.py:1859-1865):
+ * scipy.signal.find_peaks(x, height=threshold, prominence=0.9 * threshold, width=1) -- plateau midpoints that a rise
+ * opens and a fall closes, prominence over the whole series, width at half prominence -- and per peak, over the
+ * samples int(left_ip) .. int(right_ip),
+ *     mean = np.sum(samples * prob) / prob.sum();   std = sqrt(np.sum((samples - mean)^2) / prob.sum())
+ * with the first and third sums in float64 and prob.sum() in float32, all in NumPy's pairwise order.  Series t uses
+ * threshold_even when t is even and threshold_odd when it is odd: a (.., 2, n) array of P and S probabilities.
+ *   d_proba (n_traces, n_samples) f32; d_count (n_traces) i32: the TRUE number of picks of the series;
+ *   d_value f32, d_mean f64, d_std f64, d_index i32 (the peak sample), each (n_traces, max_picks), ascending in
+ *   time: the first min(count, max_picks) picks; the unused slots hold NaN / -1.  Every element is written.
+ * The results equal postprocess.find_picks_host bit for bit.
+ * Returns -1 for a null pointer, n_samples == 0 or > 16384 (the series is staged in LDS), max_picks == 0 or > 4096,
+ * 2^31 series or more, or a NaN threshold.  n_traces == 0 launches nothing and returns 0. */
+int bpmf_find_picks_dev(const float *d_proba, size_t n_traces, size_t n_samples, double threshold_even,
+                        double threshold_odd, size_t max_picks, bpmf_stream_t stream, int32_t *d_count,
+                        float *d_value, double *d_mean, double *d_std, int32_t *d_index);
+
 /* ------------------------------------------------- robust statistics (stats.hip) --- */
 /* np.median and MAD (median of |x - median|, float32 like NumPy) of every row of a (rows, n)
  * device array; skip_zeros != 0: over the samples != 0 only (`a[a != 0]`).  NaN for an empty

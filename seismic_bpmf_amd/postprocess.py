@@ -180,6 +180,235 @@ def template_arguments(S, C, origin_samples, moveouts, n_samples, normalize, noi
     return origin, mv, L, n_noise, offset
 
 
+# ---- the deep-learning picker's surroundings: utils.normalize_batch, find_picks, get_picks (BPMF/utils.py:1966-2200) ----
+
+PICKER_MAX_WINDOW = 8192                     # one NumPy sum is one pairwise tree up to here (csrc/np_sums.h)
+PICK_COLUMNS = ("P_probas", "P_picks", "P_unc", "S_probas", "S_picks", "S_unc")
+
+
+def normalize_batch_plan(n_samples, normalization_window_sample=3000, overlap=0.5):
+    """(shift, n_windows) of utils.normalize_batch for rows of `n_samples`: shift = int((1 - overlap) * W), windows
+    at the multiples of shift in the row reflect-padded by shift, a trailing partial window dropped.  ValueError for
+    what the reference cannot do (fewer than 2 windows: its IndexError; shift > n - 1: np.pad reflects more than once)
+    or what the device does not do (W > 8192)."""
+    n, W = int(n_samples), int(normalization_window_sample)
+    if W < 2:
+        raise ValueError(f"normalize_batch: normalization_window_sample must be at least 2; got {W}")
+    if W > PICKER_MAX_WINDOW:
+        raise ValueError(f"normalize_batch: normalization_window_sample must be at most {PICKER_MAX_WINDOW}; got {W}")
+    shift = int((1.0 - overlap) * W)
+    if shift < 1:
+        raise ValueError(f"normalize_batch: overlap {overlap} leaves a shift of {shift} samples; need at least 1")
+    if shift > n - 1:
+        raise ValueError(f"normalize_batch: the shift ({shift}) must be at most n_samples - 1 ({n - 1}): the reflect "
+                         "padding would fold more than once")
+    n_windows = (n + 2 * shift - W) // shift + 1 if n + 2 * shift >= W else 0
+    if n_windows < 2:
+        raise ValueError(f"normalize_batch: {n} samples hold {n_windows} window(s) of {W}; need at least 2")
+    return shift, n_windows
+
+
+def normalize_batch_nodes(n_samples, shift, n_windows):
+    """The abscissae the reference interpolates the window statistics from (BPMF/utils.py:2005) -- not the centres of
+    the windows."""
+    return np.linspace(shift, n_samples - shift, n_windows)
+
+
+def _normalize_batch_replace_edges(std, mean):
+    """BPMF/utils.py:2007-2014: the last window takes the statistics of the last but one, then the first those of the
+    second."""
+    std[..., -1], mean[..., -1] = std[..., -2], mean[..., -2]
+    std[..., 0], mean[..., 0] = std[..., 1], mean[..., 1]
+
+
+def normalize_batch_host(seismogram, normalization_window_sample=3000, overlap=0.5):
+    """The DEFINITION of bpmf_normalize_batch_dev (csrc/picker.hip): utils.normalize_batch (BPMF/utils.py:1966-2036),
+    the running Z-score in front of the deep-learning picker, bit for bit and without SciPy.  `seismogram`
+    (R, C, n) float32; returns float64 (R, C, n).  Per row: reflect-pad by shift = int((1 - overlap) * W); np.std and
+    np.mean (float32) of the windows at the multiples of shift; the edge windows take their neighbours' statistics;
+    std == 0 becomes 1; both are interpolated to every sample with np.interp (float64) from the nodes
+    np.linspace(shift, n - shift, n_windows); out = (x - mean) / std in float64.  Refusals: normalize_batch_plan."""
+    x = np.asarray(seismogram, dtype=np.float32)
+    if x.ndim != 3:
+        raise ValueError("normalize_batch: seismogram must be (R, C, n)")
+    R, C, n = x.shape
+    W = int(normalization_window_sample)
+    shift, n_windows = normalize_batch_plan(n, W, overlap)
+    padded = np.pad(x, ((0, 0), (0, 0), (shift, shift)), mode="reflect")
+    windows = np.ascontiguousarray(
+        np.lib.stride_tricks.sliding_window_view(padded, W, axis=-1)[:, :, ::shift, :])
+    assert windows.shape[2] == n_windows
+    with np.errstate(invalid="ignore", over="ignore", under="ignore"):
+        std = np.std(windows, axis=-1)
+        mean = np.mean(windows, axis=-1)
+        _normalize_batch_replace_edges(std, mean)
+        std[std == 0] = 1
+        nodes = normalize_batch_nodes(n, shift, n_windows)
+        t = np.arange(n)
+        std_t = np.stack([np.interp(t, nodes, row, left=row[0], right=row[-1])
+                          for row in std.reshape(-1, n_windows)]).reshape(R, C, n)
+        mean_t = np.stack([np.interp(t, nodes, row, left=row[0], right=row[-1])
+                           for row in mean.reshape(-1, n_windows)]).reshape(R, C, n)
+        return (x - mean_t) / std_t
+
+
+def picker_windows_host(data, starts, n_samples):
+    """(E, S, C, n_samples) float32: the windows data[s, c, starts[e(, s)] + i] of the (S, C, N) day, +0.0 outside it
+    -- what picker_batch normalises without ever storing it."""
+    data = np.asarray(data, dtype=np.float32)
+    S, C, N = data.shape
+    starts = picker_starts(starts, S)
+    return _clipped_windows(data, np.broadcast_to(starts[:, :, None], starts.shape + (C,)), int(n_samples))
+
+
+def picker_starts(starts, S):
+    """`starts` (E,) or (E, S) integers as (E, S) int64, within +-2^40.  Raises ValueError."""
+    st = np.asarray(starts)
+    if st.ndim not in (1, 2) or (st.ndim == 2 and st.shape[1] != S) or (st.size and st.dtype.kind not in "iu"):
+        raise ValueError(f"picker_batch: starts must be (E,) or (E, {S}) integers (samples); got {st.dtype} {st.shape}")
+    st = st.astype(np.int64)
+    if np.any(np.abs(st) > 2**40):
+        raise ValueError("picker_batch: starts must lie within +-2^40")
+    return np.array(np.broadcast_to(st[:, None] if st.ndim == 1 else st, (len(st), S)), dtype=np.int64, order="C")
+
+
+def _plateau_midpoint(left, right):
+    return (left + right) // 2
+
+
+def _reaches(value, threshold):
+    """find_peaks(height=threshold) keeps value >= threshold."""
+    return value >= threshold
+
+
+def _pick_moments(samples, prob):
+    """BPMF/utils.py:2083-2084 as written: np.sum(samples * prob) in float64, prob.sum() in float32, and a spread that
+    the probabilities do not weight."""
+    mean = np.sum(samples * prob) / prob.sum()
+    std = np.sqrt(np.sum((samples - mean) ** 2) / prob.sum())
+    return mean, std
+
+
+def find_peaks_host(phase_probability, threshold):
+    """scipy.signal.find_peaks(x, height=threshold, prominence=0.9 * threshold, width=1) restated without SciPy:
+    (peaks, left_ips, right_ips).  Local maxima are the midpoints of plateaus that a rise opens and a fall closes (one
+    touching either end of the series is none); height: x[peak] >= threshold; prominence over the whole series
+    (wlen=None): x[peak] - max(lowest value on either side before a higher sample); width at half prominence between
+    linearly interpolated crossings, kept when >= 1.  The series is compared as float64, as SciPy casts it."""
+    x = np.ascontiguousarray(phase_probability, dtype=np.float64)
+    if x.ndim != 1:
+        raise ValueError("find_picks: phase_probability must be one series")
+    n = len(x)
+    min_prominence = 0.9 * threshold
+    peaks, left_ips, right_ips = [], [], []
+    i = 1
+    while i < n - 1:
+        if x[i - 1] < x[i]:
+            ahead = i + 1
+            while ahead < n - 1 and x[ahead] == x[i]:
+                ahead += 1
+            if x[ahead] < x[i]:
+                pk = _plateau_midpoint(i, ahead - 1)
+                if _reaches(x[pk], threshold):
+                    # prominence: walk out while the samples are not higher than the peak, keep the lowest
+                    j, left_min, left_base = pk, x[pk], pk
+                    while j >= 0 and x[j] <= x[pk]:
+                        if x[j] < left_min:
+                            left_min, left_base = x[j], j
+                        j -= 1
+                    j, right_min, right_base = pk, x[pk], pk
+                    while j <= n - 1 and x[j] <= x[pk]:
+                        if x[j] < right_min:
+                            right_min, right_base = x[j], j
+                        j += 1
+                    prominence = x[pk] - max(left_min, right_min)
+                    if min_prominence <= prominence:
+                        height = x[pk] - prominence * 0.5
+                        j = pk
+                        while left_base < j and height < x[j]:
+                            j -= 1
+                        left_ip = float(j)
+                        if x[j] < height:
+                            left_ip += (height - x[j]) / (x[j + 1] - x[j])
+                        j = pk
+                        while j < right_base and height < x[j]:
+                            j += 1
+                        right_ip = float(j)
+                        if x[j] < height:
+                            right_ip -= (height - x[j]) / (x[j - 1] - x[j])
+                        if 1 <= right_ip - left_ip:
+                            peaks.append(pk)
+                            left_ips.append(left_ip)
+                            right_ips.append(right_ip)
+                i = ahead
+        i += 1
+    return np.array(peaks, dtype=np.int64), np.array(left_ips, dtype=np.float64), np.array(right_ips, dtype=np.float64)
+
+
+def find_picks_host(phase_probability, threshold, return_index=False):
+    """The DEFINITION of bpmf_find_picks_dev (csrc/picker.hip): utils.find_picks (BPMF/utils.py:2039-2094) with its
+    default keywords, bit for bit and without SciPy.  Returns (values float32, means float64, stds float64) [and the
+    peak indices int64]: per peak of find_peaks_host, over the samples int(left_ip) .. int(right_ip), the moments
+    of _pick_moments on the float32 series.  Other find_peaks keywords are out of scope."""
+    prob_series = np.ascontiguousarray(phase_probability, dtype=np.float32)
+    peaks, left_ips, right_ips = find_peaks_host(prob_series, threshold)
+    means, stds = np.zeros(len(peaks), dtype=np.float64), np.zeros(len(peaks), dtype=np.float64)
+    with np.errstate(invalid="ignore", divide="ignore"):
+        for k in range(len(peaks)):
+            samples = np.arange(int(left_ips[k]), int(right_ips[k]) + 1)
+            means[k], stds[k] = _pick_moments(samples, prob_series[samples])
+    values = prob_series[peaks]
+    return (values, means, stds, peaks) if return_index else (values, means, stds)
+
+
+def _best_pick(probas, picks, prior, search_win_samp):
+    if prior is None:
+        return int(np.argmax(probas))
+    return int(np.argmax(probas * np.exp(-((picks - prior) ** 2) / (2.0 * search_win_samp**2))))
+
+
+def get_picks_host(values, means, stds, counts, buffer_length, prior=None, search_win_samp=None):
+    """utils.get_picks (BPMF/utils.py:2097-2200) on arrays instead of a pandas table: one P and one S pick per
+    station.  `values` (S, 2, max_picks) float32, `means`, `stds` (S, 2, max_picks) float64 and `counts` (S, 2): the
+    picks of find_picks, phase 0 = P, phase 1 = S.  Picks > int(buffer_length) only; the best S first (argmax of the
+    probability, or of probability * exp(-(pick - prior)^2 / (2 win^2)) where `prior` (S, 2), in samples, is not NaN
+    for the station: a station has both priors or none); then the P picks strictly before that S; a station without
+    an S keeps its best P.  `buffer_length` is explicit: the reference binds int(2 * cfg.SAMPLING_RATE_HZ) when it is
+    imported.  Returns (S, 6) float32 in the order of PICK_COLUMNS, NaN where there is no pick."""
+    values, means, stds = np.asarray(values, np.float32), np.asarray(means, np.float64), np.asarray(stds, np.float64)
+    counts = np.asarray(counts)
+    if values.ndim != 3 or values.shape[1] != 2 or means.shape != values.shape or stds.shape != values.shape or \
+            counts.shape != values.shape[:2]:
+        raise ValueError("get_picks: values, means, stds must be (S, 2, max_picks) and counts (S, 2)")
+    if counts.size and (counts.min() < 0 or counts.max() > values.shape[2]):
+        raise ValueError("get_picks: counts must lie in 0 .. max_picks (picks were dropped: raise max_picks)")
+    S = values.shape[0]
+    if prior is not None:
+        prior = np.asarray(prior, dtype=np.float64)
+        if prior.shape != (S, 2) or np.any(np.isnan(prior[:, 0]) != np.isnan(prior[:, 1])):
+            raise ValueError(f"get_picks: prior must be ({S}, 2), a row being all NaN (no prior) or not at all")
+        if search_win_samp is None:
+            raise ValueError("get_picks: prior needs search_win_samp (the width of the Gaussian, in samples)")
+    out = np.full((S, 6), np.nan, dtype=np.float32)
+    for s in range(S):
+        station_prior = None if prior is None or np.isnan(prior[s, 0]) else prior[s]
+        cols = []
+        for ph in range(2):
+            k = int(counts[s, ph])
+            valid = means[s, ph, :k] > int(buffer_length)
+            cols.append([values[s, ph, :k][valid], means[s, ph, :k][valid], stds[s, ph, :k][valid]])
+        (p_probas, p_picks, p_unc), (s_probas, s_picks, s_unc) = cols
+        if len(s_picks):
+            best = _best_pick(s_probas, s_picks, None if station_prior is None else station_prior[1], search_win_samp)
+            out[s, 3:] = s_probas[best], s_picks[best], s_unc[best]
+            before = p_picks < s_picks[best]
+            p_probas, p_picks, p_unc = p_probas[before], p_picks[before], p_unc[before]
+        if len(p_picks):
+            best = _best_pick(p_probas, p_picks, None if station_prior is None else station_prior[0], search_win_samp)
+            out[s, :3] = p_probas[best], p_picks[best], p_unc[best]
+    return out
+
+
 def normalize_weights(weights):
     """Sum of channel weights = 1 per template, BPMF/similarity_search.py:469-472."""
     w = np.array(weights, dtype=np.float32, copy=True)

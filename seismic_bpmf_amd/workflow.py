@@ -12,6 +12,9 @@
   ``_find_detections_t`` attaches to every detection (BPMF/similarity_search.py:695-722).
 * :func:`templates_from_events` = the templates of the located events, cut from the day on the device
   (``Event.read_waveforms`` + ``Template.init_from_event`` + ``TemplateGroup.normalize``, BPMF/dataset.py).
+* :func:`picker_batch` / :func:`normalize_batch` / :func:`find_picks` / :func:`pick_events` = what surrounds the
+  deep-learning picker in ``Event.pick_PS_phases`` (BPMF/dataset.py:1706-1927; ``utils.normalize_batch``,
+  ``find_picks``, ``get_picks``, BPMF/utils.py:1966-2200): device tensors in, device tensors out, pick tables back.
 """
 import numpy as np
 
@@ -267,6 +270,192 @@ def templates_from_events(data_dev, origin_samples, moveouts, n_samples, *, norm
         return {"templates": templates, "moveouts": d_mv, "weights": torch.as_tensor(weights, device=dev),
                 "available": available, "complete": complete, "norm": norm.cpu().numpy(),
                 "snr": None if snr is None else snr.cpu().numpy()}
+
+
+NORMALIZE_BATCH_LDS_FLOATS = 38400           # n + 2 shift + W + 2 n_windows of one row (csrc/picker.hip)
+FIND_PICKS_MAX_SAMPLES = 16384
+FIND_PICKS_MAX_PICKS = 4096
+
+
+def _normalize_rows(what, x, n_rows, d_start, n, W, overlap, dtype, out_shape):
+    """Checks on the host, then one bpmf_normalize_batch_dev launch on the current stream of x's device: rows
+    (r, c) = x[r % S, c, start[r] + i] of the contiguous float32 (S, C, N) tensor `x`."""
+    import ctypes as C
+    import torch
+    from . import _lib
+    if dtype not in (torch.float32, torch.float64):
+        raise ValueError(f"{what}: dtype must be torch.float32 or torch.float64; got {dtype}")
+    S, Cc, N = (int(v) for v in x.shape)
+    shift, n_windows = pp.normalize_batch_plan(n, normalization_window_sample=W, overlap=overlap)
+    floats = n + 2 * shift + int(W) + 2 * n_windows
+    if floats > NORMALIZE_BATCH_LDS_FLOATS:
+        raise ValueError(f"{what}: a row of {n} samples with windows of {int(W)} at shift {shift} takes {floats} floats "
+                         f"of LDS; at most {NORMALIZE_BATCH_LDS_FLOATS} fit")
+    if S * Cc == 0 or N == 0:
+        raise ValueError(f"{what}: the data are empty")
+    if n_rows * Cc >= 2**31:
+        raise ValueError(f"{what}: {n_rows} x {Cc} rows in one call; fewer than 2^31 fit")
+    dev = x.device
+    with torch.cuda.device(dev):
+        out = torch.empty(out_shape, dtype=dtype, device=dev)
+        if n_rows == 0:
+            return out
+        nodes = torch.as_tensor(pp.normalize_batch_nodes(n, shift, n_windows), device=dev)
+        rc = _lib.lib().bpmf_normalize_batch_dev(
+            C.c_void_p(x.data_ptr()), S, Cc, N, n_rows, None if d_start is None else C.c_void_p(d_start.data_ptr()),
+            n, int(W), shift, C.c_void_p(nodes.data_ptr()), n_windows, int(dtype == torch.float64),
+            C.c_void_p(torch.cuda.current_stream(dev).cuda_stream), C.c_void_p(out.data_ptr()))
+        _lib.check(rc, "bpmf_normalize_batch_dev")
+    return out
+
+
+def normalize_batch(x_dev, normalization_window_sample=3000, overlap=0.5, dtype=None):
+    """utils.normalize_batch (BPMF/utils.py:1966-2036), the running Z-score in front of the deep-learning picker, of an
+    already cut (R, C, n) float32 tensor on the GPU, in one launch (bpmf_normalize_batch_dev, csrc/picker.hip) on the
+    current stream.  Returns a tensor on the same device: float32 by default (the `.float()` of the reference's
+    float64 result, as the tutorial's ml_picker takes it) or, with dtype=torch.float64, the float64 result itself.  The
+    definition is postprocess.normalize_batch_host, which equals the reference bit for bit; the device equals it bit
+    for bit, NaN samples included.  Refusals (ValueError, before any device call): a window under 2 or over 8192
+    samples, a shift int((1 - overlap) * W) under 1 or over n - 1, fewer than two windows, a row too long for LDS
+    (n + 2 shift + W + 2 n_windows over 38400: n = 16384 with W = 3000 takes 22406).
+
+    Out of scope: the model itself; the resample_poly up- and down-sampling of Event.pick_PS_phases (a caller who
+    resamples with torch normalises the resampled tensor here); the power-of-two reflect padding of
+    tutorial/notebooks/6_relocate.ipynb cell 54; infinite samples."""
+    import torch
+    if not isinstance(x_dev, torch.Tensor) or not x_dev.is_cuda:
+        raise ValueError("normalize_batch: x_dev must be a tensor on the GPU (there is no CPU path; the definition on "
+                         "the host is postprocess.normalize_batch_host)")
+    if x_dev.dim() != 3:
+        raise ValueError("normalize_batch: x_dev must be (R, C, n)")
+    R, Cc, n = (int(v) for v in x_dev.shape)
+    with torch.cuda.device(x_dev.device):
+        x = x_dev.to(dtype=torch.float32).contiguous()
+    return _normalize_rows("normalize_batch", x, R, None, n, normalization_window_sample, overlap,
+                           torch.float32 if dtype is None else dtype, (R, Cc, n))
+
+
+def picker_batch(data_dev, starts, n_samples, *, normalization_window_sample=3000, overlap=0.5, dtype=None):
+    """The picker's input batch for E events, cut from the day in HBM and normalised in one launch
+    (bpmf_normalize_batch_dev, csrc/picker.hip): out[e, s, c, :] = normalize_batch of the window
+    data[s, c, starts[e(, s)] : + n_samples], zero-padded where it leaves the day -- what Event.read_waveforms +
+    utils.get_np_array + utils.normalize_batch make on the host for every event (BPMF/dataset.py:1770-1810,
+    BPMF/utils.py:1966-2036) -- without the un-normalised windows ever being stored.  Bit for bit
+    normalize_batch(the zero-padded cut windows) (postprocess.picker_windows_host / normalize_batch_host).
+
+    `data_dev`: the (S, C, N) float32 day as a tensor on the GPU (what MatchedFilterGPU.data holds); `starts` (E,) or
+    (E, S) int64 window starts in samples (origin - offset_ot), any sign, within +-2^40; `n_samples` per window.
+    Returns (E, S, C, n_samples) on the day's device and the current stream, float32 by default, ready for
+    model(x.flatten(0, 1)).  DEPARTURE: a window cut by the START of the day keeps its alignment here (zeros in
+    front); the reference left-aligns the samples it could read and pads behind them.
+
+    Refusals and what is out of scope: see normalize_batch."""
+    import torch
+    if not isinstance(data_dev, torch.Tensor) or not data_dev.is_cuda:
+        raise ValueError("picker_batch: data_dev must be a tensor on the GPU (there is no CPU path; the definition on "
+                         "the host is postprocess.normalize_batch_host of postprocess.picker_windows_host)")
+    if data_dev.dim() != 3:
+        raise ValueError("picker_batch: data_dev must be (S, C, N)")
+    S, Cc, N = (int(v) for v in data_dev.shape)
+    if isinstance(starts, torch.Tensor):
+        starts = starts.detach().cpu().numpy()
+    st = pp.picker_starts(starts, S)
+    n = int(n_samples)
+    dev = data_dev.device
+    with torch.cuda.device(dev):
+        x = data_dev.to(dtype=torch.float32).contiguous()
+        d_start = torch.as_tensor(st.reshape(-1), device=dev) if st.size else None
+    return _normalize_rows("picker_batch", x, st.size, d_start, n, normalization_window_sample, overlap,
+                           torch.float32 if dtype is None else dtype, (len(st), S, Cc, n))
+
+
+def find_picks(proba_dev, threshold_P=0.6, threshold_S=0.6, max_picks=32, truncate=False):
+    """utils.find_picks (BPMF/utils.py:2039-2094, default keywords) on every series of the picker's output while it
+    is still on the GPU, in one launch (bpmf_find_picks_dev, csrc/picker.hip): only the pick tables leave the device.
+    `proba_dev` (..., 2, n) float32 on the GPU, [..., 0, :] the P and [..., 1, :] the S probabilities, n <= 16384.
+    Returns a dict of host arrays: `count` (..., 2) int32, the number of picks of each series; `value` float32 (the
+    probability at the peak), `mean`, `std` float64 (the pick and its spread, in samples) and `index` int32 (the peak
+    sample), each (..., 2, max_picks), ascending in time, NaN / -1 in the unused slots.  The definition is
+    postprocess.find_picks_host; the device equals it bit for bit.  A series with more than `max_picks` picks raises
+    RuntimeError, unless `truncate`: then its first max_picks picks are kept and `count` tells how many there were.
+
+    Out of scope: find_peaks keywords other than the reference's defaults; infinite samples."""
+    import ctypes as C
+    import torch
+    from . import _lib
+    if not isinstance(proba_dev, torch.Tensor) or not proba_dev.is_cuda:
+        raise ValueError("find_picks: proba_dev must be a tensor on the GPU (there is no CPU path; the definition on "
+                         "the host is postprocess.find_picks_host)")
+    if proba_dev.dim() < 2 or proba_dev.shape[-2] != 2:
+        raise ValueError(f"find_picks: proba_dev must be (..., 2, n); got {tuple(proba_dev.shape)}")
+    n, max_picks = int(proba_dev.shape[-1]), int(max_picks)
+    if not 1 <= n <= FIND_PICKS_MAX_SAMPLES:
+        raise ValueError(f"find_picks: series of 1 .. {FIND_PICKS_MAX_SAMPLES} samples; got {n}")
+    if not 1 <= max_picks <= FIND_PICKS_MAX_PICKS:
+        raise ValueError(f"find_picks: max_picks must be 1 .. {FIND_PICKS_MAX_PICKS}; got {max_picks}")
+    thresholds = (float(threshold_P), float(threshold_S))
+    if any(t != t for t in thresholds):
+        raise ValueError("find_picks: the thresholds must be numbers")
+    lead = tuple(int(v) for v in proba_dev.shape[:-1])
+    T = int(np.prod(lead))
+    if T >= 2**31:
+        raise ValueError("find_picks: fewer than 2^31 series in one call")
+    dev = proba_dev.device
+    with torch.cuda.device(dev):
+        x = proba_dev.to(dtype=torch.float32).contiguous()
+        count = torch.empty(lead, dtype=torch.int32, device=dev)
+        value = torch.empty(lead + (max_picks,), dtype=torch.float32, device=dev)
+        mean = torch.empty(lead + (max_picks,), dtype=torch.float64, device=dev)
+        std = torch.empty(lead + (max_picks,), dtype=torch.float64, device=dev)
+        index = torch.empty(lead + (max_picks,), dtype=torch.int32, device=dev)
+        if T:
+            rc = _lib.lib().bpmf_find_picks_dev(
+                C.c_void_p(x.data_ptr()), T, n, thresholds[0], thresholds[1], max_picks,
+                C.c_void_p(torch.cuda.current_stream(dev).cuda_stream), C.c_void_p(count.data_ptr()),
+                C.c_void_p(value.data_ptr()), C.c_void_p(mean.data_ptr()), C.c_void_p(std.data_ptr()),
+                C.c_void_p(index.data_ptr()))
+            _lib.check(rc, "bpmf_find_picks_dev")
+        out = {"count": count.cpu().numpy(), "value": value.cpu().numpy(), "mean": mean.cpu().numpy(),
+               "std": std.cpu().numpy(), "index": index.cpu().numpy()}
+    if not truncate and T and out["count"].max() > max_picks:
+        raise RuntimeError(f"find_picks: a series holds {int(out['count'].max())} picks, more than max_picks = "
+                           f"{max_picks}; raise max_picks or pass truncate=True")
+    return out
+
+
+def pick_events(proba_dev, *, threshold_P, threshold_S, buffer_length, prior=None, search_win_samp=None, sr=None,
+                max_picks=32):
+    """One P and one S pick per station for E events, from the picker's (E, S, 2, n) probabilities on the GPU:
+    find_picks on the device, then postprocess.get_picks_host (utils.get_picks, BPMF/utils.py:2097-2200) per event on
+    the small pick tables -- the second half of Event.pick_PS_phases (BPMF/dataset.py:1854-1898).  `buffer_length`
+    (samples): picks up to it are discarded (the reference binds int(2 * cfg.SAMPLING_RATE_HZ) at import time);
+    `prior` (S, 2) or (E, S, 2): a priori P and S picks in samples, NaN rows for stations without one, with
+    `search_win_samp`.  Returns (E, S, 6) float32 in the order of postprocess.PICK_COLUMNS, NaN where there is no pick:
+    picks and uncertainties in samples, or in seconds when `sr` is given (the division of :1895-1898).
+
+    Out of scope: absolute pick times and the pandas table; see find_picks and normalize_batch for the rest."""
+    import torch
+    if not isinstance(proba_dev, torch.Tensor) or not proba_dev.is_cuda:
+        raise ValueError("pick_events: proba_dev must be a tensor on the GPU (there is no CPU path; the definitions on "
+                         "the host are postprocess.find_picks_host and postprocess.get_picks_host)")
+    if proba_dev.dim() != 4 or proba_dev.shape[2] != 2:
+        raise ValueError(f"pick_events: proba_dev must be (E, S, 2, n); got {tuple(proba_dev.shape)}")
+    E, S = int(proba_dev.shape[0]), int(proba_dev.shape[1])
+    if prior is not None:
+        prior = np.asarray(prior, dtype=np.float64)
+        if prior.shape not in ((S, 2), (E, S, 2)):
+            raise ValueError(f"pick_events: prior must be ({S}, 2) or ({E}, {S}, 2); got {prior.shape}")
+        if search_win_samp is None:
+            raise ValueError("pick_events: prior needs search_win_samp")
+        prior = np.broadcast_to(prior, (E, S, 2))
+    picks = find_picks(proba_dev, threshold_P, threshold_S, max_picks=max_picks)
+    out = np.full((E, S, 6), np.nan, dtype=np.float32)
+    for e in range(E):
+        out[e] = pp.get_picks_host(picks["value"][e], picks["mean"][e], picks["std"][e], picks["count"][e],
+                                   buffer_length, None if prior is None else prior[e], search_win_samp)
+    if sr is not None:
+        out[..., [1, 2, 4, 5]] = out[..., [1, 2, 4, 5]] / np.float32(sr)
+    return out
 
 
 def _peak_amplitude_window(sr, offset_win_peak_amp_sec, duration_win_peak_amp_sec):

@@ -110,6 +110,8 @@ int bpmf_host_call_stats(double *out, int n);
  *   debug.copy_stall_ms (tests, 0 .. 2000: k > 0 = in every multi-block fill of a pinned piece by the copy pool, the
  *     pool thread that draws the first block sleeps k ms before copying it, and the fill returns without waiting for
  *     it: a straggler that writes the start of the piece k ms later, every time; out[10] of bpmf_host_call_stats)
+ *   svdwf.max_sweeps (60, 1 .. 1000: Jacobi sweeps of bpmf_svdwf_stack_dev before a channel is reported as not
+ *     converged; a converged channel is the same at any cap -- the tests pass 1 to reach that status)
  *   mf.split16 (off by default; CHANGES RESULTS within a stated tolerance: matched-filter numerators on the fp16
  *     matrix pipe from hi/lo splits of data and templates, three products, fp32 accumulation -- csrc/mf_split.h;
  *     |d cc_sum| <= 3e-7 * sum|w| measured, 2e-5 allowed by the north star; against its float64 definition: bit-equal
@@ -671,6 +673,68 @@ int bpmf_row_kurtosis_dev(const float *d_x, size_t rows, size_t n, void *d_works
 int bpmf_row_kurtosis_parts_dev(const float *d_x, size_t rows, size_t n, void *d_workspace,
                                 size_t workspace_bytes, bpmf_stream_t stream, float *d_kurtosis,
                                 float *d_parts);
+
+/* ------------------------------------------- SVD-Wiener stack of a template's detections --- */
+/*
+ * EventGroup.SVDWF_stack (BPMF/dataset.py:4275-4374: utils.SVDWF, BPMF/utils.py:667-772, and utils.bandpass_filter,
+ * :24-90, on every channel, then the normalised mean) for a ragged batch of G groups (templates) in one call
+ * (svdwf.hip).  Group g holds the events offsets[g] .. offsets[g + 1] of d_x; a channel (g, s, c) is the (n, m) matrix
+ * A = d_x[offsets[g] .. offsets[g + 1], s, c, :], w = wiener_colsize, or n where that is 0.  In float64 throughout:
+ *   1. the eigenpairs of the Gram matrix on the smaller side (A A^T for n <= m, else A^T A) by two-sided cyclic
+ *      Jacobi, one workgroup per channel; sigma_j^2 are its eigenvalues, var = cumsum(sigma^2) / sum(sigma^2);
+ *      sum == 0: the channel's output is zeros, k = 0, no band-pass; else
+ *      k = min(max_singular_values, 1 + first j with var[j] >= expl_var);
+ *   2. for j < k the projection P_j = sigma_j u_j v_j^T, left as it is for w == 1, else scipy.signal.wiener(P_j,
+ *      [w, 1]): the local sums of row i run over the rows i - w / 2 .. i + (w - 1) / 2 that exist, divided by w;
+ *      noise = the mean local variance of the matrix; where the local variance is below it the local mean, else
+ *      (P - mean) (1 - noise / var) + mean.  A projection whose filtered form holds a NaN is skipped whole;
+ *   3. their sum, through the same filter once more (w != 1); NaN and +-Inf become 0;
+ *   4. with d_sos: every row loses its mean and its least-squares line, is multiplied by tukey(m, taper_alpha) and
+ *      goes through the cascade forward and backward (see bpmf_bandpass_rows_dev);
+ *   5. d_filtered = (float) of that; d_stack[g, s, c, :] = the float64 mean over the group's events of the float32
+ *      values, divided by its signed maximum over the samples (a maximum of 0 divides by 1), as float32.
+ * The definitions are seismic_bpmf_amd.postprocess.svdwf_host / svdwf_stack_host; the device is within 2^-22 of the
+ * channel's largest |filtered| and 2^-21 on the stack wherever the retained sigma_j^2 are separated from the next by
+ * 1e-4 sigma_1^2.  A channel gives the same bits in any batch and with any workspace.
+ *   d_x (N, S, C, m) f32, N = offsets[G]; offsets (G + 1) i64 ON THE HOST, ascending from 0; d_sos_or_null
+ *   (n_sections, 6) f64 rows [b0, b1, b2, 1, a1, a2] on the device, NULL: no band-pass; d_filtered_or_null (N, S, C, m)
+ *   f32; d_stack (G, S, C, m) f32; d_n_singular (G, S, C) i32 = k; d_status (G, S, C) i32: 0, or 1 where the solver
+ *   had not converged after option svdwf.max_sweeps sweeps (that channel's outputs are zeros, k = 0).
+ * Every element of every output is written.  An empty group has a zero stack, k = 0 and status 0.
+ * The workspace holds the offsets and one slot per channel in flight (two Gram-sized matrices, two (n, m) float64
+ * tables, the vectors): bpmf_svdwf_workspace_bytes(G, largest group, m, channels) for `channels` slots; the call
+ * processes the G * S * C channels in as many slabs as the slots it is given require (at most 65535 per slab), and
+ * needs at least one.  bpmf_svdwf_workspace_bytes returns 0 for sizes that the call refuses.
+ * Synchronises `stream` once before the first launch (the offsets are copied to the device).
+ * Returns -1 for a null pointer, S * C == 0, n_samples == 0, a group with min(n, m) > 512 or max(n, m) > 16384,
+ * max_singular_values outside 1 .. 8, expl_var outside (0, 1], wiener_colsize > 65536, d_sos with 0 or more than 8
+ * sections or a taper_alpha that is NaN, offsets that do not start at 0 or do not ascend, N * S * C or
+ * G * S * C >= 2^31, or a workspace smaller than the offsets and one slot (the offsets alone where every group is
+ * empty).  G == 0 launches nothing and returns 0.
+ */
+size_t bpmf_svdwf_workspace_bytes(size_t n_groups, size_t max_group_size, size_t n_samples, size_t n_channels);
+int bpmf_svdwf_stack_dev(const float *d_x, const int64_t *offsets, size_t n_groups, size_t S, size_t C,
+                         size_t n_samples, double expl_var, int max_singular_values, size_t wiener_colsize,
+                         const double *d_sos_or_null, size_t n_sections, double taper_alpha, void *d_workspace,
+                         size_t workspace_bytes, bpmf_stream_t stream, float *d_filtered_or_null, float *d_stack,
+                         int32_t *d_n_singular, int32_t *d_status);
+
+/* utils.bandpass_filter (BPMF/utils.py:24-90) on every row of a (rows, n_samples) table, one thread per row: with
+ * `detrend` the mean, then the least-squares line (closed form about the middle index) are subtracted; with
+ * taper_alpha > 0 the row is multiplied by scipy.signal.windows.tukey(n_samples, taper_alpha) (<= 0: no taper; above
+ * 1: 1); then the cascade of second-order sections runs from zero state in SciPy's operation order -- per sample,
+ * sections innermost, y = b0 x + z0; z0 = (b1 x - a1 y) + z1; z1 = b2 x - a2 y -- and, with `zerophase`, once more on
+ * the reversed row, reversed again.  No padding.  Without detrend and taper a float64 result equals
+ * scipy.signal.sosfilt (seismic_bpmf_amd.postprocess.bandpass_filter_host) bit for bit.
+ *   d_x f32 (in_f64 == 0) or f64; d_sos (n_sections, 6) f64 on the device, a0 = 1; d_out f32 or f64 (out_f64), must
+ *   not overlap d_x.  Every element of the output is written.  A zero-phase call with float32 output keeps the
+ *   forward pass in d_workspace: bpmf_bandpass_rows_workspace_bytes (8 rows n_samples; 0 for the other calls).
+ * Returns -1 for a null pointer, n_samples == 0 or above 2^24, rows >= 2^31, 0 or more than 8 sections, a
+ * taper_alpha that is NaN, or a workspace that is missing or too small.  rows == 0 launches nothing and returns 0. */
+size_t bpmf_bandpass_rows_workspace_bytes(size_t rows, size_t n_samples, int zerophase, int out_f64);
+int bpmf_bandpass_rows_dev(const void *d_x, int in_f64, size_t rows, size_t n_samples, const double *d_sos,
+                           size_t n_sections, int detrend, double taper_alpha, int zerophase, int out_f64,
+                           void *d_workspace, size_t workspace_bytes, bpmf_stream_t stream, void *d_out);
 
 /* ------------------------------------------- events detected by several templates --- */
 /*

@@ -65,6 +65,7 @@ const OptionDef OPTION_DEFS[OPT_COUNT] = {
     {"mf.split16", 0, 0, 2, false},                        // matched filter (template lengths: include/bpmf_hip.h, option mf.split16): numerators from fp16 hi/lo splits of data and templates (three v_mfma_f32_32x32x16_f16 products, fp32 accumulation; csrc/mf_split.h) instead of the exact-fp32 MFMA chain: |d cc| ~ 2e-7 instead of bit-identity with the oracle, ~2.4x the rate.  Norms, lag ranges, zero rules unchanged.  OFF by default; 1 = launches of at least 128 (template, 8192-lag block) pairs, 2 = every launch; changes the workspace size and what a prepared day holds
     {"debug.fail_peer_copy", 0, 0, 1, false},              // tests: every device-to-device probe of the multi-device hand-over fails (context.hip: peer_copy_works), so the fall-back -- each device uploads the day from the host, with a note in bpmf_last_error -- runs on a one-GPU box
     {"debug.copy_stall_ms", 0, 0, 2000, false},            // tests: k > 0 = in every idempotent fill of a pinned piece by the copy pool (context.hip: CopyPool::run with a token) the worker that draws block 0 sleeps k ms before its copy and the caller returns without it -- a straggler that writes offset 0 of the piece k ms later, every time
+    {"svdwf.max_sweeps", 60, 1, 1000, false},              // SVD-Wiener stack (csrc/svdwf.hip): Jacobi sweeps before a channel is given up as not converged (status 1, zeros); a converged solve is the same at any cap -- the tests pass 1 to reach that status
     {"mf.compat_exclusive_last_lag", 0, 0, 1, false},  // last valid data offset i * step < N - L - mv_max (default: <=)
     {"mf.compat_sqrt_norm", 0, 0, 1, false},           // cc = num / sqrtf(E_t * E_d) above 1e-6 (default: num * r_t * r_d)
     {"bp.compat_first_computed", 0, 0, 1, false},      // running max starts from the first computed beam (default: from (0, source 0))

@@ -1184,3 +1184,264 @@ def flag_multiples(origin_time_sec, template_rows, cc, pair_ok, dt_criterion):
     out = np.empty(n, dtype=bool)
     out[order] = unique
     return out
+
+
+# ---- SVD-Wiener stack of a template's detections (BPMF/utils.py: bandpass_filter :24-90, SVDWF :667-772;
+# ---- BPMF/dataset.py: EventGroup.SVDWF_stack :4275-4374) ----
+SVDWF_MAX_SMALL_SIDE = 512            # min(n, m) of one channel's (n, m) matrix (csrc/svdwf.hip)
+SVDWF_MAX_LARGE_SIDE = 16384          # max(n, m)
+SVDWF_MAX_SINGULAR_VALUES = 8
+BANDPASS_MAX_SECTIONS = 8
+
+
+def butter_bandpass_sos(order, low, high):
+    """Second-order sections of a digital Butterworth band-pass of `order` corners between `low` and `high`, both as
+    fractions of the Nyquist frequency: what scipy.signal.iirfilter(order, [low, high], btype="bandpass",
+    ftype="butter", output="zpk") followed by zpk2sos makes, without SciPy -- the analogue prototype, the band-pass
+    transform, the bilinear map, and the sections paired as zpk2sos pairs them (the pole pair closest to the unit circle
+    goes last and takes the two zeros nearest to it; the gain goes to the first section).  Returns (order, 6) float64
+    rows [b0, b1, b2, 1, a1, a2].  A band so wide that the transform makes real poles is refused."""
+    order = int(order)
+    low, high = float(low), float(high)
+    if not 1 <= order <= BANDPASS_MAX_SECTIONS:
+        raise ValueError(f"butter_bandpass_sos: order must be 1 .. {BANDPASS_MAX_SECTIONS}; got {order}")
+    if not 0.0 < low < high < 1.0:
+        raise ValueError(f"butter_bandpass_sos: need 0 < low < high < 1 (fractions of Nyquist); got {low}, {high}")
+    steps = np.arange(-order + 1, order, 2)
+    p = -np.exp(1j * np.pi * steps / (2 * order))                  # buttap
+    fs = 2.0
+    warped = 2 * fs * np.tan(np.pi * np.array([low, high]) / fs)
+    bw, wo = warped[1] - warped[0], np.sqrt(warped[0] * warped[1])
+    p_lp = p * bw / 2                                              # lp2bp_zpk
+    root = np.sqrt(p_lp ** 2 - wo ** 2)
+    p_bp = np.concatenate((p_lp + root, p_lp - root))
+    k_bp = bw ** order
+    fs2 = 2.0 * fs                                                 # bilinear_zpk
+    p_z = (fs2 + p_bp) / (fs2 - p_bp)
+    k_z = k_bp * np.real(1.0 / np.prod(fs2 - p_bp))                # (the zeros at s = 0 give prod(fs2 - 0) = fs2^order ...
+    k_z *= fs2 ** order                                            # ... in the numerator)
+    if np.any(np.abs(p_z.imag) <= 100 * np.finfo(float).eps * np.abs(p_z)):
+        raise ValueError("butter_bandpass_sos: the band is so wide that the band-pass transform makes real poles")
+    poles = p_z[p_z.imag > 0]
+    poles = poles[np.lexsort((np.abs(poles.imag), poles.real))]    # _cplxreal's order
+    if len(poles) != order:
+        raise ValueError("butter_bandpass_sos: the poles do not come in conjugate pairs")
+    zeros = [1.0] * order + [-1.0] * order                         # s = 0 -> z = 1; s = infinity -> z = -1
+    zeros.sort()
+    sos = np.zeros((order, 6))
+    for si in range(order - 1, -1, -1):
+        i = int(np.argmin(np.abs(1 - np.abs(poles))))
+        p1 = poles[i]
+        poles = np.delete(poles, i)
+        pair = []
+        for _ in range(2):
+            j = int(np.argmin(np.abs(p1 - np.array(zeros))))
+            pair.append(zeros.pop(j))
+        z1, z2 = pair
+        sos[si] = [1.0, -(z1 + z2), z1 * z2, 1.0, -2.0 * p1.real, p1.real * p1.real + p1.imag * p1.imag]
+    sos[0, :3] *= k_z
+    return sos
+
+
+def sos_table(sos):
+    """`sos` as the contiguous (n_sections, 6) float64 table the filters take: 1 .. 8 finite rows with a0 = 1."""
+    sos = np.ascontiguousarray(np.asarray(sos, dtype=np.float64))
+    if sos.ndim != 2 or sos.shape[1] != 6 or not 1 <= sos.shape[0] <= BANDPASS_MAX_SECTIONS:
+        raise ValueError(f"sos must be (n_sections, 6) with 1 .. {BANDPASS_MAX_SECTIONS} sections; got {sos.shape}")
+    if not np.isfinite(sos).all() or not (sos[:, 3] == 1.0).all():
+        raise ValueError("sos must be finite with a0 = 1 in every section")
+    return sos
+
+
+def bandpass_sos(sos=None, freqmin=None, freqmax=None, f_Nyq=None, filter_order=4):
+    """The section table of a band-pass call: `sos` itself, or butter_bandpass_sos(filter_order, freqmin / f_Nyq,
+    freqmax / f_Nyq)."""
+    if sos is not None:
+        return sos_table(sos)
+    if freqmin is None or freqmax is None or f_Nyq is None:
+        raise ValueError("give either sos or freqmin, freqmax and f_Nyq")
+    return butter_bandpass_sos(filter_order, float(freqmin) / float(f_Nyq), float(freqmax) / float(f_Nyq))
+
+
+def sosfilt_rows(sos, x):
+    """scipy.signal.sosfilt(sos, x) along the last axis of the (rows, m) float64 `x`, from zero state, in SciPy's
+    operation order: per sample the sections run innermost, y = b0 x + z0; z0 = (b1 x - a1 y) + z1;
+    z1 = b2 x - a2 y.  Bit for bit SciPy's result."""
+    y = np.array(x, dtype=np.float64)
+    rows, m = y.shape
+    n_sec = sos.shape[0]
+    z = np.zeros((n_sec, 2, rows))
+    coef = [[float(v) for v in row] for row in sos]
+    for t in range(m):
+        cur = y[:, t].copy()
+        for s in range(n_sec):
+            b0, b1, b2, _, a1, a2 = coef[s]
+            new = b0 * cur + z[s, 0]
+            z[s, 0] = (b1 * cur - a1 * new) + z[s, 1]
+            z[s, 1] = b2 * cur - a2 * new
+            cur = new
+        y[:, t] = cur
+    return y
+
+
+def tukey_window(m, alpha):
+    """scipy.signal.windows.tukey(m, alpha) (symmetric), float64."""
+    m = int(m)
+    if m <= 1 or alpha <= 0:
+        return np.ones(max(m, 0))
+    alpha = min(float(alpha), 1.0)
+    n = np.arange(m, dtype=np.float64)
+    width = int(np.floor(alpha * (m - 1) / 2.0))
+    w = np.ones(m)
+    n1, n3 = n[:width + 1], n[m - width - 1:]
+    w[:width + 1] = 0.5 * (1 + np.cos(np.pi * (-1 + 2.0 * n1 / alpha / (m - 1))))
+    w[m - width - 1:] = 0.5 * (1 + np.cos(np.pi * (-2.0 / alpha + 1 + 2.0 * n3 / alpha / (m - 1))))
+    return w
+
+
+def bandpass_filter_host(x, sos=None, *, freqmin=None, freqmax=None, f_Nyq=None, filter_order=4, detrend=True,
+                         taper_alpha=0.01, zerophase=True):
+    """utils.bandpass_filter (BPMF/utils.py:24-90) along the last axis of `x` (..., m), float64, NumPy only.  Per row:
+    the mean is subtracted, then the least-squares line (closed form: slope = sum((i - c) x) / sum((i - c)^2) about the
+    middle index c, intercept = the mean that is left; the reference solves the same problem with lstsq) -- both only
+    with `detrend` --, the row is multiplied by tukey(m, taper_alpha) (`taper_alpha` None: no taper), and the SOS
+    cascade (sosfilt_rows) runs forward from zero state and, with `zerophase`, on the reversed row from zero state,
+    reversed again.  No padding.  The sections are `sos` (n_sections, 6) or butter_bandpass_sos of the keywords."""
+    table = bandpass_sos(sos, freqmin, freqmax, f_Nyq, filter_order)
+    x = np.asarray(x)
+    y = np.array(x.reshape(-1, x.shape[-1]) if x.ndim else x.reshape(1, 1), dtype=np.float64)
+    m = y.shape[1]
+    if detrend and m:
+        y = y - y.mean(axis=1, keepdims=True)
+        d = np.arange(m, dtype=np.float64) - (m - 1) / 2.0
+        den = float((d * d).sum())
+        slope = (y * d).sum(axis=1, keepdims=True) / den if den > 0 else np.zeros((y.shape[0], 1))
+        y = y - (slope * d + y.mean(axis=1, keepdims=True))
+    if taper_alpha is not None and m:
+        y = y * tukey_window(m, taper_alpha)
+    y = sosfilt_rows(table, y)
+    if zerophase:
+        y = sosfilt_rows(table, y[:, ::-1])[:, ::-1]
+    return y.copy().reshape(x.shape)                               # (a copy: C order, no negative stride left)
+
+
+def wiener_rows_host(p, w):
+    """scipy.signal.wiener(p, [w, 1]) of the (n, m) float64 `p`: the local sums of row i run over the rows
+    i - w // 2 .. i + (w - 1) // 2 that exist (zero padding: the divisor is always w); noise = the mean local variance
+    of the whole matrix; where the local variance is below it the local mean, else
+    (p - mean) (1 - noise / var) + mean."""
+    n = p.shape[0]
+    lo, hi = w // 2, (w - 1) // 2
+    s1, s2 = np.zeros_like(p), np.zeros_like(p)
+    p2 = p * p
+    for d in range(-lo, hi + 1):
+        a, b = max(0, -d), min(n, n - d)                           # rows i with 0 <= i + d < n
+        if a < b:
+            s1[a:b] += p[a + d:b + d]
+            s2[a:b] += p2[a + d:b + d]
+    mean = s1 / w
+    var = s2 / w - mean ** 2
+    noise = var.mean()
+    with np.errstate(all="ignore"):
+        res = (p - mean) * (1 - noise / var) + mean
+        return np.where(var < noise, mean, res)
+
+
+def svdwf_arguments(n, m, expl_var, max_singular_values, wiener_filter_colsize):
+    """Checks shared by svdwf_host and workflow.svdwf_stack; returns (expl_var, max_singular_values, w or None)."""
+    expl_var, k = float(expl_var), int(max_singular_values)
+    if not 0.0 < expl_var <= 1.0:
+        raise ValueError(f"svdwf: expl_var must be in (0, 1]; got {expl_var}")
+    if not 1 <= k <= SVDWF_MAX_SINGULAR_VALUES:
+        raise ValueError(f"svdwf: max_singular_values must be 1 .. {SVDWF_MAX_SINGULAR_VALUES}; got {k}")
+    w = None if wiener_filter_colsize is None else int(wiener_filter_colsize)
+    if w is not None and not 1 <= w < 2**31:
+        raise ValueError(f"svdwf: wiener_filter_colsize must be at least 1; got {w}")
+    if m < 1:
+        raise ValueError("svdwf: the waveforms hold no samples")
+    return expl_var, k, w
+
+
+def svdwf_host(matrix, expl_var=0.4, max_singular_values=5, wiener_filter_colsize=None, sos=None, taper_alpha=0.01,
+               return_rank=False):
+    """utils.SVDWF (BPMF/utils.py:667-772) of one channel's (n, m) float32 matrix of detections, restated in float64
+    with its quirks; NumPy only.  1. singular values of the matrix, var = cumsum(s^2) / sum(s^2); a zero matrix gives
+    zeros (no band-pass); k = min(max_singular_values, 1 + first j with var[j] >= expl_var).  2. for j < min(n, k):
+    the rank-one projection P_j = u_j (u_j^T A), left as it is when w = wiener_filter_colsize (default n) is 1, else
+    wiener_rows_host(P_j, w); a projection whose filtered form holds a NaN is skipped whole.  3. their sum, passed
+    through wiener_rows_host again (w != 1); NaN and +-Inf become 0.  4. with `sos`: bandpass_filter_host (mean, line,
+    tukey(m, taper_alpha), zero phase).  5. the result rounded to float32.  Departure: where LAPACK fails the
+    reference returns Gaussian noise; here the error is raised.  Returns (n, m) float32 (and k, 0 for a zero matrix,
+    with `return_rank`)."""
+    a = np.asarray(matrix, dtype=np.float32).astype(np.float64)
+    if a.ndim != 2:
+        raise ValueError("svdwf_host: matrix must be (n, m)")
+    n, m = a.shape
+    expl_var, kmax, w = svdwf_arguments(n, m, expl_var, max_singular_values, wiener_filter_colsize)
+    out = np.zeros((n, m), dtype=np.float32)
+    if n == 0:
+        return (out, 0) if return_rank else out
+    if w is None:
+        w = n
+    u, s, _ = np.linalg.svd(a, full_matrices=False)
+    var = np.cumsum(s ** 2)
+    if var[-1] == 0.0:
+        return (out, 0) if return_rank else out
+    var = var / var[-1]
+    k = min(kmax, int(np.flatnonzero(var >= expl_var)[0]) + 1)
+    d = np.zeros((n, m))
+    for j in range(min(n, k)):
+        proj = np.outer(u[:, j], u[:, j] @ a)
+        f = proj if w == 1 else wiener_rows_host(proj, w)
+        if np.isnan(f).any():
+            continue
+        d += f
+    if w != 1:
+        d = wiener_rows_host(d, w)
+    d[~np.isfinite(d)] = 0.0
+    if sos is not None:
+        d = bandpass_filter_host(d, sos, taper_alpha=taper_alpha)
+    out = d.astype(np.float32)
+    return (out, k) if return_rank else out
+
+
+def group_offsets(n_events, offsets=None):
+    """`offsets` (G + 1,) int64 of a ragged batch of groups over `n_events` rows (None: one group), checked."""
+    if offsets is None:
+        return np.array([0, int(n_events)], dtype=np.int64)
+    off = np.ascontiguousarray(np.asarray(offsets).astype(np.int64).reshape(-1))
+    if off.size < 1 or off[0] != 0 or off[-1] != int(n_events) or (np.diff(off) < 0).any():
+        raise ValueError(f"offsets must ascend from 0 to the number of events ({int(n_events)}); got {off.tolist()}")
+    return off
+
+
+def svdwf_stack_host(x, offsets=None, *, expl_var=0.4, max_singular_values=5, wiener_filter_colsize=None, sos=None,
+                     taper_alpha=0.01):
+    """EventGroup.SVDWF_stack (BPMF/dataset.py:4313-4335) on plain arrays, for a ragged batch of groups: `x`
+    (N, S, C, m) float32, group g = rows offsets[g] .. offsets[g + 1].  Every channel of every group goes through
+    svdwf_host; the stack of a group is the float64 mean over its events of the float32 filtered values, divided by
+    its SIGNED maximum over the samples (a maximum of 0 divides by 1), rounded to float32.  An empty group has a zero
+    stack.  Returns (filtered (N, S, C, m) float32, stack (G, S, C, m) float32, n_singular (G, S, C) int32)."""
+    x = np.asarray(x, dtype=np.float32)
+    if x.ndim != 4:
+        raise ValueError("svdwf_stack_host: x must be (N, S, C, m)")
+    N, S, Cc, m = x.shape
+    off = group_offsets(N, offsets)
+    G = len(off) - 1
+    filtered = np.zeros_like(x)
+    stack = np.zeros((G, S, Cc, m), dtype=np.float32)
+    rank = np.zeros((G, S, Cc), dtype=np.int32)
+    for g in range(G):
+        a, b = int(off[g]), int(off[g + 1])
+        if a == b:
+            continue
+        for s in range(S):
+            for c in range(Cc):
+                filtered[a:b, s, c], rank[g, s, c] = svdwf_host(
+                    x[a:b, s, c], expl_var, max_singular_values, wiener_filter_colsize, sos, taper_alpha,
+                    return_rank=True)
+        mean = filtered[a:b].astype(np.float64).mean(axis=0)
+        norm = mean.max(axis=-1, keepdims=True)
+        norm[norm == 0.0] = 1.0
+        stack[g] = (mean / norm).astype(np.float32)
+    return filtered, stack, rank

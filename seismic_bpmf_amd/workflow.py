@@ -458,6 +458,144 @@ def pick_events(proba_dev, *, threshold_P, threshold_S, buffer_length, prior=Non
     return out
 
 
+SVDWF_WORKSPACE_BYTES = 2 << 30            # svdwf_stack: the workspace it asks for at most (and at least one channel)
+
+
+def bandpass_filter(x_dev, sos=None, *, freqmin=None, freqmax=None, f_Nyq=None, filter_order=4, detrend=True,
+                    taper_alpha=0.01, zerophase=True, dtype=None):
+    """utils.bandpass_filter (BPMF/utils.py:24-90) along the last axis of any (..., m) float32 or float64 tensor on the
+    GPU, one launch on the current stream (bpmf_bandpass_rows_dev, csrc/svdwf.hip): mean and least-squares line removed
+    (`detrend`), Tukey taper (`taper_alpha`, None for none), the Butterworth band-pass `filter_order` corners between
+    `freqmin` and `freqmax` (postprocess.butter_bandpass_sos) or the caller's `sos` (n_sections <= 8, 6) table, forward
+    and -- `zerophase` -- backward, from zero state, in float64.  Returns a tensor of the same shape and device,
+    float64 by default as the reference returns it, or `dtype` torch.float32.  The definition is
+    postprocess.bandpass_filter_host; without detrend and taper the float64 result equals it (and SciPy's sosfilt) bit
+    for bit."""
+    import ctypes as C
+    import torch
+    from . import _lib
+    if not isinstance(x_dev, torch.Tensor) or not x_dev.is_cuda:
+        raise ValueError("bandpass_filter: x_dev must be a tensor on the GPU (there is no CPU path; the definition on "
+                         "the host is postprocess.bandpass_filter_host)")
+    if x_dev.dim() < 1 or x_dev.dtype not in (torch.float32, torch.float64):
+        raise ValueError("bandpass_filter: x_dev must be a float32 or float64 tensor (..., m)")
+    dtype = torch.float64 if dtype is None else dtype
+    if dtype not in (torch.float32, torch.float64):
+        raise ValueError(f"bandpass_filter: dtype must be torch.float32 or torch.float64; got {dtype}")
+    table = pp.bandpass_sos(sos, freqmin, freqmax, f_Nyq, filter_order)
+    alpha = -1.0 if taper_alpha is None else float(taper_alpha)
+    if alpha != alpha:
+        raise ValueError("bandpass_filter: taper_alpha must be a number or None")
+    m = int(x_dev.shape[-1])
+    rows = int(np.prod(x_dev.shape[:-1]))
+    if m == 0 or m > 2**24 or rows >= 2**31:
+        raise ValueError(f"bandpass_filter: rows of 1 .. 2^24 samples, fewer than 2^31 of them; got {rows} x {m}")
+    dev = x_dev.device
+    with torch.cuda.device(dev):
+        x = x_dev.contiguous()
+        out = torch.empty(x.shape, dtype=dtype, device=dev)
+        if rows == 0:
+            return out
+        d_sos = torch.as_tensor(table, device=dev)
+        out_f64, zp = int(dtype == torch.float64), int(bool(zerophase))
+        need = _lib.lib().bpmf_bandpass_rows_workspace_bytes(rows, m, zp, out_f64)
+        ws = torch.empty((need,), dtype=torch.uint8, device=dev) if need else None
+        rc = _lib.lib().bpmf_bandpass_rows_dev(
+            C.c_void_p(x.data_ptr()), int(x.dtype == torch.float64), rows, m, C.c_void_p(d_sos.data_ptr()),
+            table.shape[0], int(bool(detrend)), alpha, zp, out_f64, None if ws is None else C.c_void_p(ws.data_ptr()),
+            need, C.c_void_p(torch.cuda.current_stream(dev).cuda_stream), C.c_void_p(out.data_ptr()))
+        _lib.check(rc, "bpmf_bandpass_rows_dev")
+    return out
+
+
+def svdwf_stack(x_dev, offsets=None, *, expl_var=0.4, max_singular_values=5, wiener_filter_colsize=None,
+                freqmin=None, freqmax=None, sampling_rate=None, sos=None, taper_alpha=0.01, return_filtered=True,
+                strict=True, workspace=None):
+    """EventGroup.SVDWF_stack (BPMF/dataset.py:4275-4374; utils.SVDWF, BPMF/utils.py:667-772) for a ragged batch of
+    templates in one call (bpmf_svdwf_stack_dev, csrc/svdwf.hip): the SVD-Wiener filter of every channel's (n, m)
+    matrix of detections, the band-pass behind it, the mean over the events and its normalisation by the signed
+    maximum -- the stack that becomes the template of the next iteration.
+
+    `x_dev` (N, S, C, m) float32 on the GPU: the waveforms of all detections (what templates_from_events cuts),
+    group g = rows offsets[g] .. offsets[g + 1] (`offsets` (G + 1,) ascending from 0 to N; None: one group).  A group
+    holds at most 512 events of up to 16384 samples, or up to 16384 events of at most 512 samples.  The band-pass is
+    applied when `sampling_rate` is given (order 4 between `freqmin` and `freqmax`, as the reference) or with a
+    caller's `sos` table; `wiener_filter_colsize` None: each group's size.
+
+    Returns (stack, filtered, n_singular, status): `stack` (G, S, C, m) float32 and `filtered` (N, S, C, m) float32
+    (None without `return_filtered`) on x_dev's device, `n_singular` (G, S, C) int32 (0 for a zero channel) and `status`
+    (G, S, C) int32 on the host.  A channel whose eigen-solve did not converge (status 1; its outputs are zeros)
+    raises RuntimeError unless strict=False.  The definition is postprocess.svdwf_stack_host, within 2^-22 of each
+    channel's largest |filtered| and 2^-21 on the stack.  `workspace`: a uint8 tensor to work in (at
+    least one channel's worth, bpmf_svdwf_workspace_bytes); by default up to 2 GiB are allocated for the call.
+
+    Departure: where LAPACK fails the reference returns Gaussian noise; here `status` reports it.  Out of scope:
+    non-finite input, fetching the waveforms, the Stack object."""
+    import ctypes as C
+    import torch
+    from . import _lib
+    if not isinstance(x_dev, torch.Tensor) or not x_dev.is_cuda:
+        raise ValueError("svdwf_stack: x_dev must be a tensor on the GPU (there is no CPU path; the definition on the "
+                         "host is postprocess.svdwf_stack_host)")
+    if x_dev.dim() != 4:
+        raise ValueError("svdwf_stack: x_dev must be (N, S, C, m)")
+    N, S, Cc, m = (int(v) for v in x_dev.shape)
+    if isinstance(offsets, torch.Tensor):
+        offsets = offsets.detach().cpu().numpy()
+    off = pp.group_offsets(N, offsets)
+    G = len(off) - 1
+    expl_var, kmax, w = pp.svdwf_arguments(N, m, expl_var, max_singular_values, wiener_filter_colsize)
+    if S * Cc == 0:
+        raise ValueError("svdwf_stack: the waveforms hold no channels")
+    sizes = np.diff(off)
+    n_max = int(sizes.max()) if G else 0
+    if G and (np.minimum(sizes, m).max() > pp.SVDWF_MAX_SMALL_SIDE or max(n_max, m) > pp.SVDWF_MAX_LARGE_SIDE):
+        raise ValueError(f"svdwf_stack: a group of {n_max} events x {m} samples is not served: min(n, m) <= "
+                         f"{pp.SVDWF_MAX_SMALL_SIDE} and max(n, m) <= {pp.SVDWF_MAX_LARGE_SIDE}")
+    if w is not None and w > 65536:
+        raise ValueError(f"svdwf_stack: wiener_filter_colsize <= 65536; got {w}")
+    if max(N, G) * S * Cc >= 2**31:
+        raise ValueError("svdwf_stack: fewer than 2^31 rows in one call")
+    table = None
+    if sos is not None or sampling_rate is not None:
+        table = pp.bandpass_sos(sos, freqmin, freqmax, None if sampling_rate is None else float(sampling_rate) / 2.0, 4)
+    alpha = -1.0 if taper_alpha is None else float(taper_alpha)
+    dev = x_dev.device
+    with torch.cuda.device(dev):
+        x = x_dev.to(dtype=torch.float32).contiguous()
+        stack = torch.empty((G, S, Cc, m), dtype=torch.float32, device=dev)
+        filtered = torch.empty((N, S, Cc, m), dtype=torch.float32, device=dev) if return_filtered else None
+        n_singular = torch.empty((G, S, Cc), dtype=torch.int32, device=dev)
+        status = torch.empty((G, S, Cc), dtype=torch.int32, device=dev)
+        if G:
+            lib = _lib.lib()
+            if workspace is None:
+                one = lib.bpmf_svdwf_workspace_bytes(G, n_max, m, 1)
+                per = one - lib.bpmf_svdwf_workspace_bytes(G, n_max, m, 0)
+                channels = max(1, min(G * S * Cc, SVDWF_WORKSPACE_BYTES // max(per, 1)))
+                workspace = torch.empty((lib.bpmf_svdwf_workspace_bytes(G, n_max, m, channels),), dtype=torch.uint8,
+                                        device=dev)
+            elif not (isinstance(workspace, torch.Tensor) and workspace.is_cuda and workspace.dtype == torch.uint8
+                      and workspace.is_contiguous() and workspace.data_ptr() % 256 == 0):
+                raise ValueError("svdwf_stack: workspace must be a contiguous uint8 tensor on the GPU, aligned to 256")
+            d_sos = None if table is None else torch.as_tensor(table, device=dev)
+            rc = lib.bpmf_svdwf_stack_dev(
+                C.c_void_p(x.data_ptr()), off.ctypes.data_as(C.POINTER(C.c_int64)), G, S, Cc, m, expl_var, kmax,
+                0 if w is None else w, None if d_sos is None else C.c_void_p(d_sos.data_ptr()),
+                0 if table is None else table.shape[0], alpha, C.c_void_p(workspace.data_ptr()),
+                int(workspace.numel()), C.c_void_p(torch.cuda.current_stream(dev).cuda_stream),
+                None if filtered is None else C.c_void_p(filtered.data_ptr()), C.c_void_p(stack.data_ptr()),
+                C.c_void_p(n_singular.data_ptr()), C.c_void_p(status.data_ptr()))
+            _lib.check(rc, "bpmf_svdwf_stack_dev")
+        n_singular, status = n_singular.cpu().numpy(), status.cpu().numpy()
+    if strict and status.any():
+        bad = np.argwhere(status != 0)[0]
+        raise RuntimeError(f"svdwf_stack: the eigen-solve of {int((status != 0).sum())} channel(s) did not converge "
+                           f"(first: group {bad[0]}, station {bad[1]}, component {bad[2]}); pass strict=False to get "
+                           "zeros there and the status array")
+    return stack, filtered, n_singular, status
+
+
 def _peak_amplitude_window(sr, offset_win_peak_amp_sec, duration_win_peak_amp_sec):
     """(offset, duration) in samples, as MatchedFilter.set_data converts them (BPMF/similarity_search.py:175-180)."""
     return (int(pp.sec_to_samp(offset_win_peak_amp_sec, sr)), int(pp.sec_to_samp(duration_win_peak_amp_sec, sr)))

@@ -586,6 +586,36 @@ int bpmf_normalize_batch_dev(const float *d_data, size_t S, size_t C, size_t N, 
                              const int64_t *d_start_or_null, size_t n_samples, size_t window, size_t shift,
                              const double *d_nodes, size_t n_windows, int out_f64, bpmf_stream_t stream, void *d_out);
 
+/* Polyphase resampling of float32 rows (resample.hip; the reference: scipy.signal.resample_poly(data_arr, upsampling,
+ * downsampling, axis=-1) between the cut windows and the picker in Event.pick_PS_phases, BPMF/dataset.py:1801-1804,
+ * and Stack.pick_PS_phases_family_mode, :5596-5599).  Rows are addressed as bpmf_normalize_batch_dev addresses them:
+ * row (r, c), r < n_rows, c < C, is
+ *     x[i] = d_data[r % S, c, d_start[r] + i] where 0 <= d_start[r] + i < N, else +0.0            (i = 0 .. n_in-1)
+ * -- windows cut from a day in HBM, or an already cut tensor (S = n_rows, N = n_in, d_start_or_null NULL).  The window
+ * is cut FIRST: the samples of the day beside it do not enter.  `up` and `down` are reduced by their gcd; d_table,
+ * taps_per_phase (hp) and n_pre_remove are the plan of postprocess.resample_poly_plan: the Kaiser-windowed filter
+ * firwin(20 max(up, down) + 1, 1 / max(up, down), ("kaiser", 5.0)) as float32 times up, with the zeros upfirdn runs it
+ * with in front and behind, zero-extended to hp taps for each of the `up` phases.  With m = q + n_pre_remove,
+ * j_hi = m down / up and t = m down % up,
+ *     d_out[r, c, q] = the float32 sum over k = hp - 1 .. 0 of x[j_hi - k] * d_table[t + k up]   (0 <= j_hi - k < n_in)
+ * from +0, input index ascending, one rounded multiply and one rounded add per tap (never a fused multiply-add), the
+ * zero taps of the padding included (they spread a NaN sample as far as SciPy spreads it).  The results equal
+ * postprocess.resample_poly_host, and through it SciPy, bit for bit.  One workgroup per (row, tile of outputs):
+ * bpmf_resample_poly_tile(up, down, taps_per_phase) is the tile the host picks (a multiple of 64, at most 1024, so
+ * that the table and the tile's input span take at most 48 KB of LDS; 0 for arguments the call below refuses).
+ *   d_data (S, C, N) f32; d_start_or_null (n_rows) i64, clamped to +-2^40; d_table (taps_per_phase * up) f32;
+ *   d_out (n_rows, C, n_out) f32.  Every element of the output is written.
+ * Returns -1, before anything is launched, for a null pointer, S * C == 0, N == 0 or above 2^40,
+ * n_rows * C >= 2^31, up or down under 1 or over 64, not reduced, or both 1 (a copy: the caller's), n_in < 1,
+ * n_in * max(up, down) >= 2^40, n_out other than ceil(n_in up / down), taps_per_phase == 0 or a table of more than
+ * 2048 taps, n_pre_remove above the table's length, or 2^31 workgroups or more.  n_rows == 0 launches nothing and
+ * returns 0. */
+size_t bpmf_resample_poly_tile(size_t up, size_t down, size_t taps_per_phase);
+int bpmf_resample_poly_dev(const float *d_data, size_t S, size_t C, size_t N, size_t n_rows,
+                           const int64_t *d_start_or_null, size_t n_in, size_t up, size_t down, const float *d_table,
+                           size_t taps_per_phase, size_t n_pre_remove, size_t n_out, bpmf_stream_t stream,
+                           float *d_out);
+
 /* The picks of every probability series the picker returns (picker.hip; the reference: utils.find_picks,
  * BPMF/utils.py:2039-2094, called per station and phase by Event.pick_PS_phases, BPMF/dataset.py:1859-1865):
  * scipy.signal.find_peaks(x, height=threshold, prominence=0.9 * threshold, width=1) -- plateau midpoints that a rise

@@ -90,6 +90,8 @@ SIGNATURES = {
     "bpmf_templates_from_events_dev": (C.c_int, [_vp, _sz, _sz, _sz, _sz, _vp, _vp, _sz, C.c_int, C.c_int64, _sz, _vp,
                                                  _vp, _vp, _vp, _vp]),
     "bpmf_normalize_batch_dev": (C.c_int, [_vp, _sz, _sz, _sz, _sz, _vp, _sz, _sz, _sz, _vp, _sz, C.c_int, _vp, _vp]),
+    "bpmf_resample_poly_tile": (_sz, [_sz, _sz, _sz]),
+    "bpmf_resample_poly_dev": (C.c_int, [_vp, _sz, _sz, _sz, _sz, _vp, _sz, _sz, _sz, _vp, _sz, _sz, _sz, _vp, _vp]),
     "bpmf_find_picks_dev": (C.c_int, [_vp, _sz, _sz, C.c_double, C.c_double, _sz, _vp, _vp, _vp, _vp, _vp, _vp]),
     "bpmf_svdwf_workspace_bytes": (_sz, [_sz, _sz, _sz, _sz]),
     "bpmf_svdwf_stack_dev": (C.c_int, [_vp, C.POINTER(C.c_int64), _sz, _sz, _sz, _sz, C.c_double, C.c_int, _sz, _vp, _sz,

@@ -272,6 +272,97 @@ def picker_starts(starts, S):
     return np.array(np.broadcast_to(st[:, None] if st.ndim == 1 else st, (len(st), S)), dtype=np.int64, order="C")
 
 
+RESAMPLE_MAX_RATE = 64                       # max(up, down) after the reduction by their gcd
+RESAMPLE_INDEX_LIMIT = 2**40                 # n_in * max(up, down) stays below it
+
+
+def resample_poly_factors(up, down):
+    """`up` and `down` of scipy.signal.resample_poly as Python ints divided by their gcd.  ValueError for factors that
+    are no integers or under 1, or a reduced max(up, down) over 64."""
+    factors = []
+    for name, v in (("up", up), ("down", down)):
+        if isinstance(v, (bool, np.bool_)) or not isinstance(v, (int, np.integer)):
+            if not isinstance(v, (float, np.floating)) or v != int(v):
+                raise ValueError(f"resample_poly: {name} must be an integer; got {v!r}")
+        if int(v) < 1:
+            raise ValueError(f"resample_poly: {name} must be at least 1; got {v!r}")
+        factors.append(int(v))
+    g = int(np.gcd(factors[0], factors[1]))
+    up, down = factors[0] // g, factors[1] // g
+    if max(up, down) > RESAMPLE_MAX_RATE:
+        raise ValueError(f"resample_poly: the reduced factors {up} / {down} exceed {RESAMPLE_MAX_RATE}")
+    return up, down
+
+
+def resample_poly_plan(n_in, up, down):
+    """What scipy.signal.resample_poly(x, up, down) (default window and padtype) does to a row of `n_in` float32
+    samples, restated without SciPy: (h, n_out, n_pre_pad, n_pre_remove, n_post_pad, table) for `up` and `down`
+    reduced by their gcd.  With r = max(up, down) and half = 10 r: `h` (2 half + 1,) float32 =
+    firwin(2 half + 1, 1 / r, window=("kaiser", 5.0)).astype(float32) * float32(up); `n_out` = ceil(n_in up / down);
+    upfirdn runs the filter with `n_pre_pad` zeros in front and `n_post_pad` behind and the first `n_pre_remove` of its
+    outputs are dropped; `table` (hp up,) float32 is that padded filter, zero-extended to hp = ceil(len / up) taps per
+    phase: output q reads table[t + k up], k = 0 .. hp - 1, for its phase t.  The float32 taps equal SciPy's bit for
+    bit for every r from 2 to 64 (the float64 ones do not: np.i0 and SciPy's i0 differ in the last bits).
+    Refusals (ValueError): resample_poly_factors; n_in < 1; n_in max(up, down) >= 2^40."""
+    up, down = resample_poly_factors(up, down)
+    n_in = int(n_in)
+    if n_in < 1:
+        raise ValueError(f"resample_poly: rows of at least 1 sample; got {n_in}")
+    r = max(up, down)
+    if n_in * r >= RESAMPLE_INDEX_LIMIT:
+        raise ValueError(f"resample_poly: n_in * max(up, down) = {n_in * r} must stay below 2^40")
+    half = 10 * r
+    m = (np.arange(2 * half + 1) - half).astype(np.float64)
+    cutoff = 1.0 / r                         # firwin forms cutoff * m, not m / r: the two differ in the last bit
+    h64 = cutoff * np.sinc(cutoff * m) * (np.i0(5.0 * np.sqrt(1.0 - (m / half) ** 2)) / np.i0(5.0))
+    h64 = h64 / h64.sum()
+    h = h64.astype(np.float32) * np.float32(up)
+    n_out = n_in * up // down + bool(n_in * up % down)
+    n_pre_pad = down - half % down
+    n_pre_remove = (half + n_pre_pad) // down
+    n_post_pad = 0
+    while ((n_in - 1) * up + len(h) + n_pre_pad + n_post_pad - 1) // down + 1 < n_out + n_pre_remove:
+        n_post_pad += 1
+    length = len(h) + n_pre_pad + n_post_pad
+    hp = -(-length // up)
+    table = np.zeros(hp * up, dtype=np.float32)
+    table[n_pre_pad:n_pre_pad + len(h)] = h
+    return h, n_out, n_pre_pad, n_pre_remove, n_post_pad, table
+
+
+def resample_poly_host(x, up, down):
+    """The DEFINITION of bpmf_resample_poly_dev (csrc/resample.hip): scipy.signal.resample_poly(x, up, down, axis=-1)
+    of float32 rows, bit for bit and without SciPy -- the up- and down-sampling between the cut windows and the picker
+    in Event.pick_PS_phases (BPMF/dataset.py:1801-1804, 5596-5599).  `x` (..., n_in) float32; returns (..., n_out)
+    float32.  With the plan of resample_poly_plan, output q has m = q + n_pre_remove, j_hi = m down // up,
+    t = m down % up and is the float32 chain
+        acc = +0;   for k = hp - 1 .. 0:   j = j_hi - k;   acc = fl(acc + fl(x[j] * table[t + k up]))   where 0 <= j < n_in
+    -- input index ascending, one rounded multiply and one rounded add per tap, never fused, samples outside the row
+    skipped.  The zero taps of the padding do multiply: a NaN sample spreads as far as SciPy spreads it.  up == down
+    after the reduction returns a copy.  Refusals: resample_poly_plan."""
+    x = np.asarray(x)
+    if x.dtype != np.float32:
+        raise ValueError(f"resample_poly: x must be float32; got {x.dtype}")
+    if x.ndim < 1:
+        raise ValueError("resample_poly: x must be (..., n)")
+    up, down = resample_poly_factors(up, down)
+    n_in = x.shape[-1]
+    _, n_out, _, n_pre_remove, _, table = resample_poly_plan(n_in, up, down)
+    if up == down:
+        return x.copy()
+    hp = len(table) // up
+    m = np.arange(n_out, dtype=np.int64) + n_pre_remove
+    j_hi, t = m * down // up, m * down % up
+    acc = np.zeros(x.shape[:-1] + (n_out,), dtype=np.float32)
+    with np.errstate(invalid="ignore", over="ignore", under="ignore"):
+        for k in range(hp - 1, -1, -1):
+            j = j_hi - k
+            q = np.flatnonzero((j >= 0) & (j < n_in))
+            if len(q):
+                acc[..., q] = acc[..., q] + x[..., j[q]] * table[t[q] + k * up]
+    return acc
+
+
 def _plateau_midpoint(left, right):
     return (left + right) // 2
 

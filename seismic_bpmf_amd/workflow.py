@@ -12,9 +12,10 @@
   ``_find_detections_t`` attaches to every detection (BPMF/similarity_search.py:695-722).
 * :func:`templates_from_events` = the templates of the located events, cut from the day on the device
   (``Event.read_waveforms`` + ``Template.init_from_event`` + ``TemplateGroup.normalize``, BPMF/dataset.py).
-* :func:`picker_batch` / :func:`normalize_batch` / :func:`find_picks` / :func:`pick_events` = what surrounds the
-  deep-learning picker in ``Event.pick_PS_phases`` (BPMF/dataset.py:1706-1927; ``utils.normalize_batch``,
-  ``find_picks``, ``get_picks``, BPMF/utils.py:1966-2200): device tensors in, device tensors out, pick tables back.
+* :func:`picker_batch` / :func:`resample_poly` / :func:`normalize_batch` / :func:`find_picks` / :func:`pick_events` =
+  what surrounds the deep-learning picker in ``Event.pick_PS_phases`` (BPMF/dataset.py:1706-1927;
+  ``scipy.signal.resample_poly``, ``utils.normalize_batch``, ``find_picks``, ``get_picks``, BPMF/utils.py:1966-2200):
+  device tensors in, device tensors out, pick tables back.
 """
 import numpy as np
 
@@ -277,15 +278,13 @@ FIND_PICKS_MAX_SAMPLES = 16384
 FIND_PICKS_MAX_PICKS = 4096
 
 
-def _normalize_rows(what, x, n_rows, d_start, n, W, overlap, dtype, out_shape):
-    """Checks on the host, then one bpmf_normalize_batch_dev launch on the current stream of x's device: rows
-    (r, c) = x[r % S, c, start[r] + i] of the contiguous float32 (S, C, N) tensor `x`."""
-    import ctypes as C
+def _normalize_checks(what, shape, n_rows, n, W, overlap, dtype):
+    """The refusals of the normalisation of `n_rows` rows of `n` samples cut from an (S, C, N) tensor; returns
+    (shift, n_windows)."""
     import torch
-    from . import _lib
     if dtype not in (torch.float32, torch.float64):
         raise ValueError(f"{what}: dtype must be torch.float32 or torch.float64; got {dtype}")
-    S, Cc, N = (int(v) for v in x.shape)
+    S, Cc, N = shape
     shift, n_windows = pp.normalize_batch_plan(n, normalization_window_sample=W, overlap=overlap)
     floats = n + 2 * shift + int(W) + 2 * n_windows
     if floats > NORMALIZE_BATCH_LDS_FLOATS:
@@ -295,6 +294,17 @@ def _normalize_rows(what, x, n_rows, d_start, n, W, overlap, dtype, out_shape):
         raise ValueError(f"{what}: the data are empty")
     if n_rows * Cc >= 2**31:
         raise ValueError(f"{what}: {n_rows} x {Cc} rows in one call; fewer than 2^31 fit")
+    return shift, n_windows
+
+
+def _normalize_rows(what, x, n_rows, d_start, n, W, overlap, dtype, out_shape):
+    """Checks on the host, then one bpmf_normalize_batch_dev launch on the current stream of x's device: rows
+    (r, c) = x[r % S, c, start[r] + i] of the contiguous float32 (S, C, N) tensor `x`."""
+    import ctypes as C
+    import torch
+    from . import _lib
+    S, Cc, N = (int(v) for v in x.shape)
+    shift, n_windows = _normalize_checks(what, (S, Cc, N), n_rows, n, W, overlap, dtype)
     dev = x.device
     with torch.cuda.device(dev):
         out = torch.empty(out_shape, dtype=dtype, device=dev)
@@ -319,9 +329,9 @@ def normalize_batch(x_dev, normalization_window_sample=3000, overlap=0.5, dtype=
     samples, a shift int((1 - overlap) * W) under 1 or over n - 1, fewer than two windows, a row too long for LDS
     (n + 2 shift + W + 2 n_windows over 38400: n = 16384 with W = 3000 takes 22406).
 
-    Out of scope: the model itself; the resample_poly up- and down-sampling of Event.pick_PS_phases (a caller who
-    resamples with torch normalises the resampled tensor here); the power-of-two reflect padding of
-    tutorial/notebooks/6_relocate.ipynb cell 54; infinite samples."""
+    The resample_poly up- and down-sampling that Event.pick_PS_phases runs in front of it is resample_poly below (and
+    picker_batch(upsampling=, downsampling=) runs both on the windows of a day).  Out of scope: the model itself; the
+    power-of-two reflect padding of tutorial/notebooks/6_relocate.ipynb cell 54; infinite samples."""
     import torch
     if not isinstance(x_dev, torch.Tensor) or not x_dev.is_cuda:
         raise ValueError("normalize_batch: x_dev must be a tensor on the GPU (there is no CPU path; the definition on "
@@ -335,7 +345,89 @@ def normalize_batch(x_dev, normalization_window_sample=3000, overlap=0.5, dtype=
                            torch.float32 if dtype is None else dtype, (R, Cc, n))
 
 
-def picker_batch(data_dev, starts, n_samples, *, normalization_window_sample=3000, overlap=0.5, dtype=None):
+def _resample_checks(what, shape, n_rows, n_in, up, down):
+    """The refusals of the resampling of `n_rows` rows of `n_in` samples cut from an (S, C, N) tensor by the reduced
+    up / down; returns (n_out, n_pre_remove, table, hp) of postprocess.resample_poly_plan."""
+    S, Cc, N = shape
+    _, n_out, _, n_pre_remove, _, table = pp.resample_poly_plan(n_in, up, down)
+    hp = len(table) // up
+    if S * Cc == 0 or N == 0:
+        raise ValueError(f"{what}: the data are empty")
+    if n_rows * Cc >= 2**31:
+        raise ValueError(f"{what}: {n_rows} x {Cc} rows in one call; fewer than 2^31 fit")
+    tile = resample_poly_tile(up, down, hp)
+    if n_rows * Cc * (-(-n_out // tile)) >= 2**31:
+        raise ValueError(f"{what}: {n_rows * Cc} rows of {n_out} output samples take 2^31 tiles of {tile} or more")
+    return n_out, n_pre_remove, table, hp
+
+
+def _resample_rows(what, x, n_rows, d_start, n_in, up, down):
+    """Checks on the host, then one bpmf_resample_poly_dev launch on the current stream of x's device: rows
+    (r, c) = x[r % S, c, start[r] + i], i < n_in, of the contiguous float32 (S, C, N) tensor `x`, resampled by the
+    reduced up / down (not both 1).  Returns (n_rows, C, n_out) float32."""
+    import ctypes as C
+    import torch
+    from . import _lib
+    S, Cc, N = (int(v) for v in x.shape)
+    n_out, n_pre_remove, table, hp = _resample_checks(what, (S, Cc, N), n_rows, n_in, up, down)
+    dev = x.device
+    with torch.cuda.device(dev):
+        out = torch.empty((n_rows, Cc, n_out), dtype=torch.float32, device=dev)
+        if n_rows == 0:
+            return out
+        d_table = torch.as_tensor(table, device=dev)
+        rc = _lib.lib().bpmf_resample_poly_dev(
+            C.c_void_p(x.data_ptr()), S, Cc, N, n_rows, None if d_start is None else C.c_void_p(d_start.data_ptr()),
+            n_in, up, down, C.c_void_p(d_table.data_ptr()), hp, n_pre_remove, n_out,
+            C.c_void_p(torch.cuda.current_stream(dev).cuda_stream), C.c_void_p(out.data_ptr()))
+        _lib.check(rc, "bpmf_resample_poly_dev")
+    return out
+
+
+def resample_poly_tile(up, down, taps_per_phase):
+    """The output samples one workgroup of bpmf_resample_poly_dev makes (csrc/resample.hip picks it so that the tap
+    table and the tile's input span fit its LDS budget): a row of n_out samples takes ceil(n_out / tile) workgroups."""
+    from . import _lib
+    tile = int(_lib.lib().bpmf_resample_poly_tile(int(up), int(down), int(taps_per_phase)))
+    if tile == 0:
+        raise ValueError(f"resample_poly: no tile for up={up} down={down} taps_per_phase={taps_per_phase}")
+    return tile
+
+
+def resample_poly(x_dev, up, down):
+    """scipy.signal.resample_poly(x, up, down, axis=-1) (default window and padtype) of a (..., n) float32 tensor on the
+    GPU, in one launch (bpmf_resample_poly_dev, csrc/resample.hip) on the current stream: the up- and down-sampling
+    that Event.pick_PS_phases(upsampling=, downsampling=) runs between cutting the windows and normalising them
+    (BPMF/dataset.py:1801-1804; 5596-5599 in Stack.pick_PS_phases_family_mode).  Returns (..., n_out) float32 on the
+    same device, n_out = ceil(n up / down).  The definition is postprocess.resample_poly_host, which equals SciPy bit
+    for bit; the device equals it bit for bit, NaN samples included.  up == down after the reduction by their gcd
+    returns a copy.  Refusals (ValueError, before any device call): factors that are no integers or under 1, a
+    reduced max(up, down) over 64, n < 1, n max(up, down) >= 2^40, a dtype other than float32.
+
+    Out of scope: the other `padtype` and `window` arguments; float64 and complex input."""
+    import torch
+    if not isinstance(x_dev, torch.Tensor) or not x_dev.is_cuda:
+        raise ValueError("resample_poly: x_dev must be a tensor on the GPU (there is no CPU path; the definition on "
+                         "the host is postprocess.resample_poly_host)")
+    if x_dev.dim() < 1 or x_dev.dtype != torch.float32:
+        raise ValueError(f"resample_poly: x_dev must be (..., n) float32; got {x_dev.dtype} {tuple(x_dev.shape)}")
+    up, down = pp.resample_poly_factors(up, down)
+    lead, n = tuple(int(v) for v in x_dev.shape[:-1]), int(x_dev.shape[-1])
+    n_out = pp.resample_poly_plan(n, up, down)[1]
+    R = int(np.prod(lead, dtype=np.int64))
+    if up != down and R:
+        _resample_checks("resample_poly", (R, 1, n), R, n, up, down)
+    with torch.cuda.device(x_dev.device):
+        if up == down:
+            return x_dev.clone(memory_format=torch.contiguous_format)
+        if R == 0:
+            return torch.empty(lead + (n_out,), dtype=torch.float32, device=x_dev.device)
+        x = x_dev.contiguous().view(R, 1, n)
+    return _resample_rows("resample_poly", x, R, None, n, up, down).view(lead + (n_out,))
+
+
+def picker_batch(data_dev, starts, n_samples, *, normalization_window_sample=3000, overlap=0.5, dtype=None,
+                 upsampling=1, downsampling=1):
     """The picker's input batch for E events, cut from the day in HBM and normalised in one launch
     (bpmf_normalize_batch_dev, csrc/picker.hip): out[e, s, c, :] = normalize_batch of the window
     data[s, c, starts[e(, s)] : + n_samples], zero-padded where it leaves the day -- what Event.read_waveforms +
@@ -349,7 +441,16 @@ def picker_batch(data_dev, starts, n_samples, *, normalization_window_sample=300
     model(x.flatten(0, 1)).  DEPARTURE: a window cut by the START of the day keeps its alignment here (zeros in
     front); the reference left-aligns the samples it could read and pads behind them.
 
-    Refusals and what is out of scope: see normalize_batch."""
+    `upsampling` / `downsampling`: the keywords of Event.pick_PS_phases for data that are not at the picker's rate
+    (the tutorial's 25 Hz day and a 100 Hz picker: upsampling=4).  The windows of `n_samples` INPUT samples are then
+    resampled between the cut and the normalisation, as BPMF/dataset.py:1801-1804 does with scipy.signal.resample_poly:
+    bpmf_resample_poly_dev (csrc/resample.hip) writes the resampled windows to a temporary (E S, C, n_out) tensor and
+    bpmf_normalize_batch_dev normalises it.  Returns (E, S, C, n_out), n_out = ceil(n_samples up / down): bit for bit
+    normalize_batch_host(resample_poly_host(picker_windows_host(...))).  The normalisation window and its refusals then
+    count in RESAMPLED samples, and so do the picks that find_picks / pick_events make of the model's output.  Equal
+    factors (1 and 1 after the reduction by their gcd) take the path without resampling: the same launch and bits.
+
+    Refusals (every one before any device call) and what is out of scope: see normalize_batch and resample_poly."""
     import torch
     if not isinstance(data_dev, torch.Tensor) or not data_dev.is_cuda:
         raise ValueError("picker_batch: data_dev must be a tensor on the GPU (there is no CPU path; the definition on "
@@ -361,12 +462,24 @@ def picker_batch(data_dev, starts, n_samples, *, normalization_window_sample=300
         starts = starts.detach().cpu().numpy()
     st = pp.picker_starts(starts, S)
     n = int(n_samples)
+    up, down = pp.resample_poly_factors(upsampling, downsampling)
+    dtype = torch.float32 if dtype is None else dtype
+    W = normalization_window_sample
+    n_out = n
+    if up != down:
+        n_out = _resample_checks("picker_batch", (S, Cc, N), st.size, n, up, down)[0]
+        _normalize_checks("picker_batch", (S, Cc, N), st.size, n_out, W, overlap, dtype)
     dev = data_dev.device
     with torch.cuda.device(dev):
         x = data_dev.to(dtype=torch.float32).contiguous()
         d_start = torch.as_tensor(st.reshape(-1), device=dev) if st.size else None
-    return _normalize_rows("picker_batch", x, st.size, d_start, n, normalization_window_sample, overlap,
-                           torch.float32 if dtype is None else dtype, (len(st), S, Cc, n))
+    if up != down:
+        if st.size == 0:
+            return torch.empty((0, S, Cc, n_out), dtype=dtype, device=dev)
+        resampled = _resample_rows("picker_batch", x, st.size, d_start, n, up, down)
+        return _normalize_rows("picker_batch", resampled, st.size, None, n_out, W, overlap, dtype,
+                               (len(st), S, Cc, n_out))
+    return _normalize_rows("picker_batch", x, st.size, d_start, n, W, overlap, dtype, (len(st), S, Cc, n))
 
 
 def find_picks(proba_dev, threshold_P=0.6, threshold_S=0.6, max_picks=32, truncate=False):
@@ -431,7 +544,9 @@ def pick_events(proba_dev, *, threshold_P, threshold_S, buffer_length, prior=Non
     (samples): picks up to it are discarded (the reference binds int(2 * cfg.SAMPLING_RATE_HZ) at import time);
     `prior` (S, 2) or (E, S, 2): a priori P and S picks in samples, NaN rows for stations without one, with
     `search_win_samp`.  Returns (E, S, 6) float32 in the order of postprocess.PICK_COLUMNS, NaN where there is no pick:
-    picks and uncertainties in samples, or in seconds when `sr` is given (the division of :1895-1898).
+    picks and uncertainties in samples, or in seconds when `sr` is given (the division of :1895-1898).  Behind
+    picker_batch(upsampling=, downsampling=) the samples are those of the RESAMPLED rate: `sr` is then
+    sr * upsampling / downsampling, as BPMF/dataset.py:1807 sets it, and so are buffer_length, prior and search_win_samp.
 
     Out of scope: absolute pick times and the pandas table; see find_picks and normalize_batch for the rest."""
     import torch

@@ -700,6 +700,17 @@ __device__ __forceinline__ int2 mf_fused_prologue(const float* __restrict__ tmpl
 // hour-long series with a handful of templates, BASELINE configs[0]: 704 waves of 1024 lags on 1024
 // SIMDs, each wave alone with its serial work; at 256 lags per wave 2816 waves share the matrix pipes
 // three to a SIMD).  The hand-placed operand reads and their counted waits follow NTILE.
+// LDS of a wave: [band: tp[15 + l] = tmpl[l], Kpad + 16 floats][window][64 floats of slack for whole-chunk stores].
+//   NTILE 1 / 2: window sample x at dw[x + 2 (x >> 4)] (2 floats of padding per 16: conflict-free ds_read_b32 of B),
+//                5 / 3 / 2 ds_read_b32 per k-step, two k-steps ahead.
+//   NTILE 4:     the four-phase window -- sample x at dw[(x & 3) P + (x >> 2)], P = 16 (ceil(Ww / 64) | 1) + 2 floats
+//                per plane (P = 18 mod 32; 4 P <= Ww + 135, inside the same buffer: mf_lds_bytes does not change).  The k index
+//                of lane (a, kq) is kq + 4 s: always plane kq, and consecutive k-steps s are consecutive dwords, so a
+//                PAIR of k-steps takes one ds_read_b64 per tile (tile u at +256 u bytes) and one ds_read2_b32 of the
+//                band -- 10 LDS instructions per trip of 16 MFMAs, bank-conflict-free for every L (lanes 0-31: dwords
+//                {4 a, 4 a + 1} of plane 0 and {P + 4 a, P + 4 a + 1} of plane 1 are 64 distinct banks).  Staging
+//                register r of a lane (x = lane + 64 r) goes to (lane & 3) P + (lane >> 2) + 16 r: one address
+//                register and an immediate.  Measured: profiles/mf_phase_window.txt.
 // Cycle accounting (tools/phase/build_phase_lib.py builds a second library with -DBPMF_PHASE_CYCLES; the
 // shipping library carries none of it): s_memtime at the phase boundaries of a channel, summed per wave
 // over its channels and, at the end of the kernel, over all waves of the launch into g_mf_phase[{staging
@@ -805,9 +816,21 @@ __global__ __launch_bounds__(MF_THREADS, 4) void mf_mfma_wave_kernel(
 
     if (wave_valid) {
         float* tp = smem + wv * wave_floats;  // tp[15 + l] = tmpl[l], zeros around
-        float* dw = tp + tp_len;              // dw[pad(x)] = data[g0 + x]
+        float* dw = tp + tp_len;              // dw[pad(x)] = data[g0 + x]; 4 tiles per wave: four planes, see below
         const int a_base = 15 - a + kq;
-        const int b_base = 18 * a + kq;  // window padded 2 floats per 16: conflict-free B reads
+        // 1 / 2 tiles per wave: window padded 2 floats per 16, conflict-free 4-byte B reads.
+        // 4 tiles per wave: the four-phase window -- sample x at dw[(x & 3) PH + (x >> 2)], PH = 16 (ceil(Ww / 64) | 1) + 2:
+        // 16 entries per 64-lane staging chunk, the chunk count made odd so that PH = 18 (mod 32) -- the planes then start
+        // 18 banks apart and the 64 lanes of a staging store spread over 58 banks (PH = 2 (mod 64) put them on 22, 4 deep).
+        // Lane (a, kq) of tile u reads x = 256 u + 16 a + kq + 16 q + 4 s at k-step s of trip q: plane kq, index
+        // 64 u + 4 a + 4 q + s, so two consecutive k-steps are ONE 8-byte read (PH is even: aligned), and with
+        // PH = 2 (mod 4) the 32 lanes of a half wave hit 64 distinct banks whatever the template length.
+        const int rd_chunks = (Ww + 63) >> 6, rt_chunks = (tp_len + 63) >> 6;
+        const int PH = 16 * (rd_chunks | 1) + 2;
+        const int b_base = NTILE == 4 ? kq * PH + 4 * a : 18 * a + kq;
+        // staging register r of a lane holds x = lane + 64 r: one base address and the immediate 16 r floats.  The
+        // surplus lanes of the last chunk fall into their own plane's tail (16 rd_chunks <= PH - 2 entries are written per plane).
+        float* const dws = dw + (lane & 3) * PH + (lane >> 2);
         const int4* __restrict__ recs = FUSED ? nullptr : chan_rec + (size_t)t * (n_ch + 2);
         // FUSED: the records are in LDS; one broadcast read, and the four fields back into SGPRs (the channel
         // number goes into buffer descriptors, the tests on it are scalar branches).  The read is issued in
@@ -833,14 +856,13 @@ __global__ __launch_bounds__(MF_THREADS, 4) void mf_mfma_wave_kernel(
         };
         // Staging registers -> LDS in WHOLE 64-lane chunks, as many as the band / the window need (wave-
         // uniform counts, one scalar jump): the lanes of the last chunk past the end of the band land in
-        // the first floats of the window, which is written afterwards; those past the end of the window in
-        // the 64 floats of slack behind it.  What they carry is real data or the zero fill of the buffer
-        // load, and nobody reads it.  A per-lane `if (x < Ww)` cost 160 instructions per channel (exec masks
+        // the first floats of the window (of its plane 0), which is written afterwards; those past the end of
+        // the window in the tail of their own plane (16 entries per chunk in each of the four).  What they carry
+        // is real data or the zero fill of the buffer load, and nobody reads it.  A per-lane `if (x < Ww)` cost 160 instructions per channel (exec masks
         // per register) -- and an instruction of a wave that is NOT in its K loop waits 40-60 cycles for
         // an issue slot while the other three waves of the SIMD stream MFMAs: 4 500-8 800 cycles per
         // channel and wave for L < 241 against 860 on the full-window path (s_memtime around the stage,
         // profiles/r03_mf_phase_cycles.txt).
-        const int rd_chunks = (Ww + 63) >> 6, rt_chunks = (tp_len + 63) >> 6;
         auto write_stage = [&]() {
             if constexpr (FULLW) {
                 // The small problems' variants write EVERY staging register, needed or not: the band chunks past
@@ -863,7 +885,8 @@ __global__ __launch_bounds__(MF_THREADS, 4) void mf_mfma_wave_kernel(
                 default: break;
             }
 #undef MF_WT
-#define MF_WD(r) case (r) + 1: if constexpr ((r) < MAXR) { const int x = lane + 64 * (r); dw[x + 2 * (x >> 4)] = rd[(r) < MAXR ? (r) : 0]; } [[fallthrough]];
+            // (4 tiles per wave only from here on: the four-phase window)
+#define MF_WD(r) case (r) + 1: if constexpr ((r) < MAXR) dws[16 * (r)] = rd[(r) < MAXR ? (r) : 0]; [[fallthrough]];
             switch (rd_chunks) {
                 MF_WD(19) MF_WD(18) MF_WD(17) MF_WD(16) MF_WD(15) MF_WD(14) MF_WD(13) MF_WD(12) MF_WD(11) MF_WD(10)
                 MF_WD(9) MF_WD(8) MF_WD(7) MF_WD(6) MF_WD(5) MF_WD(4) MF_WD(3) MF_WD(2) MF_WD(1) MF_WD(0)
@@ -924,6 +947,58 @@ __global__ __launch_bounds__(MF_THREADS, 4) void mf_mfma_wave_kernel(
             for (int u = 0; u < NTILE; ++u) acc[u] = (f32x4){0.0f, 0.0f, 0.0f, 0.0f};
             const int nq = Kpad >> 4;
             unsigned ap = (unsigned)(size_t)(tp + a_base), bp = (unsigned)(size_t)(dw + b_base);
+            if constexpr (NTILE == 4) {
+            // Four tiles per wave: operands by PAIRS of k-steps -- one ds_read_b64 per tile for B (the lane's own plane
+            // of the four-phase window, tile u at 256 u bytes), one ds_read2_b32 for A (the two k-steps' band entries are
+            // 4 floats apart) -- 10 LDS instructions per trip of 16 MFMAs instead of 20, in the same 20 registers (two
+            // slots of 5 register pairs).  Operands are requested ONE PAIR ahead, the 5 reads of the next pair between
+            // this pair's MFMAs: on entry the queue reads A B0 B1 B2 B3 of this pair, LDS returns in order, so
+            // lgkmcnt(2) = "A, B0, B1 have landed" and, with the next A behind them, lgkmcnt(1) = "B2, B3 too" (a scalar
+            // record load in flight only makes either stricter).  (One and a half pairs ahead -- every register pair
+            // requested again as soon as its last MFMA has issued, 9 reads in front of the first MFMA of a channel --
+            // was no faster in the bare loop and slower in the channel structure: tools/ubench/mfma_lds.hip modes
+            // 20 - 23, profiles/mf_phase_window.txt.)
+            typedef float f32x2 __attribute__((ext_vector_type(2)));
+            f32x2 pa[2], pb[2][4];
+#define MF_RD_A(slot, o0) \
+    asm volatile("ds_read2_b32 %0, %1 offset0:%2 offset1:%3" : "=v"(pa[slot]) : "v"(ap), "n"(o0), "n"((o0) + 4))
+#define MF_RD_B(slot, u, off) \
+    asm volatile("ds_read_b64 %0, %1 offset:%2" : "=v"(pb[slot][u]) : "v"(bp), "n"((off) + 256 * (u)))
+#define MF_MFMA2(slot, u, j) \
+    acc[u] = __builtin_amdgcn_mfma_f32_16x16x4f32(pa[slot][j], pb[slot][u][j], acc[u], 0, 0, 0)
+#define MF_SB __builtin_amdgcn_sched_barrier(0)
+// the 8 MFMAs of the pair in slot `cur` with the reads of the next pair (A at dword offset ao, B at byte offset bo)
+// into the other slot, each placed behind an MFMA, where it issues for free
+#define MF_PAIR(cur, ao, bo)                                                         \
+    asm volatile("s_waitcnt lgkmcnt(2)" ::: "memory"); MF_SB;                        \
+    MF_MFMA2(cur, 0, 0); MF_SB; MF_RD_A((cur) ^ 1, ao); MF_SB;                       \
+    MF_MFMA2(cur, 1, 0); MF_SB;                                                      \
+    asm volatile("s_waitcnt lgkmcnt(1)" ::: "memory"); MF_SB;                        \
+    MF_MFMA2(cur, 2, 0); MF_SB; MF_RD_B((cur) ^ 1, 0, bo); MF_SB;                    \
+    MF_MFMA2(cur, 3, 0); MF_SB; MF_RD_B((cur) ^ 1, 1, bo); MF_SB;                    \
+    MF_MFMA2(cur, 0, 1); MF_SB; MF_RD_B((cur) ^ 1, 2, bo); MF_SB;                    \
+    MF_MFMA2(cur, 1, 1); MF_SB; MF_RD_B((cur) ^ 1, 3, bo); MF_SB;                    \
+    MF_MFMA2(cur, 2, 1); MF_SB;                                                      \
+    MF_MFMA2(cur, 3, 1); MF_SB
+            MF_SB;
+            if (prio) __builtin_amdgcn_s_setprio(0);
+            MF_RD_A(0, 0);
+            MF_RD_B(0, 0, 0); MF_RD_B(0, 1, 0); MF_RD_B(0, 2, 0); MF_RD_B(0, 3, 0);
+            int q = nq;                     // Kpad >= 16: at least one trip
+            do {
+                MF_PAIR(0, 8, 8);           // k-steps 0, 1; requests k-steps 2, 3
+                MF_PAIR(1, 16, 16);         // k-steps 2, 3; requests k-steps 0, 1 of the next trip (past the last trip: slack)
+                ap += 64;
+                bp += 16;
+            } while (--q > 0);
+            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+            MF_SB;
+#undef MF_RD_A
+#undef MF_RD_B
+#undef MF_MFMA2
+#undef MF_PAIR
+#undef MF_SB
+            } else {
             float sa[4], sb[4][NTILE];
             // counted waits as in mf_mfma_kernel; the ds_writes above are older than every read
             // and complete first (one wave's LDS ops are ordered), so they can only make the
@@ -975,6 +1050,11 @@ __global__ __launch_bounds__(MF_THREADS, 4) void mf_mfma_wave_kernel(
             }
             asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
             __builtin_amdgcn_sched_barrier(0);
+#undef MF_LDS_READ
+#undef MF_MFMA
+#undef MF_REQ
+#undef MF_STEP
+            }
             // option mf.boundary_prio (default 1): a wave outside its K loop (epilogue, staging writes, norm loads,
             // the next channel's loads) asks for a higher issue priority than the waves that stream MFMAs -- its
             // ~250 instructions per channel otherwise wait 40-65 cycles each for a slot behind the other waves'
@@ -985,10 +1065,6 @@ __global__ __launch_bounds__(MF_THREADS, 4) void mf_mfma_wave_kernel(
             if (prio == 1) __builtin_amdgcn_s_setprio(1);
             else if (prio == 2) __builtin_amdgcn_s_setprio(2);
             else if (prio == 3) __builtin_amdgcn_s_setprio(3);
-#undef MF_LDS_READ
-#undef MF_MFMA
-#undef MF_REQ
-#undef MF_STEP
             MF_PHASE(2);
             if constexpr (CSPLIT) {
                 // this channel's CC of the lane's four lags -> row `ri` of the exchange buffer (0 outside the range)
@@ -1000,6 +1076,33 @@ __global__ __launch_bounds__(MF_THREADS, 4) void mf_mfma_wave_kernel(
                     c4[r] = ok ? mf_cc_of<SQRT_NORM>(acc[0][r], et, ed[0][r]) : 0.0f;
                 }
                 *(f32x4*)(exch + ri * 256 + 16 * a + 4 * kq) = c4;
+            } else if constexpr (NETWORK_SUM && STEP1 && NTILE == 4) {
+                // the day-long search: both paths -- every lag of the wave inside the template's valid range (wave-uniform,
+                // all but the first and last tiles of a day: no per-lag tests) or not -- leave the channel's CC values in
+                // the accumulators, and ONE fmaf chain updates the sums in place (two chains left the 16 sums in
+                // different registers: 24 moves at the back edge of the channel loop)
+                if (wave_inside) {
+#pragma unroll
+                    for (int u = 0; u < NTILE; ++u) {
+#pragma unroll
+                        for (int r = 0; r < 4; ++r) acc[u][r] = mf_cc_of<SQRT_NORM>(acc[u][r], et, ed[u][r]);
+                    }
+                } else {
+#pragma unroll
+                    for (int u = 0; u < NTILE; ++u) {
+#pragma unroll
+                        for (int r = 0; r < 4; ++r) {
+                            const long long lag = lag_w + 256 * u + r;
+                            const bool ok = lag >= rg.x && lag <= rg.y;
+                            acc[u][r] = ok ? mf_cc_of<SQRT_NORM>(acc[u][r], et, ed[u][r]) : 0.0f;
+                        }
+                    }
+                }
+#pragma unroll
+                for (int u = 0; u < NTILE; ++u) {
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) sum[u][r] = __fmaf_rn(w, acc[u][r], sum[u][r]);
+                }
             } else if (NETWORK_SUM && STEP1 && wave_inside) {
                 // every lag of this wave is inside the template's valid range (wave-uniform, all
                 // but the first and last tiles of a day): no per-lag range tests

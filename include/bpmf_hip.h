@@ -766,6 +766,41 @@ int bpmf_bandpass_rows_dev(const void *d_x, int in_f64, size_t rows, size_t n_sa
                            size_t n_sections, int detrend, double taper_alpha, int zerophase, int out_f64,
                            void *d_workspace, size_t workspace_bytes, bpmf_stream_t stream, void *d_out);
 
+/* ------------------------------------------- multi-band displacement spectra of a day's events --- */
+/*
+ * Spectrum.compute_multi_band_spectrum (BPMF/spectrum.py:387-505, method "multiband" of compute_moment_magnitude) for
+ * every window of a day in HBM in one call (spectrum.hip).  Windows are addressed as bpmf_normalize_batch_dev
+ * addresses them: window w < n_windows = E * S starts at d_start[w] on station w % S; row (w, c), c < C, is
+ *     x[i] = d_data[w % S, c, d_start[w] + i]                                                (i = 0 .. n_samples-1)
+ * In float64 throughout (the definition is seismic_bpmf_amd.postprocess.multiband_spectrum_host; obspy's detrend,
+ * taper and filter are restated there from their documented behaviour):
+ *   1. the mean is subtracted, then the least-squares line (closed form about the middle index, as
+ *      bpmf_bandpass_rows_dev), both from compensated sums;
+ *   2. sample i and sample n_samples - 1 - i, i < taper, are multiplied by 0.5 (1 - cos(pi i / taper));
+ *   3. for every band b with skip[b] == 0 the cascade of the n_sections sections d_sos[b] runs from zero state in
+ *      SciPy's operation order, forward and then over the reversed result;
+ *   4. d_out[w, c, b] = max |y[k]| over buffer <= k < n_samples - buffer, divided by bandwidths[b]; a NaN in that
+ *      range gives NaN.  A band with skip[b] != 0 gives +0.
+ * A window that is not wholly inside [0, N) is not processed: its outputs are +0 and d_valid[w] = 0 (1 elsewhere).
+ *   d_data (S, C, N) f32; d_start (n_windows) i64 on the device, clamped to +-2^40; d_sos (n_bands, n_sections, 6) f64
+ *   on the device, a0 = 1; bandwidths (n_bands) f64 and skip (n_bands) u8 ON THE HOST (read before the call returns);
+ *   d_out (n_windows, C, n_bands) f64; d_valid (n_windows) u8.  Every element of both outputs is written.
+ * Workspace: a row takes (4 + (1 + n_active) n_samples) * 8 bytes, n_active the bands that are not skipped; the rows
+ * go through in slabs of a multiple of 64 that fit, so 64 rows' worth are the least.  A row gives the same bits in any
+ * slab and any batch.  bpmf_multiband_workspace_bytes returns what n_rows = n_windows * C rows take in one slab (n_rows
+ * rounded up to 64), or 0 for sizes that the call refuses.  Asynchronous on `stream`.
+ * Returns -1 for a null pointer, S * C == 0, N == 0 or above 2^40, n_windows no multiple of S, n_samples == 0 or above
+ * 16384, buffer == 0, n_samples <= 2 buffer, taper > n_samples / 4, n_bands outside 1 .. 64, n_sections outside 1 .. 8,
+ * n_windows * C * n_bands >= 2^31, a band that is not skipped with a bandwidth that is no positive number, or a
+ * workspace smaller than 64 rows.  n_windows == 0 launches nothing and returns 0.
+ */
+size_t bpmf_multiband_workspace_bytes(size_t n_rows, size_t n_samples, size_t n_active_bands);
+int bpmf_multiband_spectrum_dev(const float *d_data, size_t S, size_t C, size_t N, size_t n_windows,
+                                const int64_t *d_start, size_t n_samples, size_t taper, size_t buffer,
+                                const double *d_sos, size_t n_bands, size_t n_sections, const double *bandwidths,
+                                const uint8_t *skip, void *d_workspace, size_t workspace_bytes, bpmf_stream_t stream,
+                                double *d_out, uint8_t *d_valid);
+
 /* ------------------------------------------- events detected by several templates --- */
 /*
  * The loop of TemplateGroup.remove_multiples (BPMF/dataset.py:5214-5282) on a catalog that is ALREADY in the

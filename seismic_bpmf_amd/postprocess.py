@@ -1536,3 +1536,188 @@ def svdwf_stack_host(x, offsets=None, *, expl_var=0.4, max_singular_values=5, wi
         norm[norm == 0.0] = 1.0
         stack[g] = (mean / norm).astype(np.float32)
     return filtered, stack, rank
+
+
+# ---- multi-band displacement spectra (BPMF/spectrum.py: Spectrum.compute_multi_band_spectrum :387-505,
+# ---- compute_signal_to_noise_ratio :601-648) ----
+# The reference runs three obspy operations on every trace and band.  obspy was not at hand when this was written: the
+# three are RESTATED here from obspy's documented behaviour, and stay unverified against obspy itself until
+# tools/diff_obspy_multiband.py (or tests/test_multiband_obspy_live.py) runs next to a real obspy:
+#   tr.detrend("constant") / tr.detrend("linear")        = scipy.signal.detrend(data, type=...)
+#   tr.taper(0.25, max_length=L, type="cosine")          = a half-Hann of w = min(int(0.25 npts), int(L sr)) samples on
+#                                                          each side, 0.5 (1 - cos(pi i / w)), i < w
+#   tr.filter("bandpass", corners=, zerophase=True)      = iirfilter -> zpk2sos -> sosfilt, forward and on the reversed
+#                                                          output
+MULTIBAND_MAX_SAMPLES = 16384
+MULTIBAND_MAX_BANDS = 64
+MULTIBAND_NYQUIST_MARGIN = 1e-6       # obspy turns a band whose upper corner is this close below Nyquist into a high-pass
+
+
+def multiband_bands(frequency_bands):
+    """The reference's `frequency_bands` -- a dict {name: [lo, hi]} in its order, or a (B, 2) array, in Hz -- as a
+    (B, 2) float64 array.  Raises ValueError for anything else, for B outside 1 .. 64, and for a band with lo <= 0 or
+    lo >= hi."""
+    if isinstance(frequency_bands, dict):
+        frequency_bands = [frequency_bands[k] for k in frequency_bands]
+    try:
+        bands = np.array(frequency_bands, dtype=np.float64)
+    except (TypeError, ValueError):
+        raise ValueError("multiband: frequency_bands must be a dict {name: [lo, hi]} or a (B, 2) array") from None
+    if bands.ndim != 2 or bands.shape[1] != 2:
+        raise ValueError(f"multiband: frequency_bands must be a dict {{name: [lo, hi]}} or a (B, 2) array; got the "
+                         f"shape {bands.shape}")
+    if not 1 <= len(bands) <= MULTIBAND_MAX_BANDS:
+        raise ValueError(f"multiband: 1 .. {MULTIBAND_MAX_BANDS} frequency bands; got {len(bands)}")
+    bad = ~((bands[:, 0] > 0) & (bands[:, 0] < bands[:, 1]) & np.isfinite(bands[:, 1]))
+    if bad.any():
+        b = int(np.flatnonzero(bad)[0])
+        raise ValueError(f"multiband: band {b} = [{bands[b, 0]}, {bands[b, 1]}] Hz; need 0 < lo < hi")
+    return bands
+
+
+def multiband_plan(n_samples, frequency_bands, sr, buffer_seconds, corners=4):
+    """What a multi-band call works with, and its refusals.  Returns a dict: `bands` (B, 2) Hz; `taper` w =
+    min(int(0.25 n), int(buffer_seconds sr)) and `buffer` = int(buffer_seconds sr) in samples, both int() as the
+    reference and obspy take them; `skip` (B,) bool: hi >= sr / 2, the reference's `continue`; `sos` (B, corners, 6):
+    butter_bandpass_sos of every band that is not skipped (a skipped band holds pass-through sections); `bandwidth`
+    (B,) = hi - lo; `freq` (B,) float32 = 0.5 (lo + hi), skipped bands included.  Raises ValueError: bad bands
+    (multiband_bands); corners outside 1 .. 8; buffer == 0 or n <= 2 buffer, where the reference's data[buf:-buf] is
+    empty and it returns zeros; a band with (1 - 1e-6) sr / 2 < hi < sr / 2, which obspy silently turns into a
+    high-pass (not restated here)."""
+    n, sr = int(n_samples), float(sr)
+    bands = multiband_bands(frequency_bands)
+    corners = int(corners)
+    if not 1 <= corners <= BANDPASS_MAX_SECTIONS:
+        raise ValueError(f"multiband: corners must be 1 .. {BANDPASS_MAX_SECTIONS}; got {corners}")
+    if not sr > 0 or not float(buffer_seconds) >= 0:
+        raise ValueError(f"multiband: need sr > 0 and buffer_seconds >= 0; got {sr}, {buffer_seconds}")
+    buf = int(buffer_seconds * sr)
+    if buf == 0 or n <= 2 * buf:
+        raise ValueError(f"multiband: windows of {n} samples with buffers of {buf}: the trimmed range data[buf:-buf] is "
+                         "empty (the reference returns all zeros there); need buffer >= 1 sample and n > 2 buffer")
+    w = min(int(0.25 * n), buf)
+    nyq = sr / 2.0
+    skip = bands[:, 1] >= nyq
+    near = (bands[:, 1] > (1.0 - MULTIBAND_NYQUIST_MARGIN) * nyq) & ~skip
+    if near.any():
+        b = int(np.flatnonzero(near)[0])
+        raise ValueError(f"multiband: band {b} ends at {bands[b, 1]} Hz, within 1e-6 below the Nyquist frequency "
+                         f"{nyq} Hz: obspy silently turns such a band-pass into a high-pass, which is not served")
+    sos = np.zeros((len(bands), corners, 6))
+    sos[:, :, 0] = sos[:, :, 3] = 1.0
+    for b, (lo, hi) in enumerate(bands):
+        if not skip[b]:
+            sos[b] = butter_bandpass_sos(corners, lo / nyq, hi / nyq)
+    return {"bands": bands, "taper": w, "buffer": buf, "skip": skip, "sos": sos,
+            "bandwidth": bands[:, 1] - bands[:, 0], "freq": (0.5 * (bands[:, 0] + bands[:, 1])).astype(np.float32)}
+
+
+def multiband_prepare_host(windows, taper):
+    """Steps 1-3 of the definition on (rows, n) float32 windows: float64 rows with the mean subtracted
+    (v -= sum(v) / n), the least-squares line removed (with t_k = k - (n - 1) / 2: minus (sum(v t) / sum(t^2)) t_k +
+    sum(v) / n, slope 0 where sum(t^2) = 0), and a half-Hann of `taper` samples, 0.5 (1 - cos(pi i / taper)), on each
+    side (0: none).  The sums are exact (math.fsum), so that no summation order shows."""
+    import math
+    v = np.array(windows, dtype=np.float64)
+    rows, n = v.shape
+    t = np.arange(n, dtype=np.float64) - (n - 1) / 2.0
+    den = math.fsum(t * t)
+    for r in range(rows):
+        v[r] -= math.fsum(v[r]) / n
+        slope = math.fsum(v[r] * t) / den if den > 0 else 0.0
+        v[r] -= slope * t + math.fsum(v[r]) / n
+    if taper:
+        g = 0.5 * (1.0 - np.cos(np.pi * np.arange(taper, dtype=np.float64) / taper))
+        v[:, :taper] *= g
+        v[:, n - taper:] *= g[::-1]
+    return v
+
+
+def _sosfilt_bands(sos, x):
+    """sosfilt_rows for several filters at once: `sos` (A, n_sections, 6), `x` (m, A, rows) time-major; element by
+    element the same operations in the same order, so bit for bit sosfilt_rows(sos[a], x[:, a, :].T).T."""
+    y = np.array(x, dtype=np.float64)
+    m, A, rows = y.shape
+    n_sec = sos.shape[1]
+    z = np.zeros((n_sec, 2, A, rows))
+    coef = [[np.ascontiguousarray(sos[:, s, j])[:, None] for j in range(6)] for s in range(n_sec)]
+    for t in range(m):
+        cur = y[t].copy()
+        for s in range(n_sec):
+            b0, b1, b2, _, a1, a2 = coef[s]
+            new = b0 * cur + z[s, 0]
+            z[s, 0] = (b1 * cur - a1 * new) + z[s, 1]
+            z[s, 1] = b2 * cur - a2 * new
+            cur = new
+        y[t] = cur
+    return y
+
+
+def multiband_spectrum_host(windows, frequency_bands, *, sr, buffer_seconds, corners=4, multi_component=False):
+    """The definition of the multi-band spectra: Spectrum.compute_multi_band_spectrum (BPMF/spectrum.py:387-505) on
+    plain arrays, float64 throughout, NumPy only.  `windows` (..., n) float32, one trace each (noise, P or S window;
+    (..., C, n) with `multi_component`).  Per window: multiband_prepare_host (detrend "constant", detrend "linear",
+    the cosine taper of min(int(0.25 n), int(buffer_seconds sr)) samples); per band with hi < sr / 2 the Butterworth
+    band-pass of `corners` corners (butter_bandpass_sos) forward from zero state and over the reversed result from
+    zero state (as sosfilt_rows: SciPy's operation order); a = max |y[k]| over buf <= k < n - buf, buf =
+    int(buffer_seconds sr), divided by hi - lo; a NaN in that range gives NaN.  A band with hi >= sr / 2 gives 0.
+    `multi_component`: sqrt(sum over the components a^2), in component order.  Returns (spectra (..., B) float64,
+    freq (B,) float32 = 0.5 (lo + hi)).  Refusals: multiband_plan.
+
+    obspy's detrend, taper and filter are restated from their documented behaviour (see the section comment); the
+    arithmetic around them is pinned to the reference in tests/test_multiband_host.py."""
+    x = np.asarray(windows, dtype=np.float32)
+    if x.ndim < (2 if multi_component else 1):
+        raise ValueError("multiband_spectrum_host: windows must be (..., n), or (..., C, n) with multi_component")
+    n = x.shape[-1]
+    plan = multiband_plan(n, frequency_bands, sr, buffer_seconds, corners)
+    buf, B = plan["buffer"], len(plan["bands"])
+    lead = x.shape[:-1]
+    out = np.zeros((int(np.prod(lead, dtype=np.int64)), B))
+    live = np.flatnonzero(~plan["skip"])
+    if out.shape[0] and len(live):
+        v = multiband_prepare_host(x.reshape(-1, n), plan["taper"])
+        y = _sosfilt_bands(plan["sos"][live], np.broadcast_to(v.T[:, None, :], (n, len(live), len(v))))
+        y = _sosfilt_bands(plan["sos"][live], y[::-1])[::-1]
+        out[:, live] = (np.max(np.abs(y[buf:n - buf]), axis=0) / plan["bandwidth"][live, None]).T
+    out = out.reshape(lead + (B,))
+    if multi_component:
+        total = np.zeros(lead[:-1] + (B,))
+        for c in range(lead[-1]):
+            total += out[..., c, :] * out[..., c, :]
+        out = np.sqrt(total)
+    return out, plan["freq"]
+
+
+def multiband_windows_host(data, starts, n_samples):
+    """The windows a multi-band call works on: (windows (E, S, C, n_samples) float32, valid (E, S) bool).
+    windows[e, s, c] = data[s, c, starts[e(, s)] : + n_samples] of the (S, C, N) day where that range lies wholly inside
+    the day (valid); elsewhere zeros and valid = False -- the reference would go on with the shorter trace it managed
+    to read, which is not served.  `starts` (E,) or (E, S) integers (picker_starts)."""
+    data = np.asarray(data, dtype=np.float32)
+    if data.ndim != 3:
+        raise ValueError("multiband_windows_host: data must be (S, C, N)")
+    S, C, N = data.shape
+    n = int(n_samples)
+    st = picker_starts(starts, S)
+    valid = (st >= 0) & (st + n <= N)
+    windows = _clipped_windows(data, np.broadcast_to(st[:, :, None], st.shape + (C,)), n)
+    windows[~valid] = 0.0
+    return windows, valid
+
+
+def spectral_snr_host(signal, noise, noise_valid=None):
+    """Spectrum.compute_signal_to_noise_ratio (BPMF/spectrum.py:601-648) on arrays of equal shape (..., B): 0 where
+    signal and noise are both 0, |signal| / |noise| elsewhere (inf included), and 0 where the noise spectrum is missing:
+    `noise_valid` (...) bool, the `valid` of the noise windows, broadcast over the trailing axes."""
+    signal, noise = np.abs(np.asarray(signal, dtype=np.float64)), np.abs(np.asarray(noise, dtype=np.float64))
+    if signal.shape != noise.shape:
+        raise ValueError(f"spectral_snr_host: signal {signal.shape} and noise {noise.shape} differ in shape")
+    snr = np.zeros(signal.shape)
+    keep = ~((signal == 0.0) & (noise == 0.0))
+    if noise_valid is not None:
+        nv = np.asarray(noise_valid, dtype=bool)
+        keep &= nv.reshape(nv.shape + (1,) * (signal.ndim - nv.ndim))
+    with np.errstate(divide="ignore", invalid="ignore"):
+        snr[keep] = signal[keep] / noise[keep]
+    return snr

@@ -711,6 +711,113 @@ def svdwf_stack(x_dev, offsets=None, *, expl_var=0.4, max_singular_values=5, wie
     return stack, filtered, n_singular, status
 
 
+MULTIBAND_MAX_SAMPLES = pp.MULTIBAND_MAX_SAMPLES
+MULTIBAND_WORKSPACE_BYTES = 4 << 30        # multiband_spectra: the workspace it asks for at most (and at least 64 rows)
+
+
+def multiband_spectra(data_dev, starts, n_samples, frequency_bands, *, sr, buffer_seconds, corners=4,
+                      multi_component=False, workspace_bytes=MULTIBAND_WORKSPACE_BYTES):
+    """Spectrum.compute_multi_band_spectrum (BPMF/spectrum.py:387-505; method "multiband" of
+    compute_moment_magnitude) for the windows of E events, cut from the day in HBM, in one call
+    (bpmf_multiband_spectrum_dev, csrc/spectrum.hip): per window the mean and the least-squares line are removed, a
+    cosine taper of min(int(0.25 n), int(buffer_seconds sr)) samples is applied on each side, and per frequency band
+    the zero-phase Butterworth band-pass of `corners` corners runs over it; the spectrum is max |y| over the window
+    less `buffer_seconds` at either end, divided by the bandwidth.  Only these maxima are stored.
+
+    `data_dev`: the (S, C, N) day as a tensor on the GPU, in the units the spectra are wanted in (the instrument
+    response is the caller's); `starts` (E,) or (E, S) int64 window starts in samples as in picker_batch;
+    `frequency_bands` the reference's dict {name: [lo, hi]} in its order, or a (B, 2) array, in Hz; `sr` in Hz.  The
+    noise, P and S windows of the reference's extract_windows are three calls, or one on concatenated starts.
+    Returns (spectra, freq, valid) on the day's device and the current stream: `spectra` (E, S, C, B) float64, or
+    (E, S, B) with `multi_component` (sqrt of the sum over the components of the squares); `freq` (B,) float32, the
+    band centres; `valid` (E, S) bool.  A band with hi >= sr / 2 gives 0, as the reference skips it.  The definition
+    is postprocess.multiband_spectrum_host of postprocess.multiband_windows_host; obspy's detrend, taper and filter
+    are RESTATED there from their documented behaviour and not yet verified against obspy itself
+    (tools/diff_obspy_multiband.py).  A window gives the same bits in any batch and with any `workspace_bytes` (the
+    rows go through in slabs of a multiple of 64 that fit it).
+
+    DEPARTURE: a window that is not wholly inside the day gives zeros and valid = False; the reference would filter
+    the shorter trace it managed to read.
+
+    Refusals (ValueError, before any device call): data_dev not a GPU tensor or not (S, C, N); n_samples over 16384;
+    int(buffer_seconds sr) == 0 or n_samples <= twice that (the reference's data[buf:-buf] is empty there and it
+    returns zeros); B outside 1 .. 64; corners outside 1 .. 8; a band with lo <= 0 or lo >= hi; a band with
+    (1 - 1e-6) sr / 2 < hi < sr / 2 (obspy silently turns it into a high-pass); rows x B >= 2^31; a workspace too small
+    for 64 rows.  Out of scope: the FFT method, response removal, propagation corrections, averaging and model fits."""
+    import ctypes as C
+    import torch
+    from . import _lib
+    if not isinstance(data_dev, torch.Tensor) or not data_dev.is_cuda:
+        raise ValueError("multiband_spectra: data_dev must be a tensor on the GPU (there is no CPU path; the definition "
+                         "on the host is postprocess.multiband_spectrum_host of postprocess.multiband_windows_host)")
+    if data_dev.dim() != 3:
+        raise ValueError("multiband_spectra: data_dev must be (S, C, N)")
+    S, Cc, N = (int(v) for v in data_dev.shape)
+    n = int(n_samples)
+    if not 1 <= n <= MULTIBAND_MAX_SAMPLES:
+        raise ValueError(f"multiband_spectra: windows of 1 .. {MULTIBAND_MAX_SAMPLES} samples; got {n}")
+    plan = pp.multiband_plan(n, frequency_bands, sr, buffer_seconds, corners)
+    if isinstance(starts, torch.Tensor):
+        starts = starts.detach().cpu().numpy()
+    st = pp.picker_starts(starts, S)
+    E, B = len(st), len(plan["bands"])
+    if S * Cc == 0 or N == 0:
+        raise ValueError("multiband_spectra: the data are empty")
+    rows = st.size * Cc
+    if rows * B >= 2**31:
+        raise ValueError(f"multiband_spectra: {rows} rows x {B} bands in one call; fewer than 2^31 values fit")
+    n_active = int((~plan["skip"]).sum())
+    row_bytes = (4 + (1 + n_active) * n) * 8
+    workspace_bytes = int(workspace_bytes)
+    if workspace_bytes < 64 * row_bytes:
+        raise ValueError(f"multiband_spectra: workspace_bytes = {workspace_bytes}; 64 rows of {n} samples and "
+                         f"{n_active} active bands take {64 * row_bytes}")
+    dev = data_dev.device
+    with torch.cuda.device(dev):
+        freq = torch.as_tensor(plan["freq"], device=dev)
+        spectra = torch.empty((E, S, Cc, B), dtype=torch.float64, device=dev)
+        valid = torch.empty((E, S), dtype=torch.uint8, device=dev)
+        if E:
+            lib = _lib.lib()
+            x = data_dev.to(dtype=torch.float32).contiguous()
+            d_start = torch.as_tensor(st.reshape(-1), device=dev)
+            d_sos = torch.as_tensor(np.ascontiguousarray(plan["sos"]), device=dev)
+            n_bytes = min(workspace_bytes, int(lib.bpmf_multiband_workspace_bytes(rows, n, n_active)))
+            ws = torch.empty((n_bytes,), dtype=torch.uint8, device=dev)
+            bandwidth = np.ascontiguousarray(plan["bandwidth"], dtype=np.float64)
+            skip = np.ascontiguousarray(plan["skip"], dtype=np.uint8)
+            rc = lib.bpmf_multiband_spectrum_dev(
+                C.c_void_p(x.data_ptr()), S, Cc, N, st.size, C.c_void_p(d_start.data_ptr()), n, plan["taper"],
+                plan["buffer"], C.c_void_p(d_sos.data_ptr()), B, int(plan["sos"].shape[1]),
+                bandwidth.ctypes.data_as(C.POINTER(C.c_double)), skip.ctypes.data_as(C.POINTER(C.c_uint8)),
+                C.c_void_p(ws.data_ptr()), n_bytes, C.c_void_p(torch.cuda.current_stream(dev).cuda_stream),
+                C.c_void_p(spectra.data_ptr()), C.c_void_p(valid.data_ptr()))
+            _lib.check(rc, "bpmf_multiband_spectrum_dev")
+        if multi_component:
+            total = torch.zeros((E, S, B), dtype=torch.float64, device=dev)
+            for c in range(Cc):                                        # in component order, as the reference adds
+                total = total + spectra[:, :, c] * spectra[:, :, c]
+            spectra = torch.sqrt(total)
+        return spectra, freq, valid.to(torch.bool)
+
+
+def multiband_snr(signal, noise, noise_valid=None):
+    """Spectrum.compute_signal_to_noise_ratio (BPMF/spectrum.py:601-648) on two results of multiband_spectra of equal
+    shape (..., B), on their device: 0 where signal and noise are both 0, |signal| / |noise| elsewhere (inf included),
+    and 0 where the noise spectrum is missing -- `noise_valid` (...) bool, the `valid` of the noise windows, broadcast
+    over the bands (and over the components).  A few elementwise operations on small tensors; the definition is
+    postprocess.spectral_snr_host, which it equals exactly."""
+    import torch
+    if not isinstance(signal, torch.Tensor) or not isinstance(noise, torch.Tensor) or signal.shape != noise.shape:
+        raise ValueError("multiband_snr: signal and noise must be tensors of equal shape (..., B)")
+    s, z = signal.abs(), noise.abs()
+    keep = ~((s == 0) & (z == 0))
+    if noise_valid is not None:
+        nv = torch.as_tensor(noise_valid, dtype=torch.bool, device=s.device)
+        keep = keep & nv.reshape(tuple(nv.shape) + (1,) * (s.dim() - nv.dim()))
+    return torch.where(keep, s / z, torch.zeros_like(s))
+
+
 def _peak_amplitude_window(sr, offset_win_peak_amp_sec, duration_win_peak_amp_sec):
     """(offset, duration) in samples, as MatchedFilter.set_data converts them (BPMF/similarity_search.py:175-180)."""
     return (int(pp.sec_to_samp(offset_win_peak_amp_sec, sr)), int(pp.sec_to_samp(duration_win_peak_amp_sec, sr)))

@@ -14,7 +14,8 @@
 //                         the matrix and to the rows of the transposed eigenvector matrix (coalesced), in the global
 //                         workspace.  A pair with |g_pq| <= 2^-52 sqrt(g_pp g_qq) is skipped; the solve ends with the
 //                         first sweep that rotates nothing, or at the sweep cap (status 1, the channel's output is
-//                         zeros).  Then: the eight largest eigenvalues, their sum with the rest (= sum sigma^2), and
+//                         zeros).  A channel that holds a NaN or an Inf -- a diagonal element of its Gram matrix
+//                         is not finite -- is not solved at all: status 1 as well.  Then: the eight largest eigenvalues, their sum with the rest (= sum sigma^2), and
 //                         k = min(max_singular_values, 1 + first j with cumsum_j / sum >= expl_var); sum == 0: k = 0.
 //   3. sv_project_kernel  P_j = a_j b_j^T for j < k: a_j = u_j, b_j = A^T u_j on the event side; b_j = v_j,
 //                         a_j = A v_j on the sample side (= sigma_j u_j v_j^T either way; the sign cancels).
@@ -166,6 +167,16 @@ __global__ __launch_bounds__(SV_JACOBI_THREADS) void sv_jacobi_kernel(const SvCa
     double* __restrict__ V = ch.V;
     const double eps = 2.220446049250313e-16;                          // 2^-52
     int status = 1, sweeps = 0;
+    // every sample is squared into one diagonal element: a NaN or an Inf anywhere in the channel shows there
+    if (tid == 0) rotated = 0;
+    __syncthreads();
+    for (int d = tid; d < K; d += SV_JACOBI_THREADS) {
+        const double g = G[(size_t)d * Kp + d];
+        if (!(g - g == 0.0)) rotated = 1;
+    }
+    __syncthreads();
+    if (rotated) max_sweeps = 0;                                       // not solved: status 1
+    __syncthreads();
     for (int sweep = 0; sweep < max_sweeps; ++sweep) {
         if (tid == 0) rotated = 0;
         __syncthreads();

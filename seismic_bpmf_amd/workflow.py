@@ -644,8 +644,9 @@ def svdwf_stack(x_dev, offsets=None, *, expl_var=0.4, max_singular_values=5, wie
     channel's largest |filtered| and 2^-21 on the stack.  `workspace`: a uint8 tensor to work in (at
     least one channel's worth, bpmf_svdwf_workspace_bytes); by default up to 2 GiB are allocated for the call.
 
-    Departure: where LAPACK fails the reference returns Gaussian noise; here `status` reports it.  Out of scope:
-    non-finite input, fetching the waveforms, the Stack object."""
+    Departure: where LAPACK fails the reference returns Gaussian noise; here `status` reports it.  A channel that
+    holds a NaN or an Inf is not solved: it has status 1 and zero outputs, and every other channel of the batch has
+    the bits it has without it.  Out of scope: fetching the waveforms, the Stack object."""
     import ctypes as C
     import torch
     from . import _lib
@@ -705,8 +706,8 @@ def svdwf_stack(x_dev, offsets=None, *, expl_var=0.4, max_singular_values=5, wie
         n_singular, status = n_singular.cpu().numpy(), status.cpu().numpy()
     if strict and status.any():
         bad = np.argwhere(status != 0)[0]
-        raise RuntimeError(f"svdwf_stack: the eigen-solve of {int((status != 0).sum())} channel(s) did not converge "
-                           f"(first: group {bad[0]}, station {bad[1]}, component {bad[2]}); pass strict=False to get "
+        raise RuntimeError(f"svdwf_stack: the eigen-solve of {int((status != 0).sum())} channel(s) did not converge, "
+                           f"or the channel holds a NaN or an Inf (first: group {bad[0]}, station {bad[1]}, component {bad[2]}); pass strict=False to get "
                            "zeros there and the status array")
     return stack, filtered, n_singular, status
 

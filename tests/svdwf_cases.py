@@ -2,7 +2,8 @@
 tests/golden/make_svdwf_golden.py): the (n, m) matrices of one channel's detections -- two Gaussian wavelets with
 random amplitudes per event plus white noise, float32 --, the parameter sets, the ragged batch, and the conditions
 every case must meet before a device result is compared with the definition within limits that are derived and not
-measured: `conditions` asserts them on the CPU."""
+measured: `conditions` asserts them on the CPU.  `degenerate_cases` are the spectra that generator never gives --
+rank-deficient, duplicated, badly scaled, clustered -- and `jacobi_reference` the device's eigen-solver restated."""
 import numpy as np
 
 SAMPLING_RATE = 25.0
@@ -143,6 +144,148 @@ def conditions(a, expl_var, max_singular_values):
     nxt = np.append(s2, 0.0)
     assert (s2[:k] - nxt[1:k + 1] >= 1e-4 * s2[0]).all(), (s2[:k + 1] / s2[0])
     return k
+
+
+def conditions_subspace(a, expl_var, max_singular_values):
+    """`conditions` for a matrix whose retained singular values may be equal among themselves: finite input, var away
+    from expl_var by 1e-4, and sigma_k^2 - sigma_(k+1)^2 >= 1e-4 sigma_1^2 for the LAST retained value only.  What is
+    then unique is the projector onto the retained subspace, not the vectors.  Returns k."""
+    a = np.asarray(a, dtype=np.float64)
+    assert np.isfinite(a).all()
+    s2 = np.linalg.svd(a, compute_uv=False) ** 2
+    assert s2.sum() > 0.0 and expl_var < 1.0
+    var = np.cumsum(s2) / s2.sum()
+    assert (np.abs(var[:max_singular_values] - expl_var) > 1e-4).all(), (var[:8], expl_var)
+    k = min(max_singular_values, int(np.flatnonzero(var >= expl_var)[0]) + 1)
+    nxt = np.append(s2, 0.0)
+    assert s2[k - 1] - nxt[k] >= 1e-4 * s2[0], (k, s2[:k + 1] / s2[0])
+    return k
+
+
+# ---- degenerate spectra: rank-deficient, duplicated, badly scaled and clustered matrices ----
+EQUAL_SIGMA = "equal sigma 6x200"
+JACOBI_REFERENCE_MAX_K = 128             # jacobi_reference is a test helper: about a second at this order
+
+
+def degenerate_params(n):
+    """(expl_var, max_singular_values, w, band-pass) of the degenerate cases."""
+    return [(0.4, 5, None, True), (0.8, 5, 4, False), (0.8, 5, 1, False), (0.8, 8, n + 3, True)]
+
+
+def fixed_wavelets(r, m):
+    """(r, m) float64: r linearly independent Gaussian wavelets, the same for every event."""
+    t = np.arange(m, dtype=np.float64)
+    return np.stack([np.exp(-0.5 * ((t - (j + 1.0) / (r + 1.0) * m) / (0.04 * m + 1.0)) ** 2) * np.cos((0.2 + 0.15 * j) * t)
+                     for j in range(r)])
+
+
+def low_rank(n, m, r, seed):
+    """(n, m) float32 without noise: random amplitudes on r fixed wavelets (rank r up to the float32 rounding)."""
+    rng = np.random.default_rng([seed, n, m, r])
+    amplitudes = rng.uniform(0.5, 2.0, (n, r)) * rng.choice([-1.0, 1.0], (n, r))
+    return (amplitudes @ fixed_wavelets(r, m)).astype(np.float32)
+
+
+def equal_sigma_matrix():
+    """6 x 200 float32, sigma_1 = sigma_2 exactly: rows 0-2 carry one wavelet on samples 0 .. 99, rows 3-5 the same
+    wavelet moved to samples 100 .. 199 (same float32 values: equal norm), with the same three amplitudes."""
+    t = np.arange(100, dtype=np.float64)
+    w = (np.exp(-0.5 * ((t - 50.0) / 9.0) ** 2) * np.cos(0.5 * t)).astype(np.float32)
+    x = np.zeros((6, 200), dtype=np.float32)
+    for i, amplitude in enumerate((1.0, 2.0, 0.5)):
+        x[i, :100] = np.float32(amplitude) * w
+        x[3 + i, 100:] = np.float32(amplitude) * w
+    return x
+
+
+def degenerate_cases():
+    """[(label, (n, m) float32 matrix, [(expl_var, max_singular_values, w, band-pass), ...])]: the spectra real groups
+    have and `matrix` does not -- events without data, duplicated detections, noise-free stacks, one event far above
+    the others, physical units, constant traces, and two equal singular values (EQUAL_SIGMA: conditions_subspace)."""
+    out = []
+
+    def add(label, x, first_only=False):
+        assert x.dtype == np.float32
+        params = degenerate_params(len(x))
+        out.append((f"{label} {x.shape[0]}x{x.shape[1]}", x, params[:1] if first_only else params))
+
+    x = matrix(40, 200, 501)
+    x[np.random.default_rng(502).choice(40, 15, replace=False)] = 0.0
+    add("zero rows", x)
+    x = matrix(8, 200, 503)
+    x[4:] = 0.0
+    add("zero rows", x)
+    for n, m, seed in ((40, 200, 504), (512, 600, 505)):
+        x = matrix(n, m, seed)
+        x[n // 2:] = x[:n // 2]
+        add("duplicated rows", x, first_only=n == 512)
+    add("identical rows", np.repeat(matrix(1, 200, 506), 7, axis=0))
+    for r, n, m in ((3, 40, 200), (2, 7, 200), (5, 300, 96), (2, 512, 600)):
+        add(f"low rank {r}", low_rank(n, m, r, 507), first_only=n == 512)
+    x = matrix(40, 200, 508)
+    x[17] *= np.float32(1e4)
+    add("one event x 1e4", x)
+    add("scaled by 1e-9", matrix(40, 200, 509) * np.float32(1e-9))
+    add("scaled by 1e15", matrix(40, 200, 510) * np.float32(1e15))
+    add("constant rows", np.repeat(np.random.default_rng(511).uniform(-2.0, 2.0, (7, 1)).astype(np.float32), 200, axis=1))
+    out.append((EQUAL_SIGMA, equal_sigma_matrix(), degenerate_params(6)))
+    return out
+
+
+def gram(a):
+    """The float64 Gram matrix the device diagonalises: over the events for n <= m, over the samples otherwise."""
+    a = np.asarray(a, dtype=np.float32).astype(np.float64)
+    return a @ a.T if a.shape[0] <= a.shape[1] else a.T @ a
+
+
+def jacobi_reference(G, max_sweeps=60, defect=None):
+    """The eigen-solve of csrc/svdwf.hip's header restated in float64 NumPy, one round-robin step at a time: the (K, K)
+    matrix padded with a zero row and column to even order Kp; step `step` of a sweep pairs a = (step + i) % (Kp - 1)
+    with b = Kp - 1 (i = 0) or (step + Kp - 1 - i) % (Kp - 1), i < Kp / 2; a pair with
+    |g_pq| <= 2^-52 sqrt|g_pp| sqrt|g_qq| is skipped; tau = (g_qq - g_pp) / 2 g_pq,
+    t = sign(tau) / (|tau| + sqrt(1 + tau^2)), c = 1 / sqrt(1 + t^2), s = t c; the columns are rotated, then the rows,
+    and the rotated element is set to zero; the solve ends with the first sweep that rotates nothing.  Returns
+    (sweeps, status, eigenvalues (K,) in index order): status 1 at the cap, and with no sweep at all where a diagonal
+    element is not finite (a NaN or an Inf in the channel), as in the kernel.  `defect` plants one for the tests."""
+    G = np.asarray(G, dtype=np.float64)
+    K = len(G)
+    Kp = K + (K & 1)
+    A = np.zeros((Kp, Kp))
+    A[:K, :K] = G
+    M1, i = Kp - 1, np.arange(Kp // 2)
+    eps = 2.0 ** -52
+    sweeps, status = 0, 1
+    if not np.isfinite(np.diag(G)).all():
+        return 0, 1, np.diag(G).copy()
+    with np.errstate(all="ignore"):
+        for sweep in range(max_sweeps):
+            rotated = False
+            for step in range(M1):
+                a, b = (step + i) % M1, np.where(i == 0, M1, (step + M1 - i) % M1)
+                p, q = np.minimum(a, b), np.maximum(a, b)
+                gpp, gqq, gpq = A[p, p], A[q, q], A[p, q]
+                skip = np.abs(gpq) <= eps * (np.sqrt(np.abs(gpp)) * np.sqrt(np.abs(gqq)))
+                if defect == "a pair whose g_pp is 0 or below skipped":
+                    skip = skip | (gpp <= 0.0) | (gqq <= 0.0)
+                tau = (gqq - gpp) / (2.0 * gpq)
+                t = np.where(tau >= 0.0, 1.0, -1.0) / (np.abs(tau) + np.sqrt(1.0 + tau * tau))
+                c = 1.0 / np.sqrt(1.0 + t * t)
+                s = np.where(skip, 0.0, t * c)
+                on = s != 0.0                                      # (the kernel leaves a pair with s = 0 untouched)
+                if not on.any():
+                    continue
+                rotated = True
+                p, q, c, s = p[on], q[on], c[on], s[on]
+                x, y = A[:, p].copy(), A[:, q].copy()
+                A[:, p], A[:, q] = c * x - s * y, s * x + c * y
+                x, y = A[p, :].copy(), A[q, :].copy()
+                A[p, :], A[q, :] = c[:, None] * x - s[:, None] * y, s[:, None] * x + c[:, None] * y
+                A[p, q] = A[q, p] = 0.0
+            sweeps = sweep + 1
+            if not rotated:
+                status = 0
+                break
+    return sweeps, status, np.diag(A)[:Kp if defect == "padded index taken for a real one" else K].copy()
 
 
 def scale(values):

@@ -234,6 +234,196 @@ def test_gpu_cases_meet_their_conditions():
     assert n_checked > 50
 
 
+# ---- degenerate spectra (svdwf_cases.degenerate_cases): what the device tests rest on ----
+SKIP_DEFECT = "a pair whose g_pp is 0 or below skipped"
+GRAM_DEFECTS = ["clamp dropped from the total", "padded index taken for a real one"]
+
+
+def gram_formulation(a, expl_var, kmax, w, sos, defect=None):
+    """postprocess.svdwf_host by the device's route, in float64 NumPy: eigh of the Gram matrix on the smaller side
+    (padded to even order as the kernel pads it), the sum of the eigenvalues clamped at 0, the eight largest, k by the
+    same loop, P_j = u_j (u_j^T A) or (A v_j) v_j^T.  Returns (filtered float32, k, total, candidates)."""
+    a = np.asarray(a, dtype=np.float32).astype(np.float64)
+    n, m = a.shape
+    w = n if w is None else w
+    G = sc.gram(a)
+    K = len(G)
+    Kp = K + (K & 1)
+    padded = np.zeros((Kp, Kp))
+    padded[:K, :K] = G
+    real = Kp if defect == "padded index taken for a real one" else K
+    lam, vec = np.linalg.eigh(padded[:real, :real])
+    order = np.argsort(-lam, kind="stable")
+    lam, vec = lam[order], vec[:, order]
+    total = float(lam.sum() if defect == "clamp dropped from the total" else np.maximum(lam, 0.0).sum())
+    n_top = min(real, pp.SVDWF_MAX_SINGULAR_VALUES)
+    out = np.zeros((n, m), np.float32)
+    if not total > 0.0:
+        return out, 0, total, n_top
+    k, cum = min(kmax, n_top), 0.0
+    for j in range(min(n_top, kmax)):
+        cum += max(lam[j], 0.0)
+        if cum / total >= expl_var:
+            k = j + 1
+            break
+    d = np.zeros((n, m))
+    for j in range(k):
+        v = vec[:K, j]
+        proj = np.outer(v, v @ a) if n <= m else np.outer(a @ v, v)
+        f = proj if w == 1 else pp.wiener_rows_host(proj, w)
+        if np.isnan(f).any():
+            continue
+        d += f
+    if w != 1:
+        d = pp.wiener_rows_host(d, w)
+    d[~np.isfinite(d)] = 0.0
+    if sos is not None:
+        d = pp.bandpass_filter_host(d, sos, taper_alpha=0.01)
+    return d.astype(np.float32), k, total, n_top
+
+
+@pytest.fixture(scope="module")
+def degenerate():
+    return sc.degenerate_cases()
+
+
+@pytest.fixture(scope="module")
+def jacobi(degenerate):
+    """{label: (sweeps, status, eigenvalues)} of jacobi_reference on every degenerate case it serves, and under the
+    shape (n, m) the same of the generic matrix of that shape."""
+    out = {}
+    for label, x, _ in degenerate:
+        if min(x.shape) <= sc.JACOBI_REFERENCE_MAX_K:
+            out[label] = sc.jacobi_reference(sc.gram(x))
+            if x.shape not in out:
+                out[x.shape] = sc.jacobi_reference(sc.gram(sc.matrix(*x.shape, 3)))
+    return out
+
+
+def unique_regime(label, params):
+    """False where the definition itself is not unique: the equal singular values cut by k, or filtered one by one."""
+    return label != sc.EQUAL_SIGMA or (params[0] == 0.8 and params[2] == 1)
+
+
+def test_degenerate_cases_meet_their_conditions(degenerate):
+    labels = [label for label, _, _ in degenerate]
+    assert len(labels) == len(set(labels)) == 14
+    for label, x, params in degenerate:
+        for expl_var, kmax in sorted({(p[0], p[1]) for p in params}):
+            if label != sc.EQUAL_SIGMA:
+                sc.conditions(x, expl_var, kmax)
+                continue
+            with pytest.raises(AssertionError):                    # sigma_1 = sigma_2: on purpose
+                sc.conditions(x, expl_var, kmax)
+            if expl_var == 0.8:
+                assert sc.conditions_subspace(x, expl_var, kmax) == 2
+            else:                                                  # k = 1 cuts the pair: nothing is unique there
+                with pytest.raises(AssertionError):
+                    sc.conditions_subspace(x, expl_var, kmax)
+    s = np.linalg.svd(sc.equal_sigma_matrix().astype(np.float64), compute_uv=False)
+    assert s[0] == pytest.approx(s[1], rel=1e-14) and s[2] <= 1e-7 * s[0]
+
+
+def test_jacobi_reference_converges_on_the_degenerate_cases(degenerate, jacobi):
+    """The documented solver, in float64: converged on every case of order <= 128, its eigenvalues those of
+    numpy.linalg.eigvalsh within 1e-12 of the largest, and more sweeps on the duplicated and low-rank classes than on
+    the generic matrix of the same shape (else these cases would not ask more of the kernel than the old ones)."""
+    for shape in (key for key in jacobi if isinstance(key, tuple)):
+        print(f"generic {shape}: {jacobi[shape][0]} sweeps")
+        assert jacobi[shape][1] == 0
+    served = [label for label, x, _ in degenerate if min(x.shape) <= sc.JACOBI_REFERENCE_MAX_K]
+    assert len(served) == 12
+    for label, x, _ in degenerate:
+        if label not in jacobi:
+            continue
+        sweeps, status, lam = jacobi[label]
+        want = np.linalg.eigvalsh(sc.gram(x))
+        print(f"{label}: {sweeps} sweeps, {int((lam < 0).sum())} negative and {int((lam == 0).sum())} zero eigenvalues")
+        assert status == 0, label
+        assert lam.shape == want.shape and np.abs(np.sort(lam) - want).max() <= 1e-12 * want[-1], label
+        if label.startswith(("duplicated rows", "low rank")):
+            assert sweeps > jacobi[x.shape][0], (label, sweeps, jacobi[x.shape][0])
+    # the paths the generic matrix never takes are taken: eigenvalues at rounding level below zero, and exact zeros
+    assert any((jacobi[label][2] < 0).any() for label in served)
+    assert any((jacobi[label][2] == 0).any() for label in served)
+
+
+def test_jacobi_reference_gives_up_a_non_finite_matrix():
+    """As the kernel does: not solved, status 1.  Left to the sweeps a 2 x 2 matrix with an Inf on the diagonal would
+    pass the skip test and end as converged."""
+    for n in (2, 3, 7):
+        for bad in (np.nan, np.inf, -np.inf):
+            x = sc.matrix(n, 64, 31)
+            x[0, 10] = bad
+            assert sc.jacobi_reference(sc.gram(x))[:2] == (0, 1), (n, bad)
+
+
+def test_the_definition_is_stable_on_the_degenerate_cases(degenerate):
+    """A case the reference alone cannot carry stays out of the table: the Gram/eigh formulation -- another route to the
+    same definition, the device's -- gives the same n_singular and stays within a quarter of the device's limit on
+    `filtered`.  Not where the definition is not unique (unique_regime)."""
+    from test_gpu_svdwf import LIMIT_FILTERED
+    sos = sc.sos_table()
+    for label, x, params in degenerate:
+        worst = 0.0
+        for p in params:
+            if not unique_regime(label, p):
+                continue
+            expl_var, kmax, w, bandpass = p
+            want, k = pp.svdwf_host(x, expl_var, kmax, w, sos if bandpass else None, return_rank=True)
+            got, got_k = gram_formulation(x, expl_var, kmax, w, sos if bandpass else None)[:2]
+            assert got_k == k, (label, p)
+            worst = max(worst, float(np.abs(got.astype(np.float64) - want).max()) / sc.scale(want))
+        print(f"{label}: Gram/eigh within {worst / LIMIT_FILTERED:.3f} x 2^-22 of the definition")
+        assert worst <= LIMIT_FILTERED / 4, label
+
+
+def test_the_equal_sigma_definition_is_not_unique_where_the_tests_say_so():
+    """Cut by k, or filtered projection by projection, two routes to the definition differ by the channel's scale:
+    there the device tests assert invariants only."""
+    x, sos = sc.equal_sigma_matrix(), sc.sos_table()
+    seen = 0.0
+    for p in sc.degenerate_params(6):
+        if unique_regime(sc.EQUAL_SIGMA, p):
+            continue
+        expl_var, kmax, w, bandpass = p
+        want, k = pp.svdwf_host(x, expl_var, kmax, w, sos if bandpass else None, return_rank=True)
+        got, got_k = gram_formulation(x, expl_var, kmax, w, sos if bandpass else None)[:2]
+        assert got_k == k == (1 if expl_var == 0.4 else 2)
+        seen = max(seen, float(np.abs(got.astype(np.float64) - want).max()) / sc.scale(want))
+    print(f"equal sigma, not unique: the two routes differ by {seen:.3f} of the channel scale")
+    assert seen > 0.01
+
+
+def test_degenerate_cases_reject_the_planted_defects(degenerate, jacobi):
+    """One defect per mechanism the degenerate cases bring in; each must change a result on at least one of them.
+    The clamp and the padded index leave k alone on matrices that meet `conditions` (var stays 1e-4 away from expl_var,
+    k stays below the rank), so what they change is the sum of the eigenvalues and the number of candidates.  The skip
+    is planted for g_pp <= 0: a diagonal element of exactly 0 comes with a zero row in these matrices (no data, or the
+    difference of two equal rows) and is skipped anyway, whereas below zero -- rounding level, where the threshold rests
+    on fabs -- the defect ends the solve sweeps early with other eigenvalue bits."""
+    changed = {d: [] for d in GRAM_DEFECTS + [SKIP_DEFECT]}
+    for label, x, params in degenerate:
+        if label not in jacobi:
+            continue
+        expl_var, kmax, w, _ = params[0]
+        clean = gram_formulation(x, expl_var, kmax, 1, None)
+        for defect in GRAM_DEFECTS:
+            got = gram_formulation(x, expl_var, kmax, 1, None, defect)
+            if got[1:] != clean[1:] or not np.array_equal(got[0], clean[0]):
+                changed[defect].append(label)
+        sweeps, status, lam = jacobi[label]
+        padded = sc.jacobi_reference(sc.gram(x), defect="padded index taken for a real one")[2]
+        assert (len(padded) != len(lam)) == (len(lam) % 2 == 1)
+        got = sc.jacobi_reference(sc.gram(x), defect=SKIP_DEFECT)
+        if got[:2] != (sweeps, status) or not np.array_equal(got[2], lam):
+            changed[SKIP_DEFECT].append(label)
+    print(changed)
+    for defect, labels in changed.items():
+        assert labels, defect
+    assert all(label.endswith("7x200") for label in changed["padded index taken for a real one"])
+
+
 # ---- the band-pass ----
 def test_sosfilt_rows_equals_scipy_bit_for_bit():
     signal = pytest.importorskip("scipy.signal")

@@ -18,7 +18,7 @@
 // The weights are float32, and so is the reference's DENOMINATOR: np.sum(likelihood) of a float32 vector is a
 // float32 sum in NumPy's order (chunks of 8192, each summed pairwise), about 1e-7 from the exact sum.  The
 // numerators np.sum(likelihood * d) are float64.  To give the reference's numbers the denominator here is that
-// float32 sum, bit for bit (np_leaf_sum and the final kernel below); the numerators are float64 sums.
+// float32 sum, bit for bit (np_order.h and the final kernel below); the numerators are float64 sums.
 //
 // Four launches per call, all on the caller's stream:
 //   count    grid (terms / 256, events): the flag of every term, per workgroup the number that take part (and the
@@ -36,6 +36,7 @@
 // workgroup none of whose terms takes part skips the geodesic altogether.  No floating-point atomics: the sums of
 // an event depend on its own terms alone, not on the batch, the chunk or the run.
 #include "bp_plan.h"
+#include "np_order.h"
 #include <cmath>
 
 namespace bpmf {
@@ -259,37 +260,12 @@ __global__ __launch_bounds__(UNC_THREADS) void bp_unc_partial_kernel(
     }
 }
 
-// np.sum of a contiguous float32 vector, in NumPy's order.  The reference divides by np.sum(likelihood) of a
-// float32 vector: a float32 sum, taken in chunks of NP_CHUNK elements (NumPy's buffer size) added one after the
-// other, each chunk summed pairwise -- halves cut at multiples of 8 down to leaves of at most NP_LEAF elements,
-// a leaf as 8 strided running sums combined as a tree plus its tail (workflow.numpy_order_sum states the same).
-constexpr int NP_CHUNK = 8192, NP_LEAF = 128, NP_SLOT = 64, NP_DEPTH = 16;
-
-__device__ __forceinline__ float np_leaf_sum(const float* __restrict__ a, int n)
-{
-    if (n < 8) {
-        float res = 0.0f;
-        for (int i = 0; i < n; ++i) res += a[i];
-        return res;
-    }
-    float r[8];
-#pragma unroll
-    for (int j = 0; j < 8; ++j) r[j] = a[j];
-    int i = 8;
-    for (; i < n - (n % 8); i += 8) {
-#pragma unroll
-        for (int j = 0; j < 8; ++j) r[j] += a[i + j];
-    }
-    float res = ((r[0] + r[1]) + (r[2] + r[3])) + ((r[4] + r[5]) + (r[6] + r[7]));
-    for (; i < n; ++i) res += a[i];
-    return res;
-}
-
 // 4. final: one workgroup per event.  Numerators: the blocks' float64 sums, strided rows then the tree.
-// Denominator: np.sum of cw[e, 0 .. n) as above -- two chunks per round: every leaf of a chunk holds a multiple
-// of NP_SLOT (a leaf below the root has at least 64 elements), thread s descends from the root to the leaf that
-// holds 64 s and sums it if 64 s is the first multiple in it; one thread per chunk then combines the leaves along
-// the recursion, and thread 0 adds the chunks in order.
+// Denominator: np.sum of the float32 vector cw[e, 0 .. n) in NumPy's order (np_order.h), about 1e-7 from the exact
+// sum, as the reference divides by it -- two chunks per round: every leaf of a chunk holds a multiple of NP_SLOT (a
+// leaf below the root has at least 64 elements), thread s finds the leaf that holds 64 s and sums it if 64 s is the
+// first multiple in it; one thread per chunk then folds the leaves in order (NpFold, its values in LDS), and thread 0
+// adds the chunks in order, from 0.0f.
 __global__ __launch_bounds__(UNC_THREADS) void bp_unc_final_kernel(
     const int32_t* __restrict__ src_idx, UncTables T, int n_terms, int n_blocks, const double* __restrict__ part,
     const int* __restrict__ base, const float* __restrict__ cw, double* __restrict__ hunc, double* __restrict__ vunc,
@@ -297,11 +273,10 @@ __global__ __launch_bounds__(UNC_THREADS) void bp_unc_final_kernel(
     double* __restrict__ o_dep)
 {
 #pragma clang fp contract(off)
-    constexpr int PER = NP_CHUNK / NP_SLOT;            // 128 candidate leaves per chunk, 2 chunks per round
+    constexpr int NP_SLOT = 64, PER = NP_CHUNK / NP_SLOT;   // 128 candidate leaves per chunk, 2 chunks per round
     __shared__ float leaf[2][PER];
     __shared__ float chunk_sum[2];
-    __shared__ int st_off[2][NP_DEPTH], st_n[2][NP_DEPTH], st_state[2][NP_DEPTH];
-    __shared__ float st_left[2][NP_DEPTH];
+    __shared__ float fold_value[2][NP_MAX_DEPTH + 1];
     const size_t e = blockIdx.x;
     const int tid = threadIdx.x;
     double swd = 0.0, swz = 0.0;
@@ -320,57 +295,16 @@ __global__ __launch_bounds__(UNC_THREADS) void bp_unc_final_kernel(
         const int m = min(NP_CHUNK, n - c * NP_CHUNK);              // this chunk's length (<= 0: no such chunk)
         const int cand = slot * NP_SLOT;
         if (cand < m) {
-            int off = 0, len = m;
-            while (len > NP_LEAF) {
-                int n2 = len / 2;
-                n2 -= n2 % 8;
-                if (cand < off + n2) {
-                    len = n2;
-                } else {
-                    off += n2;
-                    len -= n2;
-                }
-            }
-            if ((off + NP_SLOT - 1) / NP_SLOT == slot) leaf[which][slot] = np_leaf_sum(a + (size_t)c * NP_CHUNK + off, len);
+            const NpLeaf l = np_leaf_of(m, cand);
+            const float* ac = a + (size_t)c * NP_CHUNK;
+            if ((l.off + NP_SLOT - 1) / NP_SLOT == slot)
+                leaf[which][slot] = np_leaf_sum<float>([=](int i) { return ac[i]; }, l.off, l.len);
         }
         __syncthreads();
         if (slot == 0 && m > 0) {
-            int sp = 0;
-            st_off[which][0] = 0;
-            st_n[which][0] = m;
-            st_state[which][0] = 0;
-            float val = 0.0f;
-            bool have = false;
-            while (sp >= 0) {
-                const int o = st_off[which][sp], s = st_n[which][sp];
-                int n2 = s / 2;
-                n2 -= n2 % 8;
-                if (!have) {
-                    if (s <= NP_LEAF) {
-                        val = leaf[which][(o + NP_SLOT - 1) / NP_SLOT];
-                        have = true;
-                        --sp;
-                    } else {
-                        st_state[which][sp] = 1;
-                        ++sp;
-                        st_off[which][sp] = o;
-                        st_n[which][sp] = n2;
-                        st_state[which][sp] = 0;
-                    }
-                } else if (st_state[which][sp] == 1) {
-                    st_left[which][sp] = val;
-                    st_state[which][sp] = 2;
-                    have = false;
-                    ++sp;
-                    st_off[which][sp] = o + n2;
-                    st_n[which][sp] = s - n2;
-                    st_state[which][sp] = 0;
-                } else {
-                    val = st_left[which][sp] + val;
-                    --sp;
-                }
-            }
-            chunk_sum[which] = val;
+            NpFold<float> fold{fold_value[which], 0};
+            np_walk(m, [&](const NpLeaf& l) { fold.push(leaf[which][(l.off + NP_SLOT - 1) / NP_SLOT], l.depth); });
+            chunk_sum[which] = fold_value[which][0];
         }
         __syncthreads();
         if (tid == 0) {

@@ -15,12 +15,13 @@
 //                          1024 samples, oracle/bpmf_oracle.c:mf_data_csum).
 //   intertp_cc_kernel      one workgroup per (t, tile of 8 templates u): every (u, channel, lag)
 //                          CC as an fmaf chain over the samples (8 lags per thread, register-tiled), the data rows of t staged in LDS,
-//                          max over the lags, weight, and the channel sum in NumPy's pairwise
-//                          order, so that the result equals the per-template path bit for bit.
+//                          max over the lags, weight, and the channel sum in NumPy's order
+//                          (np_order.h), so that the result equals the per-template path bit for bit.
 //
 // Weights come factorised, as the reference builds them: base (T, S, C) = row t's channel weights,
 // pair_mask (T, T) = 1 where the pair is within the distance threshold.
 #include "common.h"
+#include "np_order.h"
 #include "../../include/bpmf_hip.h"
 
 namespace bpmf {
@@ -59,30 +60,6 @@ __global__ void intertp_norms_kernel(const float* __restrict__ wf, int n_rows, i
         if (n % CSUM_CHUNK == 0 && n) { off += local; local = 0.0; }
         local += (double)x[n] * (double)x[n];
     }
-}
-
-// np.sum of n float32 in NumPy's pairwise order (numpy/core/src/umath/loops_utils.h.src)
-__device__ float numpy_pairwise_sum(const float* x, int n)
-{
-    if (n < 8) {
-        float r = 0.0f;
-        for (int i = 0; i < n; ++i) r = __fadd_rn(r, x[i]);
-        return r;
-    }
-    if (n <= 128) {
-        float r[8];
-        for (int j = 0; j < 8; ++j) r[j] = x[j];
-        int i = 8;
-        for (; i < n - (n % 8); i += 8)
-            for (int j = 0; j < 8; ++j) r[j] = __fadd_rn(r[j], x[i + j]);
-        float res = __fadd_rn(__fadd_rn(__fadd_rn(r[0], r[1]), __fadd_rn(r[2], r[3])),
-                              __fadd_rn(__fadd_rn(r[4], r[5]), __fadd_rn(r[6], r[7])));
-        for (; i < n; ++i) res = __fadd_rn(res, x[i]);
-        return res;
-    }
-    int n2 = n / 2;
-    n2 -= n2 % 8;
-    return __fadd_rn(numpy_pairwise_sum(x, n2), numpy_pairwise_sum(x + n2, n - n2));
 }
 
 // LDS: rows[ch_chunk][Lw] data of t | cc[ITP_UB][ch_chunk][n_lag] | prod[ITP_UB][n_ch]
@@ -183,7 +160,10 @@ __global__ __launch_bounds__(ITP_THREADS) void intertp_cc_kernel(
     __syncthreads();
     if (tid < ITP_UB && u0 + tid < T) {
         const int u = u0 + tid;
-        out[(size_t)t * T + u] = mask[(size_t)t * T + u] ? numpy_pairwise_sum(prod + tid * n_ch, n_ch) : 0.0f;
+        const float* p = prod + tid * n_ch;
+        // the bare tree, no chunks: the launcher keeps n_ch <= NP_CHUNK (prod alone would outgrow the LDS long before)
+        out[(size_t)t * T + u] =
+            mask[(size_t)t * T + u] ? np_chunk_sum<float>([=](int ch) { return p[ch]; }, 0, n_ch) : 0.0f;
     }
 }
 
@@ -230,6 +210,10 @@ extern "C" int bpmf_intertemplate_cc_dev(const float* d_waveforms, const float* 
     while (ch_chunk > 1 && need(ch_chunk) > 64 * 1024) --ch_chunk;
     if (need(ch_chunk) > 64 * 1024) {
         set_error("bpmf_intertemplate_cc_dev: one channel of %zu samples does not fit the LDS budget", Lw);
+        return -1;
+    }
+    if (n_ch > (size_t)NP_CHUNK) {                     // (implied by `fixed` within 64 KB; the channel sum is one tree)
+        set_error("bpmf_intertemplate_cc_dev: %zu channels; the channel sum takes at most %d", n_ch, NP_CHUNK);
         return -1;
     }
     // option debug.poison_output (tests): an entry no kernel writes comes back as NaN

@@ -1,45 +1,39 @@
-// NumPy's float32 sums on the device, shared by templates.hip and picker.hip: np.sum / np.mean / np.std of a row of at
-// most 8192 float32 staged in LDS, bit for bit.  pairwise_sum is NumPy's: under 8 elements a running sum from 0; up to
-// 128 elements eight strided running sums combined as ((r0+r1)+(r2+r3))+((r4+r5)+(r6+r7)) plus the tail; above 128 a
-// split at n/2 rounded down to a multiple of 8.  The shape of that tree depends on the length alone: the host lists its
-// leaves (offset, length, depth) once -- at most 128 -- and passes the list to the kernel by value.  One workgroup of
-// TP_THREADS threads works on one row: each (leaf, accumulator j) is one thread's at most 16 sequential adds out of
-// LDS; one thread per leaf adds the eight partial sums and the tail; thread 0 folds the leaves with a stack (equal
-// depths combine), which is the recursion.
+// NumPy's float32 sums of a row staged in LDS, by one workgroup, bit for bit: np.sum / np.mean / np.std of at most
+// NP_CHUNK float32 -- one pairwise tree.  The order of the additions is np_order.h's, the single definition; what is
+// here is its block layout, shared by templates.hip and picker.hip (resample.hip takes clipped_sample alone).  The
+// shape of the tree depends on the length alone: the host lists its leaves once (list_leaves: np_walk) and
+// passes the list to the kernel by value.  One workgroup of TP_THREADS threads works on one row: each (leaf,
+// accumulator j) is one thread's at most 16 sequential adds out of LDS; one thread per leaf adds the eight partial sums
+// and the tail; thread 0 folds the leaves (NpFold, on SumScratch's LDS array).
 #pragma once
 #include "common.h"
+#include "np_order.h"
 #include <cmath>
 
 namespace bpmf {
 
 constexpr int TP_THREADS = 256;
-constexpr int TP_MAX_SAMPLES = 8192;               // NumPy sums longer rows in buffers of 8192: another tree
-constexpr int TP_MAX_LEAVES = 128;
-constexpr int TP_MAX_DEPTH = 15;
 
-// The leaves of NumPy's pairwise sum over n elements, in order: offset (bits 0-13), length (14-21), depth (22-27).
+// The leaves of the tree over n elements, in order: offset (bits 0-13), length (14-21), depth (22-27).
 struct LeafTable {
     int n;
-    uint32_t leaf[TP_MAX_LEAVES];
+    uint32_t leaf[NP_MAX_LEAVES];
 };
 
-inline bool list_leaves(int offset, int n, int depth, LeafTable& t)
+inline bool list_leaves(int n, LeafTable& t)           // 1 <= n <= NP_CHUNK
 {
-    if (n <= 128) {
-        if (t.n >= TP_MAX_LEAVES || depth > TP_MAX_DEPTH) return false;
-        t.leaf[t.n++] = (uint32_t)offset | ((uint32_t)n << 14) | ((uint32_t)depth << 22);
-        return true;
-    }
-    int n2 = n / 2;
-    n2 -= n2 % 8;
-    return list_leaves(offset, n2, depth + 1, t) && list_leaves(offset + n2, n - n2, depth + 1, t);
+    t.n = 0;
+    np_walk(n, [&](const NpLeaf& l) {
+        if (t.n < NP_MAX_LEAVES) t.leaf[t.n] = (uint32_t)l.off | ((uint32_t)l.len << 14) | ((uint32_t)l.depth << 22);
+        ++t.n;
+    });
+    return t.n <= NP_MAX_LEAVES;
 }
 
 struct SumScratch {
-    float part[TP_MAX_LEAVES * 8];
-    float leaf_sum[TP_MAX_LEAVES];
-    float stack_value[TP_MAX_DEPTH + 1];
-    int stack_depth[TP_MAX_DEPTH + 1];
+    float part[NP_MAX_LEAVES * 8];
+    float leaf_sum[NP_MAX_LEAVES];
+    float fold_value[NP_MAX_DEPTH + 1];
     float total;
 };
 
@@ -75,20 +69,9 @@ __device__ inline float block_pairwise_sum(const float* x, const LeafTable& tab,
     }
     __syncthreads();
     if (tid == 0) {
-        int sp = 0;
-        for (int i = 0; i < n_leaves; ++i) {
-            float v = s.leaf_sum[i];
-            int d = (tab.leaf[i] >> 22) & 0x3f;
-            while (sp > 0 && s.stack_depth[sp - 1] == d) {         // sum(left half) + sum(right half)
-                --sp;
-                v = __fadd_rn(s.stack_value[sp], v);
-                --d;
-            }
-            s.stack_value[sp] = v;
-            s.stack_depth[sp] = d;
-            ++sp;
-        }
-        s.total = __fadd_rn(0.0f, s.stack_value[0]);               // np.add.reduce starts from its identity: -0.0 -> +0.0
+        NpFold<float> fold{s.fold_value, 0};
+        for (int i = 0; i < n_leaves; ++i) fold.push(s.leaf_sum[i], (tab.leaf[i] >> 22) & 0x3f);
+        s.total = __fadd_rn(0.0f, s.fold_value[0]);               // np.add.reduce starts from its identity: -0.0 -> +0.0
     }
     __syncthreads();
     const float total = s.total;

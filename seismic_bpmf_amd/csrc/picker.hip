@@ -26,8 +26,8 @@
 //   2. one lane per candidate walks out for the prominence (lowest sample on either side before a higher one) and in
 //      for the width at half prominence (interpolated crossings); a candidate below the floor or narrower than 1 goes;
 //   3. a second scan ranks the survivors; one lane per survivor of rank < max_picks sums samples * prob (float64),
-//      prob (float32) and (samples - mean)^2 (float64) over int(left_ip) .. int(right_ip) in NumPy's pairwise order
-//      (in chunks of 8192, as NumPy sums a longer row) and writes its record.  count is the true number of picks.
+//      prob (float32) and (samples - mean)^2 (float64) over int(left_ip) .. int(right_ip) as np.sum does (np_order.h:
+//      np_sum, in one thread) and writes its record.  count is the true number of picks.
 // Plain vector stores, no atomics; every output element is written.
 #include "common.h"
 #include "np_sums.h"
@@ -41,7 +41,6 @@ constexpr size_t PK_NORM_LDS_BYTES = 150 * 1024;       // dynamic; the static Su
 constexpr long long PK_INDEX_LIMIT = 1ll << 40;        // N and |start|
 constexpr int PK_MAX_SERIES = 16384;                   // find_picks: 4 (n + n/2 + 1) bytes of LDS
 constexpr int PK_MAX_PICKS = 4096;
-constexpr int PK_SUM_CHUNK = 8192;                     // NumPy sums a longer row in pieces of this length
 
 template <typename OutT>
 __global__ __launch_bounds__(PK_THREADS) void normalize_batch_kernel(
@@ -184,64 +183,6 @@ __device__ inline bool pick_window(const float* x, int n, int pk, double min_pro
     return true;
 }
 
-// one leaf of NumPy's pairwise sum (n <= 128) over f(off) .. f(off + n - 1)
-template <typename T, typename F>
-__device__ inline T np_leaf_sum(const F& f, int off, int n)
-{
-    if (n < 8) {
-        T res = (T)0;
-        for (int i = 0; i < n; ++i) res = res + f(off + i);
-        return res;
-    }
-    T r[8];
-#pragma unroll
-    for (int j = 0; j < 8; ++j) r[j] = f(off + j);
-    int i = 8;
-    for (; i < n - (n & 7); i += 8) {
-#pragma unroll
-        for (int j = 0; j < 8; ++j) r[j] = r[j] + f(off + i + j);
-    }
-    T res = ((r[0] + r[1]) + (r[2] + r[3])) + ((r[4] + r[5]) + (r[6] + r[7]));
-    for (; i < n; ++i) res = res + f(off + i);
-    return res;
-}
-
-// np.sum over f(0) .. f(n - 1) in one thread: pairwise within pieces of 8192, the pieces added in order
-template <typename T, typename F>
-__device__ inline T np_sum_thread(const F& f, int n)
-{
-    T total = (T)0;
-    for (int piece = 0; piece < n; piece += PK_SUM_CHUNK) {
-        const int len = n - piece < PK_SUM_CHUNK ? n - piece : PK_SUM_CHUNK;
-        // the recursion as two stacks: segments still to split (left on top), sums waiting for their right halves
-        int seg_off[TP_MAX_DEPTH + 2], seg_len[TP_MAX_DEPTH + 2], seg_depth[TP_MAX_DEPTH + 2], sp = 0;
-        T value[TP_MAX_DEPTH + 2];
-        int value_depth[TP_MAX_DEPTH + 2], vp = 0;
-        seg_off[0] = piece, seg_len[0] = len, seg_depth[0] = 0, sp = 1;
-        while (sp > 0) {
-            --sp;
-            const int off = seg_off[sp], m = seg_len[sp];
-            int d = seg_depth[sp];
-            if (m > 128) {
-                int m2 = m / 2;
-                m2 -= m2 % 8;
-                seg_off[sp] = off + m2, seg_len[sp] = m - m2, seg_depth[sp] = d + 1, ++sp;
-                seg_off[sp] = off, seg_len[sp] = m2, seg_depth[sp] = d + 1, ++sp;
-                continue;
-            }
-            T v = np_leaf_sum<T>(f, off, m);
-            while (vp > 0 && value_depth[vp - 1] == d) {           // sum(left half) + sum(right half)
-                --vp;
-                v = value[vp] + v;
-                --d;
-            }
-            value[vp] = v, value_depth[vp] = d, ++vp;
-        }
-        total = total + value[0];                                  // (from the identity 0, as np.add.reduce)
-    }
-    return total;
-}
-
 __global__ __launch_bounds__(PK_THREADS) void find_picks_kernel(
     const float* __restrict__ proba, int n, double thr_even, double thr_odd, double prom_even, double prom_odd,
     int max_picks, int32_t* __restrict__ count, float* __restrict__ value, double* __restrict__ mean,
@@ -298,10 +239,10 @@ __global__ __launch_bounds__(PK_THREADS) void find_picks_kernel(
             pick_window(x, n, pk, min_prominence, &first, &last);
             const int len = last - first + 1;
             const float* xs = x + first;
-            const double s1 = np_sum_thread<double>([=](int i) { return (double)(first + i) * (double)xs[i]; }, len);
-            const double s0 = (double)np_sum_thread<float>([=](int i) { return xs[i]; }, len);
+            const double s1 = np_sum<double>([=](int i) { return (double)(first + i) * (double)xs[i]; }, len);
+            const double s0 = (double)np_sum<float>([=](int i) { return xs[i]; }, len);
             const double mu = s1 / s0;
-            const double s2 = np_sum_thread<double>([=](int i) {
+            const double s2 = np_sum<double>([=](int i) {
                 const double d = (double)(first + i) - mu;
                 return d * d;
             }, len);
@@ -340,10 +281,10 @@ extern "C" int bpmf_normalize_batch_dev(const float* d_data, size_t S, size_t C,
         set_error("bpmf_normalize_batch_dev: bad argument (S=%zu C=%zu N=%zu rows=%zu)", S, C, N, n_rows);
         return -1;
     }
-    if (window < 2 || window > (size_t)TP_MAX_SAMPLES || shift < 1 || n_samples < 2 || shift > n_samples - 1 ||
+    if (window < 2 || window > (size_t)NP_CHUNK || shift < 1 || n_samples < 2 || shift > n_samples - 1 ||
         n_samples > (1u << 24)) {
         set_error("bpmf_normalize_batch_dev: need 2 <= window <= %d and 1 <= shift <= n_samples - 1 (n_samples=%zu "
-                  "window=%zu shift=%zu)", TP_MAX_SAMPLES, n_samples, window, shift);
+                  "window=%zu shift=%zu)", NP_CHUNK, n_samples, window, shift);
         return -1;
     }
     const size_t n_pad = n_samples + 2 * shift;
@@ -361,8 +302,8 @@ extern "C" int bpmf_normalize_batch_dev(const float* d_data, size_t S, size_t C,
         return -1;
     }
     LeafTable tab{};
-    if (!list_leaves(0, (int)window, 0, tab)) {
-        set_error("bpmf_normalize_batch_dev: the pairwise tree has more than %d leaves", TP_MAX_LEAVES);
+    if (!list_leaves((int)window, tab)) {
+        set_error("bpmf_normalize_batch_dev: the pairwise tree has more than %d leaves", NP_MAX_LEAVES);
         return -1;
     }
     const size_t n_items = n_rows * C, out_bytes = n_items * n_samples * (out_f64 ? sizeof(double) : sizeof(float));

@@ -12,18 +12,14 @@
 // with one difference: the results are compared with NumPy bit for bit, so the arithmetic is NumPy's, operation for
 // operation (postprocess.templates_from_events_host is the definition):
 //     mean = pairwise_sum(x) / L;   d = x - mean;   d = d * d;   var = pairwise_sum(d) / L;   std = sqrt(var)
-// in float32, every operation rounded on its own.  pairwise_sum is NumPy's: under 8 elements a running sum from 0; up
-// to 128 elements eight strided running sums combined as ((r0+r1)+(r2+r3))+((r4+r5)+(r6+r7)) plus the tail; above 128
-// a split at n/2 rounded down to a multiple of 8 (intertp.hip:numpy_pairwise_sum is the same rule in one thread).
-// NumPy sums at most 8192 elements in one go, so L and noise_samples stop there.
+// in float32, every operation rounded on its own.  pairwise_sum is NumPy's order of additions (np_order.h is its
+// definition, np_sums.h the workgroup's layout of it); it is one tree up to NP_CHUNK elements, so L and noise_samples
+// stop there.
 //
-// The shape of that tree depends on the length alone: the entry point lists its leaves (offset, length, depth) once on
-// the host -- at most 128 -- and passes the list by value.  One workgroup of 256 threads per (event, channel); i0 is
-// uniform.  The window is read once, lane-strided, 64 consecutive floats per load instruction, all loads of a thread
-// issued before the first use (addresses clamped into the day, values outside it replaced by 0 afterwards), kept in
-// registers for the final division and staged in LDS for the sums.  Each (leaf, accumulator j) is one thread's at
-// most 16 sequential adds out of LDS; one thread per leaf adds the eight partial sums and the tail; thread 0 folds the
-// leaves with a stack (equal depths combine), which is the recursion.  np.max propagates NaN and v_max_f32 drops it:
+// One workgroup of 256 threads per (event, channel); i0 is uniform.  The window is read once, lane-strided, 64
+// consecutive floats per load instruction, all loads of a thread issued before the first use (addresses clamped into
+// the day, values outside it replaced by 0 afterwards), kept in registers for the final division and staged in LDS
+// for the sums.  np.max propagates NaN and v_max_f32 drops it:
 // a "saw a NaN" flag travels beside the maximum, as in peak_amp.hip.  No atomics, plain vector stores, and every
 // output element is written, the zeros of a clipped window included.
 #include "common.h"
@@ -125,9 +121,9 @@ extern "C" int bpmf_templates_from_events_dev(const float* d_data, size_t S, siz
                   "(noise_samples=%zu)", noise_samples);
         return -1;
     }
-    if (n_samples == 0 || n_samples > (size_t)TP_MAX_SAMPLES || noise_samples > (size_t)TP_MAX_SAMPLES) {
+    if (n_samples == 0 || n_samples > (size_t)NP_CHUNK || noise_samples > (size_t)NP_CHUNK) {
         set_error("bpmf_templates_from_events_dev: need 1 <= n_samples <= %d and noise_samples <= %d, the lengths NumPy "
-                  "sums in one pairwise tree (n_samples=%zu noise_samples=%zu)", TP_MAX_SAMPLES, TP_MAX_SAMPLES,
+                  "sums in one pairwise tree (n_samples=%zu noise_samples=%zu)", NP_CHUNK, NP_CHUNK,
                   n_samples, noise_samples);
         return -1;
     }
@@ -149,8 +145,8 @@ extern "C" int bpmf_templates_from_events_dev(const float* d_data, size_t S, siz
             return -1;
         }
     LeafTable sig{}, noi{};
-    if (!list_leaves(0, (int)n_samples, 0, sig) || (noise_samples && !list_leaves(0, (int)noise_samples, 0, noi))) {
-        set_error("bpmf_templates_from_events_dev: the pairwise tree has more than %d leaves", TP_MAX_LEAVES);
+    if (!list_leaves((int)n_samples, sig) || (noise_samples && !list_leaves((int)noise_samples, noi))) {
+        set_error("bpmf_templates_from_events_dev: the pairwise tree has more than %d leaves", NP_MAX_LEAVES);
         return -1;
     }
     const size_t n_items = n_events * S * C;

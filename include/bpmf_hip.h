@@ -14,6 +14,18 @@
  *   *_run_dev  device pointers, asynchronous on the given HIP stream, caller-provided
  *              workspace (what the resident / multi-GPU / benchmark path uses).
  *
+ * Memory contract of every device-pointer entry point (tests/test_gpu_guard_bands.py runs each of them between
+ * guard bands, on a workspace of exactly the size its bpmf_*_workspace_bytes names):
+ *   - it writes no byte outside its outputs and [d_workspace, d_workspace + workspace_bytes); a call that is
+ *     refused (-1) writes nothing at all, the fill of option debug.poison_output included;
+ *   - it reads nothing of the workspace that the same call -- or the preparation its flags name
+ *     (BPMF_MF_DATA_PREPARED) -- has not written: the results do not depend on what the workspace held before, nor
+ *     on which of the accepted sizes it has;
+ *   - a bpmf_*_workspace_bytes function returns 0 for sizes that its call refuses (a zero dimension, a series shorter
+ *     than its window, more rows than one call takes) and never less for more rows;
+ *   - it expects every buffer aligned as the device allocator aligns it (256 bytes); finer alignments are the
+ *     caller's risk unless an entry point says otherwise.
+ *
  * The hot-path arithmetic itself is NOT in the reference tree: BPMF calls the external
  * packages fast_matched_filter and beampower (pyproject.toml:28-29).  Each entry point
  * cites the reference call site it serves.

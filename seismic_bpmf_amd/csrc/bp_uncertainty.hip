@@ -353,7 +353,7 @@ using namespace bpmf;
 
 extern "C" size_t bpmf_bp_location_uncertainty_workspace_bytes(size_t E, size_t n_terms)
 {
-    if (E == 0 || n_terms == 0) return 0;
+    if (E == 0 || n_terms == 0 || E > 65535 || n_terms > 0x7fff0000ull) return 0;     // (sizes the call refuses)
     return unc_layout(E, n_terms).total;
 }
 

@@ -174,6 +174,7 @@ using namespace bpmf;
 extern "C" size_t bpmf_intertemplate_workspace_bytes(size_t T, size_t S, size_t C, size_t max_lag)
 {
     const size_t n_rows = T * S * C, n_lag = 2 * max_lag + 1;
+    if (max_lag > 31) return 0;                           // (the call refuses it)
     return align_up(n_rows * sizeof(float), 256) + align_up(n_rows * n_lag * sizeof(float), 256);
 }
 

@@ -1509,11 +1509,13 @@ using namespace bpmf;
 
 extern "C" size_t bpmf_mf_workspace_bytes(size_t L, size_t N, size_t T, size_t S, size_t C)
 {
+    if (L == 0 || N < L || S == 0 || C == 0) return 0;    // (sizes every call refuses)
     return mf_carve(nullptr, L, N, T, S * C).bytes;
 }
 
 extern "C" size_t bpmf_mf_full_workspace_bytes(size_t L, size_t N, size_t T, size_t S, size_t C)
 {
+    if (L == 0 || N < L || S == 0 || C == 0) return 0;
     return mf_carve_full(nullptr, L, N, T, S * C).ws.bytes;
 }
 

@@ -140,6 +140,7 @@ using namespace bpmf;
 
 extern "C" size_t bpmf_flag_multiples_workspace_bytes(size_t n)
 {
+    if (n > 0x7ffffffeull) return 0;                      // (more events than the call takes)
     return FM_ERROR_BYTES + align_up(n * sizeof(int), 16);
 }
 

@@ -689,14 +689,6 @@ extern "C" int bpmf_svdwf_stack_dev(const float* d_x, const int64_t* offsets, si
         return -1;
     }
     const size_t n_jobs = n_groups * SC;
-    // option debug.poison_output (tests): an element the kernels skip comes back as NaN / -1
-    if (option(OPT_DEBUG_POISON_OUTPUT) != 0) {
-        BPMF_HIP_CHECK(hipMemsetAsync(d_stack, 0xFF, n_jobs * m * sizeof(float), stream));
-        BPMF_HIP_CHECK(hipMemsetAsync(d_n_singular, 0xFF, n_jobs * sizeof(int32_t), stream));
-        BPMF_HIP_CHECK(hipMemsetAsync(d_status, 0xFF, n_jobs * sizeof(int32_t), stream));
-        if (d_filtered_or_null && N)
-            BPMF_HIP_CHECK(hipMemsetAsync(d_filtered_or_null, 0xFF, N * SC * m * sizeof(float), stream));
-    }
     const size_t head = align_up((n_groups + 1) * sizeof(int64_t), 256);
     const SvSizes z = sv_sizes(n_max ? n_max : 1, m);
     const size_t slot_bytes = z.slot * sizeof(double);
@@ -704,6 +696,15 @@ extern "C" int bpmf_svdwf_stack_dev(const float* d_x, const int64_t* offsets, si
         set_error("bpmf_svdwf_stack_dev: the workspace holds %zu bytes; one channel of %zu events x %zu samples takes "
                   "%zu (bpmf_svdwf_workspace_bytes)", workspace_bytes, n_max, m, head + (n_max ? slot_bytes : 0));
         return -1;
+    }
+    // option debug.poison_output (tests): an element the kernels skip comes back as NaN / -1 (behind the last
+    // refusal: a refused call writes nothing)
+    if (option(OPT_DEBUG_POISON_OUTPUT) != 0) {
+        BPMF_HIP_CHECK(hipMemsetAsync(d_stack, 0xFF, n_jobs * m * sizeof(float), stream));
+        BPMF_HIP_CHECK(hipMemsetAsync(d_n_singular, 0xFF, n_jobs * sizeof(int32_t), stream));
+        BPMF_HIP_CHECK(hipMemsetAsync(d_status, 0xFF, n_jobs * sizeof(int32_t), stream));
+        if (d_filtered_or_null && N)
+            BPMF_HIP_CHECK(hipMemsetAsync(d_filtered_or_null, 0xFF, N * SC * m * sizeof(float), stream));
     }
     size_t slab = n_max ? (workspace_bytes - head) / slot_bytes : (size_t)SV_MAX_SLAB;
     slab = slab > (size_t)SV_MAX_SLAB ? (size_t)SV_MAX_SLAB : slab;
@@ -754,6 +755,7 @@ extern "C" int bpmf_svdwf_stack_dev(const float* d_x, const int64_t* offsets, si
 
 extern "C" size_t bpmf_bandpass_rows_workspace_bytes(size_t rows, size_t n_samples, int zerophase, int out_f64)
 {
+    if (n_samples > SV_MAX_ROW_LENGTH || rows > 0x7fffffffull) return 0;              // (sizes the call refuses)
     return zerophase && !out_f64 ? rows * n_samples * sizeof(double) : 0;
 }
 

@@ -869,6 +869,9 @@ int bpmf_suppress_peaks(const int64_t *positions, const int64_t *order, size_t n
  * reference's C functions (num_threads replaced by the method / device); the result equals the
  * reference run single-threaded.
  *   moveouts (K, S) f32 seconds; redundant_sources (K) i32 out (1 = redundant)
+ * Refused with -1 before any device work, redundant_sources untouched and the argument named in
+ * bpmf_last_error(): a null pointer, K = 0, S = 0 or S > 256, n_stations_for_diff outside 1 .. S,
+ * a method other than 0 / 1.
  */
 int bpmf_find_similar_sources(const float *moveouts, const float *source_longitude,
                               const float *source_latitude, const float *cell_longitude,

@@ -10,7 +10,8 @@
 // sequentially (who survives), (3) every later source tests itself against the batch's survivors
 // in parallel.  Distances follow the reference's arithmetic operation for operation (float
 // subtraction, square in double, float accumulator), so the result equals the single-threaded
-// reference bit for bit (tests/golden/similar_sources.npz).
+// reference bit for bit (tests/golden/similar_sources.npz; similar_sources_edges.npz on the inputs of
+// tests/decimate_cases.py, built so that each of these operations decides a flag).
 #include "common.h"
 #include "host_call.h"
 #include "../../include/bpmf_hip.h"
@@ -186,11 +187,17 @@ extern "C" int bpmf_find_similar_sources(const float* moveouts, const float* sou
                                          int method, int device, int32_t* redundant_sources)
 {
     const size_t K = n_sources, S = n_stations;
-    if (!moveouts || !source_longitude || !source_latitude || !cell_longitude || !cell_latitude ||
-        !redundant_sources || K == 0 || S == 0 || S > FS_MAX_STATIONS || n_stations_for_diff == 0 ||
-        n_stations_for_diff > S || K > 0x7fffffffull || (method != 0 && method != 1)) {
-        set_error("bpmf_find_similar_sources: bad argument (K=%zu S=%zu n_diff=%zu method=%d)", K, S,
-                  n_stations_for_diff, method);
+    // refused before any device work, naming the argument; redundant_sources stays untouched
+    const char* bad = !moveouts ? "moveouts is null" : !source_longitude ? "source_longitude is null"
+        : !source_latitude ? "source_latitude is null" : !cell_longitude ? "cell_longitude is null"
+        : !cell_latitude ? "cell_latitude is null" : !redundant_sources ? "redundant_sources is null"
+        : (K == 0 || K > 0x7fffffffull) ? "n_sources must be 1 .. 2^31-1"
+        : (S == 0 || S > FS_MAX_STATIONS) ? "n_stations must be 1 .. 256"
+        : (n_stations_for_diff == 0 || n_stations_for_diff > S) ? "n_stations_for_diff must be 1 .. n_stations"
+        : (method != 0 && method != 1) ? "method must be 0 (smallest) or 1 (closest)" : nullptr;
+    if (bad) {
+        set_error("bpmf_find_similar_sources: bad argument: %s (n_sources=%zu n_stations=%zu n_stations_for_diff=%zu method=%d)",
+                  bad, K, S, n_stations_for_diff, method);
         return -1;
     }
     // threshold^2 * n_diff exactly as the reference: (float)n * pow(threshold, 2) -> float

@@ -134,7 +134,11 @@ int bpmf_host_call_stats(double *out, int n);
  *     (tests/test_gpu_split16_anchor.py pins both sides); composes with the mf.compat_* switches; 1 leaves launches of fewer
  *     than 128 (template, 8192-lag block) pairs to the exact kernel (latency-bound there), 2 takes every launch; enlarges
  *     bpmf_mf_workspace_bytes and what a prepared day holds: set it before the day's first call; does NOT apply to full
- *     normalisation: a launch with BPMF_MF_NORMALIZE_FULL takes family 0, 1 or 2 whatever this option says)
+ *     normalisation: a launch with BPMF_MF_NORMALIZE_FULL takes family 0, 1 or 2 whatever this option says;
+ *     NON-FINITE SAMPLES: the power-of-two scale of a data or template channel comes from its largest FINITE magnitude, so
+ *     a NaN or +-Inf costs what it costs the exact path (below, "Non-finite samples") with a reach of
+ *     16 * nks + (n_seg - 1) * seg - L - (moveout mod 8) samples: at most 40 for L = 200 or 400, 64 for L = 800; finite
+ *     channels and lags in front of that reach keep the bits they have without the bad sample; never +-Inf)
  *   and the result-changing upstream-compatibility switches (off by default; every one has
  *   a variant of the CPU oracle and tools/diff_upstream.py tells which combination equals the real packages):
  *   mf.compat_exclusive_last_lag mf.compat_sqrt_norm mf.compat_range_all_channels mf.compat_sequential_csum
@@ -154,6 +158,23 @@ int bpmf_get_option(const char *name, long *value, long *default_value);
  *   data (S,C,N) f32          n_corr = (N-L)/step + 1
  *   network_sum != 0 -> cc_out (T, n_corr)          weighted network sum
  *   network_sum == 0 -> cc_out (T, n_corr, S, C)    per-channel CC (unweighted)
+ *
+ * Non-finite samples (tests/nonfinite_cases.py is the rule in NumPy).  The window norms come from a
+ * prefix sum of data^2, so per channel, for the window [j, j + L) of a lag:
+ *   +0   a window that holds a NaN; every window that starts behind the channel's first NaN or +-Inf (the rest of
+ *        the day: the norm is NaN and the guard r_t * r_d < 1000 fails); every lag of a template channel that holds a NaN
+ *   NaN  a window that holds +-Inf and no NaN and does not start behind an earlier bad sample (norm 0, cc = num * 0);
+ *        a template channel that holds +-Inf, wherever the window norm is a finite number
+ *   0 or NaN  a window that holds a finite sample whose square overflows float32 (NaN where the numerator overflows)
+ *   the value it has with the bad samples replaced by +0, bit for bit: every window that ends more than R samples in
+ *        front of the channel's first bad sample, and every channel that holds none
+ *   that value or NaN: a window that ends within R samples in front of a NaN or +-Inf -- the MFMA kernels multiply the
+ *        zeros of their band with those samples.  R = 0 for the generic kernel (family 0), 16 * ceil((L + 15) / 16) - L
+ *        (15 .. 30) for the wave and workgroup kernels (families 1, 2), see option mf.split16 for family 3.
+ * A channel that is +0 costs the network sum nothing, one that is NaN makes the lag NaN (the caller scrubs NaN:
+ * BPMF/similarity_search.py:540).  No output is ever +-Inf.  With BPMF_MF_NORMALIZE_FULL every class above is +0
+ * except the last two (Inf - Inf in the centred energy; t - mean t for a template); the channel constant is taken
+ * over the finite samples, so the windows in front of a bad sample stay what they are without it.
  */
 
 /* flags of bpmf_mf_run_dev */
@@ -189,7 +210,8 @@ int bpmf_mf_prepare_data_dev(const float *d_data, size_t L, size_t N, size_t S, 
                              void *d_workspace, size_t workspace_bytes, bpmf_stream_t stream);
 
 /* The same for BPMF_MF_NORMALIZE_FULL (a workspace of bpmf_mf_full_workspace_bytes): per channel the constant
- * c = float32(float64 mean), d' = d - c, double prefix sums of d' and d'^2, the reciprocal norms of the centred window
+ * c = float32((float64 sum of the FINITE samples) / N) -- the float64 mean of a finite channel, 0 when no sample is
+ * finite; a NaN or +-Inf sample does not reach it --, d' = d - c, double prefix sums of d' and d'^2, the reciprocal norms of the centred window
  * energies Q - P * P / L, +Inf for a window of L equal samples (decided from sample equality, not from the energy). */
 int bpmf_mf_prepare_data_full_dev(const float *d_data, size_t L, size_t N, size_t S, size_t C,
                                   void *d_workspace, size_t workspace_bytes, bpmf_stream_t stream);

@@ -5,7 +5,9 @@
 // so the main kernels of mf.hip run UNCHANGED on a centred template t' = t - tbar, the day minus one constant per
 // channel d' = d - c, and reciprocal norms of the centred window energies E_c = Q - P * P / L (Q, P: window sums of
 // d'^2 and d').  This file is the two preparations in front of them (DESIGN.md s3 "full normalisation", s4):
-//   per day     c = float32(float64 mean of the channel) -- it keeps P small against Q, nothing else depends on it;
+//   per day     c = float32((float64 sum of the channel's FINITE samples) / N), 0 when none is finite -- it keeps P small
+//               against Q, nothing else depends on it, so a NaN or +-Inf sample must not reach it: with the plain mean
+//               one bad sample made d' NaN for the whole channel, windows in front of it included;
 //               d'; double prefix sums of d' and d'^2 in the 1024-sample hierarchy of mf_csum_*; an integer prefix count
 //               of d[n] == d[n - 1]; r_c = 1 / sqrtf((float)E_c), +Inf for a window of L equal samples (decided from the
 //               count, exactly: the main kernels' r_t * r_c < 1000 guard then yields +0)
@@ -41,8 +43,9 @@ DayRegion carve_day(void* base, size_t N, size_t n_ch)
 
 size_t batch_region_bytes(size_t T, size_t n_ch, size_t L) { return align_up(T * n_ch * L * sizeof(float), 256); }
 
-// part[ch, p] = double sum of the samples [p * SUM_PART, (p + 1) * SUM_PART) of channel ch: every thread sums a
-// strided share, the shares are added in a fixed tree (the same bits on every run).
+// part[ch, p] = double sum of the finite samples among [p * SUM_PART, (p + 1) * SUM_PART) of channel ch (a NaN or +-Inf
+// sample adds +0: the sum of a finite channel keeps its bits): every thread sums a strided share, the shares are added
+// in a fixed tree (the same bits on every run).
 __global__ __launch_bounds__(256) void mf_full_part_sum_kernel(const float* __restrict__ data, size_t N, size_t n_parts,
                                                                double* __restrict__ part)
 {
@@ -51,7 +54,10 @@ __global__ __launch_bounds__(256) void mf_full_part_sum_kernel(const float* __re
     const size_t n0 = p * SUM_PART, n1 = n0 + SUM_PART < N ? n0 + SUM_PART : N;
     const float* d = data + ch * N;
     double acc = 0.0;
-    for (size_t n = n0 + threadIdx.x; n < n1; n += 256) acc = acc + (double)d[n];
+    for (size_t n = n0 + threadIdx.x; n < n1; n += 256) {
+        const float v = d[n];
+        acc = acc + ((__float_as_uint(v) & 0x7fffffffu) < 0x7f800000u ? (double)v : 0.0);
+    }
     s_sum[threadIdx.x] = acc;
     __syncthreads();
     for (int h = 128; h > 0; h >>= 1) {
@@ -61,7 +67,7 @@ __global__ __launch_bounds__(256) void mf_full_part_sum_kernel(const float* __re
     if (threadIdx.x == 0) part[ch * n_parts + p] = s_sum[0];
 }
 
-// mean[ch] = float32(sum of the channel's parts / N)   (one thread per channel)
+// mean[ch] = float32(sum of the channel's parts / N): the sum of the finite samples over ALL N   (one thread per channel)
 __global__ void mf_full_mean_kernel(const double* __restrict__ part, size_t n_ch, size_t n_parts, size_t N,
                                     float* __restrict__ mean)
 {

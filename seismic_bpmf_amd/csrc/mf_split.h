@@ -98,7 +98,16 @@ __host__ __device__ inline int band_o_off(int nks)
 }
 __host__ __device__ inline size_t split_row_bytes(size_t N) { return ((N + 7) / 8) * 32; }
 
-// power-of-two scale exponent of a channel from the bits of its largest magnitude (0: all zero or non-finite)
+// |x| as bits for a channel's maximum: a non-finite sample (Inf, NaN: bits >= 0x7f800000) counts as 0, so that one bad
+// sample does not decide the scale of a whole day -- it still splits into non-finite halves and poisons the lags
+// whose K range holds it, and only those (non-finite samples)
+__device__ __forceinline__ unsigned finite_abs_bits(float x)
+{
+    const unsigned b = __float_as_uint(x) & 0x7fffffffu;
+    return b >= 0x7f800000u ? 0u : b;
+}
+
+// power-of-two scale exponent of a channel from the bits of its largest FINITE magnitude (0: all zero / no finite sample)
 __host__ __device__ inline int scale_exp_of(unsigned maxbits)
 {
     if (maxbits == 0u || maxbits >= 0x7f800000u) return 0;
@@ -128,14 +137,14 @@ __device__ __forceinline__ void split_one(float v, float lo_scale, unsigned shor
 }
 
 // ---------------------------------------------------------------------- per-day preparation
-// largest |x| of every channel (bits; a NaN ends up above Inf): grid (blocks, n_ch)
+// largest finite |x| of every channel (bits): grid (blocks, n_ch)
 __global__ __launch_bounds__(256) void sp_absmax_kernel(const float* __restrict__ data, size_t N,
                                                         unsigned* __restrict__ maxbits)
 {
     const float* d = data + (size_t)blockIdx.y * N;
     unsigned m = 0;
     for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < N; i += (size_t)gridDim.x * 256)
-        m = max(m, __float_as_uint(d[i]) & 0x7fffffffu);
+        m = max(m, finite_abs_bits(d[i]));
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) m = max(m, (unsigned)__shfl_xor((int)m, o));
     if ((threadIdx.x & 63) == 0 && m) atomicMax(maxbits + blockIdx.y, m);
@@ -195,7 +204,7 @@ __global__ __launch_bounds__(64) void sp_band_kernel(const float* __restrict__ t
     const int lane = threadIdx.x;
     const float* x = tmpl + tc * (size_t)L;
     unsigned m = 0;
-    for (int l = lane; l < L; l += 64) m = max(m, __float_as_uint(x[l]) & 0x7fffffffu);
+    for (int l = lane; l < L; l += 64) m = max(m, finite_abs_bits(x[l]));
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) m = max(m, (unsigned)__shfl_xor((int)m, o));
     const int s = scale_exp_of(m);

@@ -62,6 +62,15 @@ def _is_flat(rows):
     return (rows == rows[..., :1]).all(axis=-1)
 
 
+def channel_constant(d):
+    """c of one channel: float32((float64 sum of its finite samples) / N), 0 when none is finite.  On a finite channel
+    this is float32(float64 mean) bit for bit (a bad sample adds +0 to the same summation); a NaN or +-Inf sample must
+    not reach c, or d' = d - c is NaN for the whole day of the channel."""
+    d64 = np.asarray(d).astype(np.float64)
+    with np.errstate(invalid="ignore"):
+        return np.float32(np.where(np.isfinite(d64), d64, 0.0).sum() / d64.size)
+
+
 def mf_full_f64(templates, moveouts, weights, data, step=1, lags=None, exclusive_last_lag=False,
                 range_all_channels=False, exact=False):
     """The definition at `lags` (all of them when None): an fa.MFRef with cc, B (T, n_lags, S, C), net, B_net, valid,
@@ -102,7 +111,7 @@ def mf_full_f64(templates, moveouts, weights, data, step=1, lags=None, exclusive
             if not ref.active[:, s, c].any():
                 continue
             d64 = data[s, c].astype(np.float64)
-            c32 = np.float32(d64.mean())
+            c32 = channel_constant(data[s, c])
             y_all = d64 - float(c32)                               # d - c (the difference of two floats: exact in double)
             dp_all = (data[s, c] - c32).astype(np.float32).astype(np.float64)      # d' = fl32(d - c)
             rows_raw = np.lib.stride_tricks.sliding_window_view(data[s, c], L)
@@ -215,7 +224,7 @@ def mf_full_emulate(templates, moveouts, weights, data, step=1, lags=None, drop=
             s, c = divmod(ch, C)
             d = flat_data[ch]
             src = flat_data[(ch + 1) % n_ch] if drop == "c_neighbour" else d
-            c32 = np.float32(src.astype(np.float64).mean())
+            c32 = channel_constant(src)
             dp = d.copy() if drop == "data_mean" else (d - c32).astype(np.float32)
             dp64 = dp.astype(np.float64)
             csP = np.concatenate([[0.0], np.cumsum(dp64)])

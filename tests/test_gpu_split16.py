@@ -190,8 +190,28 @@ def test_split16_edge_cases(oracle_lib, split16):
     _check(got, want, w1, "split16 edge: zero energy")
     got_c = matched_filter(tp2, mv0, w1, d2, 1, check_zeros=False, network_sum=False)
     assert not got_c[:, :, 1].any() and not got_c[0, :, 0, 0].any()
-    # non-finite data poison only what they touch and never reach other templates' rows as Inf
-    # (BPMF scrubs NaN from the result, similarity_search.py:540)
+
+
+def test_split16_nonfinite_data_poison_only_what_they_touch(oracle_lib, split16):
+    """Non-finite data poison only what they touch and never reach other templates' rows as Inf (BPMF scrubs NaN from the
+    result, similarity_search.py:540): a template that gives the bad channels no weight keeps a finite row with the bits
+    of the cleaned day; the rows that use them hold numbers and NaN, NaN where the oracle has NaN, never +-Inf.  (The
+    rule per lag, every family and the segments: tests/test_gpu_mf_nonfinite.py.)"""
+    import nonfinite_cases as nc
+    from seismic_bpmf_amd import matched_filter
+    for case in nc.cases(200, 1, T=3, align=False, big=False)[:3]:
+        w = case.w.copy()
+        for s, c, _, _ in case.bad:
+            w[0, s, c] = 0.0                               # template 0 does not use the bad channels
+        cl = nc.cleaned(case)
+        got = matched_filter(case.tp, case.mv, w, case.data, 1, check_zeros=False)
+        ref = matched_filter(cl.tp, cl.mv, w, cl.data, 1, check_zeros=False)
+        want = oracle_lib.matched_filter(case.tp, case.mv, w, case.data, 1, True)
+        assert not np.isinf(got).any(), case.name
+        assert np.isfinite(got[0]).all() and np.array_equal(got[0].view(np.uint32), ref[0].view(np.uint32)), case.name
+        _check(got[:1], want[:1], w[:1], f"split16, a row beside bad channels: {case.name}")
+        assert not (np.isnan(want) & ~np.isnan(got)).any(), case.name      # (more NaN only within R of a bad sample)
+        assert np.isnan(got[1:]).sum() <= np.isnan(want[1:]).sum() + 2 * 64 * len(case.bad), case.name
 
 
 def test_split16_autocorrelation_and_detection_indices(split16):

@@ -186,15 +186,20 @@ __global__ __launch_bounds__(1024) void bp_likelihood_kernel(const float* __rest
 namespace {
 struct RelocateLayout {
     BpSchedule sch;         // prestacks and partial rows of the max-beams (bp_max_batch)
-    size_t o_beam, o_arg, total;
+    void* sch_ws;           // the schedule's block: the prestacks U lie at its start
+    float* beam;            // [E, N] the spatial method's max-beams and their sources
+    int32_t* arg;
+    size_t total;
 };
-RelocateLayout relocate_layout(const bpmf_bp_plan* pl, size_t E, size_t N, int forced_split)
+RelocateLayout relocate_layout(void* ws, const bpmf_bp_plan* pl, size_t E, size_t N, int forced_split)
 {
     RelocateLayout l;
+    Carver c(ws);
     l.sch = bp_schedule(pl->shape, N, BPMF_BP_REDUCE_MAX, forced_split, E);
-    l.o_beam = l.sch.total;
-    l.o_arg = l.o_beam + align_up(E * N * sizeof(float), 256);
-    l.total = l.o_arg + align_up(E * N * sizeof(int32_t), 256);
+    l.sch_ws = c.nest(l.sch.total);
+    l.beam = c.take<float>(E * N);
+    l.arg = c.take<int32_t>(E * N);
+    l.total = c.bytes();
     return l;
 }
 }  // namespace
@@ -207,7 +212,7 @@ extern "C" size_t bpmf_bp_relocate_workspace_bytes(const bpmf_bp_plan* pl, size_
 {
     (void)C;
     if (!pl || E == 0 || N == 0) return 0;
-    return relocate_layout(pl, E, N, (int)option(OPT_BP_SPLIT)).total;
+    return relocate_layout(nullptr, pl, E, N, (int)option(OPT_BP_SPLIT)).total;
 }
 
 extern "C" int bpmf_bp_relocate_batch_dev(const bpmf_bp_plan* pl, const float* d_features, size_t event_stride,
@@ -246,15 +251,15 @@ extern "C" int bpmf_bp_relocate_batch_dev(const bpmf_bp_plan* pl, const float* d
         return -1;
     }
     const int forced_split = (int)option(OPT_BP_SPLIT);        // read once: the size check and the launches agree
-    const RelocateLayout l = relocate_layout(pl, E, N, forced_split);
+    const RelocateLayout l = relocate_layout(d_workspace, pl, E, N, forced_split);
     if (workspace_bytes < l.total) {
         set_error("bpmf_bp_relocate_batch_dev: workspace too small (%zu < %zu)", workspace_bytes, l.total);
         return -1;
     }
     const int S = (int)pl->shape.S, P = (int)pl->shape.P, K = (int)pl->shape.K;
-    float* U = (float*)d_workspace;
-    float* beam = spatial ? (float*)((char*)d_workspace + l.o_beam) : d_maxbeam;
-    int32_t* arg = spatial ? (int32_t*)((char*)d_workspace + l.o_arg) : d_maxbeam_sources;
+    float* U = (float*)l.sch_ws;
+    float* beam = spatial ? l.beam : d_maxbeam;
+    int32_t* arg = spatial ? l.arg : d_maxbeam_sources;
     float* column = d_columns ? d_columns : d_likelihood;
     // option debug.poison_output (tests): what no kernel writes comes back as NaN / -1
     if (option(OPT_DEBUG_POISON_OUTPUT) != 0) {
@@ -278,7 +283,7 @@ extern "C" int bpmf_bp_relocate_batch_dev(const bpmf_bp_plan* pl, const float* d
             d_features, event_stride, (long long)row_stride, (const long long*)d_starts, d_w_phases, (long long)N,
             (int)C, P, U);
     BPMF_LAUNCH_CHECK();
-    if (int rc = bp_max_batch(pl, l.sch, d_workspace, N, E, out_of_bounds, stream, beam, arg))
+    if (int rc = bp_max_batch(pl, l.sch, l.sch_ws, N, E, out_of_bounds, stream, beam, arg))
         return rc;
     if (spatial)
         bp_focus_kernel<true><<<dim3((unsigned)E), dim3(256), 0, stream>>>(beam, arg, (int)N, d_time_idx, d_src_idx, d_max_beam);

@@ -333,16 +333,21 @@ __global__ __launch_bounds__(UNC_THREADS) void bp_unc_final_kernel(
 size_t unc_blocks(size_t n_terms) { return (n_terms + UNC_THREADS - 1) / UNC_THREADS; }
 
 struct UncLayout {
-    size_t o_cnt, o_base, o_cw, total;                 // the float64 block sums lie at 0
+    double* part;                                      // the float64 block sums
+    int *cnt, *base;
+    float* cw;
+    size_t total;
 };
-UncLayout unc_layout(size_t E, size_t n_terms)
+UncLayout unc_layout(void* ws, size_t E, size_t n_terms)
 {
     const size_t nb = unc_blocks(n_terms);
     UncLayout l;
-    l.o_cnt = align_up(E * nb * 2 * sizeof(double), 256);
-    l.o_base = l.o_cnt + align_up(E * nb * sizeof(int), 256);
-    l.o_cw = l.o_base + align_up(E * (nb + 1) * sizeof(int), 256);
-    l.total = l.o_cw + align_up(E * n_terms * sizeof(float), 256);
+    Carver c(ws);
+    l.part = c.take<double>(E * nb * 2);
+    l.cnt = c.take<int>(E * nb);
+    l.base = c.take<int>(E * (nb + 1));
+    l.cw = c.take<float>(E * n_terms);
+    l.total = c.bytes();
     return l;
 }
 
@@ -354,7 +359,7 @@ using namespace bpmf;
 extern "C" size_t bpmf_bp_location_uncertainty_workspace_bytes(size_t E, size_t n_terms)
 {
     if (E == 0 || n_terms == 0 || E > 65535 || n_terms > 0x7fff0000ull) return 0;     // (sizes the call refuses)
-    return unc_layout(E, n_terms).total;
+    return unc_layout(nullptr, E, n_terms).total;
 }
 
 extern "C" int bpmf_bp_location_uncertainty_dev(const bpmf_bp_plan* pl, int method, size_t E, size_t N,
@@ -396,7 +401,8 @@ extern "C" int bpmf_bp_location_uncertainty_dev(const bpmf_bp_plan* pl, int meth
                   half_side_km, dist_per_lon, effective_kT, gibbs_cutoff);
         return -1;
     }
-    const size_t need = bpmf_bp_location_uncertainty_workspace_bytes(E, n_terms);
+    const UncLayout l = unc_layout(d_workspace, E, n_terms);
+    const size_t need = l.total;
     if (workspace_bytes < need) {
         set_error("%s: workspace too small (%zu < %zu)", me, workspace_bytes, need);
         return -1;
@@ -410,33 +416,28 @@ extern "C" int bpmf_bp_location_uncertainty_dev(const bpmf_bp_plan* pl, int meth
         if (d_domain_mask) BPMF_HIP_CHECK(hipMemsetAsync(d_domain_mask, 0xFF, E * K, stream));
     }
     const unsigned nb = (unsigned)unc_blocks(n_terms);
-    const UncLayout l = unc_layout(E, n_terms);
-    double* part = (double*)d_workspace;
-    int* cnt = (int*)((char*)d_workspace + l.o_cnt);
-    int* base = (int*)((char*)d_workspace + l.o_base);
-    float* cw = (float*)((char*)d_workspace + l.o_cw);
     const UncTables T{d_tables, (int)K, pl->shape.id_offset};
     const dim3 grid(nb, (unsigned)E), wg(UNC_THREADS);
     const int nt = (int)n_terms;
     if (spatial)
         bp_unc_count_kernel<true><<<grid, wg, 0, stream>>>(d_src_idx, T, nt, d_likelihood, nullptr, nullptr,
-                                                           dist_per_lon, half_side_km, kT, cutoff, cnt, d_domain_mask);
+                                                           dist_per_lon, half_side_km, kT, cutoff, l.cnt, d_domain_mask);
     else
         bp_unc_count_kernel<false><<<grid, wg, 0, stream>>>(d_src_idx, T, nt, d_maxbeam, d_maxbeam_sources, d_max_beam,
-                                                            dist_per_lon, half_side_km, kT, cutoff, cnt, nullptr);
+                                                            dist_per_lon, half_side_km, kT, cutoff, l.cnt, nullptr);
     BPMF_LAUNCH_CHECK();
-    bp_unc_scan_kernel<<<dim3((unsigned)E), wg, 0, stream>>>(cnt, (int)nb, base);
+    bp_unc_scan_kernel<<<dim3((unsigned)E), wg, 0, stream>>>(l.cnt, (int)nb, l.base);
     BPMF_LAUNCH_CHECK();
     if (spatial)
         bp_unc_partial_kernel<true><<<grid, wg, 0, stream>>>(d_src_idx, T, nt, d_likelihood, nullptr, nullptr,
-                                                             dist_per_lon, half_side_km, kT, cutoff, base, cw, part);
+                                                             dist_per_lon, half_side_km, kT, cutoff, l.base, l.cw, l.part);
     else
         bp_unc_partial_kernel<false><<<grid, wg, 0, stream>>>(d_src_idx, T, nt, d_maxbeam, d_maxbeam_sources,
-                                                              d_max_beam, dist_per_lon, half_side_km, kT, cutoff, base,
-                                                              cw, part);
+                                                              d_max_beam, dist_per_lon, half_side_km, kT, cutoff, l.base,
+                                                              l.cw, l.part);
     BPMF_LAUNCH_CHECK();
-    bp_unc_final_kernel<<<dim3((unsigned)E), wg, 0, stream>>>(d_src_idx, T, nt, (int)nb, part, base, cw, d_hunc, d_vunc,
-                                                             d_n_domain, d_longitude, d_latitude, d_depth);
+    bp_unc_final_kernel<<<dim3((unsigned)E), wg, 0, stream>>>(d_src_idx, T, nt, (int)nb, l.part, l.base, l.cw, d_hunc,
+                                                             d_vunc, d_n_domain, d_longitude, d_latitude, d_depth);
     BPMF_LAUNCH_CHECK();
     return 0;
 }

@@ -4,6 +4,7 @@
 #include <cstdarg>
 #include <cstdint>
 #include <cstdio>
+#include "workspace.h"  // align_up, Carver
 
 namespace bpmf {
 
@@ -16,8 +17,6 @@ constexpr float MAX_NORM = 1000.0f;          // r_t * r_d >= this (E_t*E_d <~ 1e
 
 // bench hook: events around the dominant kernels (util.hip)
 void profile_mark(int which, int edge, hipStream_t stream);
-
-inline size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
 
 // Execution options (util.hip, C ABI: bpmf_set_option / bpmf_get_option).  Every option selects
 // among code paths and sizes that produce IDENTICAL results -- kernel family, LDS budget, staging

@@ -171,11 +171,21 @@ __global__ __launch_bounds__(ITP_THREADS) void intertp_cc_kernel(
 
 using namespace bpmf;
 
+struct ItpWs { float *r_t, *r_d; size_t bytes; };      // the norms of the template rows, of every lagged window of them
+static ItpWs itp_carve(void* base, size_t n_rows, size_t n_lag)
+{
+    ItpWs w;
+    Carver c(base);
+    w.r_t = c.take<float>(n_rows);
+    w.r_d = c.take<float>(n_rows * n_lag);
+    w.bytes = c.bytes();
+    return w;
+}
+
 extern "C" size_t bpmf_intertemplate_workspace_bytes(size_t T, size_t S, size_t C, size_t max_lag)
 {
-    const size_t n_rows = T * S * C, n_lag = 2 * max_lag + 1;
     if (max_lag > 31) return 0;                           // (the call refuses it)
-    return align_up(n_rows * sizeof(float), 256) + align_up(n_rows * n_lag * sizeof(float), 256);
+    return itp_carve(nullptr, T * S * C, 2 * max_lag + 1).bytes;
 }
 
 extern "C" int bpmf_intertemplate_cc_dev(const float* d_waveforms, const float* d_base_weights,
@@ -199,7 +209,8 @@ extern "C" int bpmf_intertemplate_cc_dev(const float* d_waveforms, const float* 
         set_error("bpmf_intertemplate_cc_dev: too many templates / channels");
         return -1;
     }
-    if (workspace_bytes < bpmf_intertemplate_workspace_bytes(T, S, C, max_lag)) {
+    const ItpWs ws = itp_carve(d_workspace, n_rows, n_lag);
+    if (workspace_bytes < ws.bytes) {
         set_error("bpmf_intertemplate_cc_dev: workspace too small");
         return -1;
     }
@@ -220,14 +231,12 @@ extern "C" int bpmf_intertemplate_cc_dev(const float* d_waveforms, const float* 
     // option debug.poison_output (tests): an entry no kernel writes comes back as NaN
     if (option(OPT_DEBUG_POISON_OUTPUT) != 0)
         BPMF_HIP_CHECK(hipMemsetAsync(d_out, 0xFF, T * T * sizeof(float), stream));
-    float* r_t = (float*)d_workspace;
-    float* r_d = (float*)((char*)d_workspace + align_up(n_rows * sizeof(float), 256));
     intertp_norms_kernel<<<dim3((unsigned)((n_rows + 127) / 128)), dim3(128), 0, stream>>>(
-        d_waveforms, (int)n_rows, (int)Lw, (int)max_lag, r_t, r_d);
+        d_waveforms, (int)n_rows, (int)Lw, (int)max_lag, ws.r_t, ws.r_d);
     BPMF_LAUNCH_CHECK();
     dim3 grid((unsigned)((T + ITP_UB - 1) / ITP_UB), (unsigned)T);
     intertp_cc_kernel<<<grid, dim3(ITP_THREADS), need(ch_chunk), stream>>>(
-        d_waveforms, d_base_weights, d_pair_mask, r_t, r_d, (int)T, (int)n_ch, (int)Lw, (int)max_lag,
+        d_waveforms, d_base_weights, d_pair_mask, ws.r_t, ws.r_d, (int)T, (int)n_ch, (int)Lw, (int)max_lag,
         (int)ch_chunk, d_out);
     BPMF_LAUNCH_CHECK();
     return 0;

@@ -1245,29 +1245,40 @@ struct MfWorkspace {
     size_t bytes;
 };
 
+// The per-day head of both layouts.
+static void mf_carve_day(Carver& c, MfWorkspace& ws, size_t L, size_t N, size_t n_ch)
+{
+    const size_t nq = (N + CSUM_CHUNK - 1) / CSUM_CHUNK;
+    const size_t nwin = N >= L ? N - L + 1 : 0;
+    ws.local = c.take<double>(n_ch * N);
+    ws.tot = c.take<double>(n_ch * nq);
+    ws.off = c.take<double>(n_ch * nq);
+    c.skip(256);  // slack: the main kernel's 16-byte norm loads may start 3 floats early ...
+    ws.e_d = c.take<float>(n_ch * nwin, 64);  // ... or end 3 late
+    ws.sp_day = nullptr;
+    ws.sp_batch = nullptr;
+}
+
+// The per-batch tail of both layouts: everything that depends on T.
+static void mf_carve_batch(Carver& c, MfWorkspace& ws, size_t T, size_t n_ch)
+{
+    ws.e_t = c.take<float>(T * n_ch);
+    ws.range = c.take<int2>(T);
+    ws.chan_rec = c.take<int4>(T * (n_ch + 2));
+}
+
 static MfWorkspace mf_carve(void* base, size_t L, size_t N, size_t T, size_t n_ch)
 {
     MfWorkspace ws;
-    const size_t nq = (N + CSUM_CHUNK - 1) / CSUM_CHUNK;
-    const size_t nwin = N >= L ? N - L + 1 : 0;
-    char* p = (char*)base;
-    size_t o = 0;
-    ws.local = (double*)(p + o); o += align_up(n_ch * N * sizeof(double), 256);
-    ws.tot = (double*)(p + o);   o += align_up(n_ch * nq * sizeof(double), 256);
-    ws.off = (double*)(p + o);   o += align_up(n_ch * nq * sizeof(double), 256);
-    o += 256;  // slack: the main kernel's 16-byte norm loads may start 3 floats early ...
-    ws.e_d = (float*)(p + o);    o += align_up(n_ch * nwin * sizeof(float) + 64, 256);  // ... or end 3 late
+    Carver c(base);
+    mf_carve_day(c, ws, L, N, n_ch);
     // option mf.split16: the split day lies with the per-day arrays, in front of everything that depends on T (a
     // prepared day stays valid when the template count changes); the option is part of the workspace's size
     const bool split16 = option(OPT_MF_SPLIT16) != 0;
-    ws.sp_day = nullptr;
-    ws.sp_batch = nullptr;
-    if (split16) { ws.sp_day = p + o; o += align_up(sp::day_region_bytes(N, n_ch), 256); }
-    ws.e_t = (float*)(p + o);    o += align_up(T * n_ch * sizeof(float), 256);
-    ws.range = (int2*)(p + o);   o += align_up(T * sizeof(int2), 256);
-    ws.chan_rec = (int4*)(p + o); o += align_up(T * (n_ch + 2) * sizeof(int4), 256);
-    if (split16) { ws.sp_batch = p + o; o += align_up(sp::batch_region_bytes(T, n_ch, L), 256); }
-    ws.bytes = o;
+    if (split16) ws.sp_day = c.nest(sp::day_region_bytes(N, n_ch));
+    mf_carve_batch(c, ws, T, n_ch);
+    if (split16) ws.sp_batch = c.nest(sp::batch_region_bytes(T, n_ch, L));
+    ws.bytes = c.bytes();
     return ws;
 }
 
@@ -1284,24 +1295,12 @@ struct MfFullWorkspace {
 static MfFullWorkspace mf_carve_full(void* base, size_t L, size_t N, size_t T, size_t n_ch)
 {
     MfFullWorkspace f;
-    MfWorkspace& ws = f.ws;
-    const size_t nq = (N + CSUM_CHUNK - 1) / CSUM_CHUNK;
-    const size_t nwin = N >= L ? N - L + 1 : 0;
-    char* p = (char*)base;
-    size_t o = 0;
-    ws.local = (double*)(p + o); o += align_up(n_ch * N * sizeof(double), 256);
-    ws.tot = (double*)(p + o);   o += align_up(n_ch * nq * sizeof(double), 256);
-    ws.off = (double*)(p + o);   o += align_up(n_ch * nq * sizeof(double), 256);
-    o += 256;  // (the slack around the norms: mf_carve)
-    ws.e_d = (float*)(p + o);    o += align_up(n_ch * nwin * sizeof(float) + 64, 256);
-    ws.sp_day = nullptr;
-    ws.sp_batch = nullptr;
-    f.day = full::carve_day(p + o, N, n_ch); o += f.day.bytes;
-    ws.e_t = (float*)(p + o);    o += align_up(T * n_ch * sizeof(float), 256);
-    ws.range = (int2*)(p + o);   o += align_up(T * sizeof(int2), 256);
-    ws.chan_rec = (int4*)(p + o); o += align_up(T * (n_ch + 2) * sizeof(int4), 256);
-    f.tprime = (float*)(p + o);  o += full::batch_region_bytes(T, n_ch, L);
-    ws.bytes = o;
+    Carver c(base);
+    mf_carve_day(c, f.ws, L, N, n_ch);
+    f.day = full::carve_day(c.nest(full::carve_day(nullptr, N, n_ch).bytes), N, n_ch);
+    mf_carve_batch(c, f.ws, T, n_ch);
+    f.tprime = (float*)c.nest(full::batch_region_bytes(T, n_ch, L));
+    f.ws.bytes = c.bytes();
     return f;
 }
 

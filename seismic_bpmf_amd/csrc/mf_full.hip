@@ -25,19 +25,18 @@ DayRegion carve_day(void* base, size_t N, size_t n_ch)
     DayRegion r;
     const size_t nq = (N + CSUM_CHUNK - 1) / CSUM_CHUNK;
     const size_t n_parts = (N + SUM_PART - 1) / SUM_PART;
-    char* p = (char*)base;
-    size_t o = 0;
+    Carver c(base);
     // (the main kernels read d' through per-channel buffer descriptors: nothing outside [0, N) of a channel is fetched)
-    r.dprime = (float*)(p + o);   o += align_up(n_ch * N * sizeof(float), 256);
-    r.local_p = (double*)(p + o); o += align_up(n_ch * N * sizeof(double), 256);
-    r.tot_p = (double*)(p + o);   o += align_up(n_ch * nq * sizeof(double), 256);
-    r.off_p = (double*)(p + o);   o += align_up(n_ch * nq * sizeof(double), 256);
-    r.local_eq = (int*)(p + o);   o += align_up(n_ch * N * sizeof(int), 256);
-    r.tot_eq = (int*)(p + o);     o += align_up(n_ch * nq * sizeof(int), 256);
-    r.off_eq = (int*)(p + o);     o += align_up(n_ch * nq * sizeof(int), 256);
-    r.part = (double*)(p + o);    o += align_up(n_ch * n_parts * sizeof(double), 256);
-    r.mean = (float*)(p + o);     o += align_up(n_ch * sizeof(float), 256);
-    r.bytes = o;
+    r.dprime = c.take<float>(n_ch * N);
+    r.local_p = c.take<double>(n_ch * N);
+    r.tot_p = c.take<double>(n_ch * nq);
+    r.off_p = c.take<double>(n_ch * nq);
+    r.local_eq = c.take<int>(n_ch * N);
+    r.tot_eq = c.take<int>(n_ch * nq);
+    r.off_eq = c.take<int>(n_ch * nq);
+    r.part = c.take<double>(n_ch * n_parts);
+    r.mean = c.take<float>(n_ch);
+    r.bytes = c.bytes();
     return r;
 }
 

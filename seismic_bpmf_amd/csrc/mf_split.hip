@@ -10,29 +10,37 @@ namespace bpmf {
 namespace sp {
 
 namespace {
-struct DayRegion { u32x4* planes; unsigned* maxbits; int* s_exp; float* scd; };
+struct DayRegion { u32x4* planes; unsigned* maxbits; int* s_exp; float* scd; size_t bytes; };
 DayRegion carve_day(void* base, size_t N, size_t n_ch)
 {
-    char* p = (char*)base;
+    Carver c(base);
     DayRegion r;
-    size_t o = 0;
-    r.planes = (u32x4*)(p + o);  o += align_up(n_ch * split_row_bytes(N), 256);
-    r.maxbits = (unsigned*)(p + o); o += align_up(n_ch * sizeof(unsigned), 256);
-    r.s_exp = (int*)(p + o);     o += align_up(n_ch * sizeof(int), 256);
-    r.scd = (float*)(p + o);
+    r.planes = (u32x4*)c.nest(n_ch * split_row_bytes(N));
+    r.maxbits = c.take<unsigned>(n_ch);
+    r.s_exp = c.take<int>(n_ch);
+    r.scd = c.take<float>(n_ch);
+    r.bytes = c.bytes();
+    return r;
+}
+
+struct BatchRegion { unsigned* bands; float* sct; size_t bytes; };
+BatchRegion carve_batch(void* base, size_t T, size_t n_ch, size_t n_seg)
+{
+    Carver c(base);
+    BatchRegion r;
+    r.bands = (unsigned*)c.nest(T * n_ch * n_seg * (size_t)BAND_BYTES);
+    r.sct = c.take<float>(T * n_ch);
+    r.bytes = c.bytes();
     return r;
 }
 }  // namespace
 
-size_t day_region_bytes(size_t N, size_t n_ch)
-{
-    return align_up(n_ch * split_row_bytes(N), 256) + 3 * align_up(n_ch * 4, 256);
-}
+size_t day_region_bytes(size_t N, size_t n_ch) { return carve_day(nullptr, N, n_ch).bytes; }
 
 size_t batch_region_bytes(size_t T, size_t n_ch, size_t L)
 {
     const size_t n_seg = L ? (size_t)n_segments_of((int)std::min<size_t>(L, (size_t)max_template_len())) : 1;
-    return align_up(T * n_ch * n_seg * (size_t)BAND_BYTES, 256) + align_up(T * n_ch * sizeof(float), 256);
+    return carve_batch(nullptr, T, n_ch, n_seg).bytes;
 }
 
 bool usable(size_t L, size_t N)
@@ -67,14 +75,13 @@ int run(const float* d_templates, const int32_t* d_moveouts, const void* day_reg
 {
     const DayRegion r = carve_day(const_cast<void*>(day_region), N, n_ch);
     const int n_seg = n_segments_of((int)L), seg_len = segment_len_of((int)L);
-    unsigned* bands = (unsigned*)batch_region;
-    float* sct = (float*)((char*)batch_region + align_up(T * n_ch * (size_t)n_seg * (size_t)BAND_BYTES, 256));
+    const BatchRegion b = carve_batch(batch_region, T, n_ch, (size_t)n_seg);
     if (T * n_ch * (size_t)n_seg >= 0x7fffffffull || T * (nb_cnt + 8) >= 0x7fffffffull) {
         set_error("mf.split16: grid too large");
         return -1;
     }
     sp_band_kernel<<<dim3((unsigned)(T * n_ch * (size_t)n_seg)), dim3(64), 0, stream>>>(d_templates, d_moveouts, (int)L, n_seg,
-                                                                                      seg_len, bands, sct);
+                                                                                      seg_len, b.bands, b.sct);
     BPMF_LAUNCH_CHECK();
     const dim3 grid((unsigned)(8 * ((T * nb_cnt + 7) / 8)));
 #define BPMF_SP_LAUNCH(NS, S1)                                                                                       \
@@ -83,7 +90,7 @@ int run(const float* d_templates, const int32_t* d_moveouts, const void* day_reg
     do {                                                                                                             \
         auto kfn = mf_split_kernel<NS, S1, 0, SG>;                                                                   \
         /* (62 464 bytes of dynamic LDS: below the 64 KB that need no opt-in) */                                     \
-        kfn<<<grid, dim3(THREADS), WG_LDS, stream>>>(r.planes, bands, sct, r.scd, chan_rec, e_d, range, (int)L,      \
+        kfn<<<grid, dim3(THREADS), WG_LDS, stream>>>(r.planes, b.bands, b.sct, r.scd, chan_rec, e_d, range, (int)L,  \
                                                      (long long)N, (int)T, (int)n_ch, (long long)n_corr, (int)step,   \
                                                      d_cc_out, (int)nb_cnt, (int)nb_lo, sqrt_norm ? 4 : 0, n_seg,     \
                                                      seg_len);                                                        \

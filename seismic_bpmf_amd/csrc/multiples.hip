@@ -138,10 +138,21 @@ __global__ __launch_bounds__(64) void multiples_flag_kernel(const double* __rest
 
 using namespace bpmf;
 
+struct FmWs { int *bad_row, *end; size_t bytes; };      // the row-check word, the span ends of the n events
+static FmWs fm_carve(void* base, size_t n)
+{
+    FmWs w;
+    Carver c(base);
+    w.bad_row = (int*)c.nest(FM_ERROR_BYTES, 16);
+    w.end = c.take<int>(n, 0, 16);
+    w.bytes = c.bytes();
+    return w;
+}
+
 extern "C" size_t bpmf_flag_multiples_workspace_bytes(size_t n)
 {
     if (n > 0x7ffffffeull) return 0;                      // (more events than the call takes)
-    return FM_ERROR_BYTES + align_up(n * sizeof(int), 16);
+    return fm_carve(nullptr, n).bytes;
 }
 
 extern "C" int bpmf_flag_multiples_dev(const double* d_t_sorted, const int32_t* d_rows_sorted, const float* d_cc_sorted,
@@ -159,23 +170,21 @@ extern "C" int bpmf_flag_multiples_dev(const double* d_t_sorted, const int32_t* 
         set_error("bpmf_flag_multiples_dev: bad argument (n=%zu T=%zu)", n, T);
         return -1;
     }
-    if (workspace_bytes < bpmf_flag_multiples_workspace_bytes(n)) {
-        set_error("bpmf_flag_multiples_dev: workspace of %zu bytes, %zu needed", workspace_bytes,
-                  bpmf_flag_multiples_workspace_bytes(n));
+    const FmWs ws = fm_carve(d_workspace, n);
+    if (workspace_bytes < ws.bytes) {
+        set_error("bpmf_flag_multiples_dev: workspace of %zu bytes, %zu needed", workspace_bytes, ws.bytes);
         return -1;
     }
-    int* d_bad_row = (int*)d_workspace;
-    int* d_end = (int*)((char*)d_workspace + FM_ERROR_BYTES);
-    BPMF_HIP_CHECK(hipMemsetAsync(d_bad_row, 0xFF, FM_ERROR_BYTES, stream));        // -1: below every index
+    BPMF_HIP_CHECK(hipMemsetAsync(ws.bad_row, 0xFF, FM_ERROR_BYTES, stream));        // -1: below every index
     multiples_span_kernel<<<dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream>>>(
-        d_t_sorted, d_rows_sorted, (int)n, (int)T, dt_criterion, d_end, d_bad_row, d_unique_out);
+        d_t_sorted, d_rows_sorted, (int)n, (int)T, dt_criterion, ws.end, ws.bad_row, d_unique_out);
     BPMF_LAUNCH_CHECK();
     multiples_flag_kernel<<<dim3((unsigned)n), dim3(64), 0, stream>>>(
-        d_t_sorted, d_rows_sorted, d_cc_sorted, (int)n, d_pair_ok, (int)T, dt_criterion, d_end, d_unique_out);
+        d_t_sorted, d_rows_sorted, d_cc_sorted, (int)n, d_pair_ok, (int)T, dt_criterion, ws.end, d_unique_out);
     BPMF_LAUNCH_CHECK();
     // the one synchronisation of the call: the row check comes back, and the flags are complete behind it
     int bad_row = 0;
-    BPMF_HIP_CHECK(hipMemcpyAsync(&bad_row, d_bad_row, sizeof(int), hipMemcpyDeviceToHost, stream));
+    BPMF_HIP_CHECK(hipMemcpyAsync(&bad_row, ws.bad_row, sizeof(int), hipMemcpyDeviceToHost, stream));
     BPMF_HIP_CHECK(hipStreamSynchronize(stream));
     if (bad_row >= 0) {
         set_error("bpmf_flag_multiples_dev: event %d (in sorted order) names a template row outside [0, %zu)", bad_row, T);

@@ -355,15 +355,14 @@ struct TdtWorkspace {
 static TdtWorkspace tdt_carve(void* base, size_t rows, size_t n_glob, size_t n_win)
 {
     TdtWorkspace ws;
-    char* p = (char*)base;
-    size_t o = 0;
-    ws.part = (float*)(p + o);               o += align_up(rows * n_glob * sizeof(float), 256);
-    ws.cnt = (unsigned long long*)(p + o);   o += align_up(rows * n_glob * 8, 256);
-    ws.total = (unsigned long long*)(p + o); o += align_up(rows * 8, 256);
-    ws.centre = (float*)(p + o);             o += align_up(rows * sizeof(float), 256);
-    ws.dev = (float*)(p + o);                o += align_up(rows * sizeof(float), 256);
-    ws.diff = (float*)(p + o);               o += align_up(rows * n_win * sizeof(float), 256);
-    ws.bytes = o;
+    Carver c(base);
+    ws.part = c.take<float>(rows * n_glob);
+    ws.cnt = c.take<unsigned long long>(rows * n_glob);
+    ws.total = c.take<unsigned long long>(rows);
+    ws.centre = c.take<float>(rows);
+    ws.dev = c.take<float>(rows);
+    ws.diff = c.take<float>(rows * n_win);
+    ws.bytes = c.bytes();
     return ws;
 }
 

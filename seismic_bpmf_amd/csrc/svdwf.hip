@@ -90,6 +90,20 @@ static SvSizes sv_sizes(size_t n_max, size_t m)
     return z;
 }
 
+// The workspace: the offsets table, then `n_slots` slots of `slot` doubles (a multiple of 32: 256 bytes) each.
+struct SvWorkspace { long long* offsets; double* slots; size_t head, bytes; };
+
+static SvWorkspace sv_carve(void* base, size_t n_groups, size_t n_slots, size_t slot)
+{
+    SvWorkspace ws;
+    Carver c(base);
+    ws.offsets = c.take<long long>(n_groups + 1);
+    ws.head = c.offset();
+    ws.slots = c.take<double>(n_slots * slot);
+    ws.bytes = c.bytes();
+    return ws;
+}
+
 struct SvChannel {
     const float* A;                 // element (i, t) at A[i * ld + t]
     size_t ld;
@@ -625,9 +639,8 @@ extern "C" size_t bpmf_svdwf_workspace_bytes(size_t n_groups, size_t max_group_s
     const size_t large = max_group_size < n_samples ? n_samples : max_group_size;
     if (n_samples == 0 || small > (size_t)SV_MAX_SMALL || large > (size_t)SV_MAX_LARGE || n_groups >= (1ull << 31))
         return 0;
-    const size_t head = align_up((n_groups + 1) * sizeof(int64_t), 256);
-    if (max_group_size == 0 || n_channels == 0) return head;
-    return head + n_channels * sv_sizes(max_group_size, n_samples).slot * sizeof(double);
+    const size_t slot = sv_sizes(max_group_size, n_samples).slot;
+    return sv_carve(nullptr, n_groups, max_group_size ? n_channels : 0, slot).bytes;
 }
 
 extern "C" int bpmf_svdwf_stack_dev(const float* d_x, const int64_t* offsets, size_t n_groups, size_t S, size_t C,
@@ -689,12 +702,12 @@ extern "C" int bpmf_svdwf_stack_dev(const float* d_x, const int64_t* offsets, si
         return -1;
     }
     const size_t n_jobs = n_groups * SC;
-    const size_t head = align_up((n_groups + 1) * sizeof(int64_t), 256);
     const SvSizes z = sv_sizes(n_max ? n_max : 1, m);
     const size_t slot_bytes = z.slot * sizeof(double);
-    if (workspace_bytes < head + (n_max ? slot_bytes : 0)) {           // (empty groups only: no slot is touched)
+    const SvWorkspace ws = sv_carve(d_workspace, n_groups, n_max ? 1 : 0, z.slot);   // (empty groups only: no slot)
+    if (workspace_bytes < ws.bytes) {
         set_error("bpmf_svdwf_stack_dev: the workspace holds %zu bytes; one channel of %zu events x %zu samples takes "
-                  "%zu (bpmf_svdwf_workspace_bytes)", workspace_bytes, n_max, m, head + (n_max ? slot_bytes : 0));
+                  "%zu (bpmf_svdwf_workspace_bytes)", workspace_bytes, n_max, m, ws.bytes);
         return -1;
     }
     // option debug.poison_output (tests): an element the kernels skip comes back as NaN / -1 (behind the last
@@ -706,17 +719,17 @@ extern "C" int bpmf_svdwf_stack_dev(const float* d_x, const int64_t* offsets, si
         if (d_filtered_or_null && N)
             BPMF_HIP_CHECK(hipMemsetAsync(d_filtered_or_null, 0xFF, N * SC * m * sizeof(float), stream));
     }
-    size_t slab = n_max ? (workspace_bytes - head) / slot_bytes : (size_t)SV_MAX_SLAB;
+    size_t slab = n_max ? (workspace_bytes - ws.head) / slot_bytes : (size_t)SV_MAX_SLAB;
     slab = slab > (size_t)SV_MAX_SLAB ? (size_t)SV_MAX_SLAB : slab;
     // the offsets go to the head of the workspace; the copy has left the caller's array when the stream has drained
-    BPMF_HIP_CHECK(hipMemcpyAsync(d_workspace, offsets, (n_groups + 1) * sizeof(int64_t), hipMemcpyHostToDevice,
+    BPMF_HIP_CHECK(hipMemcpyAsync(ws.offsets, offsets, (n_groups + 1) * sizeof(int64_t), hipMemcpyHostToDevice,
                                   stream));
     BPMF_HIP_CHECK(hipStreamSynchronize(stream));
 
     SvCall call{};
     call.x = d_x;
-    call.offsets = (const long long*)d_workspace;
-    call.slots = (double*)((char*)d_workspace + head);
+    call.offsets = ws.offsets;
+    call.slots = ws.slots;
     call.slot = z.slot;
     call.o_v = z.o_v, call.o_a = z.o_a, call.o_b = z.o_b, call.o_sa = z.o_sa, call.o_sq = z.o_sq, call.o_d = z.o_d;
     call.o_e = z.o_e, call.o_col = z.o_col, call.o_small = z.o_small;

@@ -768,11 +768,11 @@ def multiband_spectra(data_dev, starts, n_samples, frequency_bands, *, sr, buffe
     if rows * B >= 2**31:
         raise ValueError(f"multiband_spectra: {rows} rows x {B} bands in one call; fewer than 2^31 values fit")
     n_active = int((~plan["skip"]).sum())
-    row_bytes = (4 + (1 + n_active) * n) * 8
+    least = int(_lib.lib().bpmf_multiband_workspace_bytes(64, n, n_active))
     workspace_bytes = int(workspace_bytes)
-    if workspace_bytes < 64 * row_bytes:
+    if workspace_bytes < least:
         raise ValueError(f"multiband_spectra: workspace_bytes = {workspace_bytes}; 64 rows of {n} samples and "
-                         f"{n_active} active bands take {64 * row_bytes}")
+                         f"{n_active} active bands take {least}")
     dev = data_dev.device
     with torch.cuda.device(dev):
         freq = torch.as_tensor(plan["freq"], device=dev)

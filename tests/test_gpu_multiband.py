@@ -190,10 +190,13 @@ def test_refusals_come_before_the_library(monkeypatch):
     import torch
     from seismic_bpmf_amd import _lib, workflow
 
-    def no_library():
-        raise AssertionError("the library was reached")
+    class SizesOnly:       # the workspace refusal asks the library's pure size function for a row's bytes; nothing else
+        bpmf_multiband_workspace_bytes = staticmethod(_lib.lib().bpmf_multiband_workspace_bytes)
 
-    monkeypatch.setattr(_lib, "lib", no_library)
+        def __getattr__(self, name):
+            raise AssertionError("the library was reached")
+
+    monkeypatch.setattr(_lib, "lib", SizesOnly)
     day = torch.zeros((2, 3, 500), dtype=torch.float32, device="cuda")
     starts = np.zeros((4,), np.int64)
     good = dict(data_dev=day, starts=starts, n_samples=400, frequency_bands=mc.OCTAVES, sr=SR, buffer_seconds=1.0)

@@ -835,6 +835,44 @@ int bpmf_multiband_spectrum_dev(const float *d_data, size_t S, size_t C, size_t 
                                 const uint8_t *skip, void *d_workspace, size_t workspace_bytes, bpmf_stream_t stream,
                                 double *d_out, uint8_t *d_valid);
 
+/* ------------------------------------------- FFT-method displacement spectra of a day's events --- */
+/*
+ * Spectrum.compute_spectrum and Spectrum.resample (BPMF/spectrum.py:507-599, :851-887; method "regular" of
+ * compute_moment_magnitude) for every window of a day in HBM in one call (fft_spectrum.hip).  Windows are addressed as
+ * bpmf_multiband_spectrum_dev addresses them; row (w, c) is x[j] = d_data[w % S, c, d_starts[w] + j], j < n_samples.
+ * In float64 throughout (the definition is seismic_bpmf_amd.postprocess.fft_spectrum_host), as a DFT pruned to the
+ * n_bins bins of d_bins:
+ *   X[b] = delta * sum_j x[j] d_taper[j] (T[(j k) mod n][0] + i T[(j k) mod n][1]),   k = d_bins[b],
+ * T = d_twiddles (n_samples, 2) = cos, -sin of 2 pi m / n_samples (postprocess.dft_twiddles); the sum runs in an order
+ * that depends on n_samples only, and the product with delta is one rounded multiply each on re and im.
+ *   n_targets == 0, multi_component == 0: d_out (n_windows, C, n_bins, 2) = re, im of X;
+ *   n_targets == 0, multi_component != 0: d_out (n_windows, n_bins) = sqrt(sum_c |X_c|^2), summed in component order;
+ *   n_targets > 0: with fp = |X| (or, multi_component, that root) d_out (n_windows, C, n_targets) or
+ *     (n_windows, n_targets) holds np.interp's value: fp[p] where d_flags[t] & 1 (the target is a bin's frequency),
+ *     ((fp[p + 1] - fp[p]) / d_span[t]) * d_dx[t] + fp[p] elsewhere, p = d_pair[t] an index INTO d_bins (whose next
+ *     entry is the next bin), and +0 where d_flags[t] & 2 (the target is at or beyond 0.99 f_max).
+ * A row that holds a NaN or an Inf gives NaN wherever it is not +0 by a flag.  A window that is not wholly inside
+ * [0, N) is not processed: its outputs are +0 and d_valid[w] = 0 (1 elsewhere).
+ *   d_data (S, C, N) f32; d_starts (n_windows) i64, clamped to +-2^40; d_taper (n_samples) f64; d_bins (n_bins) i32,
+ *   ascending, 0 .. n_samples / 2; d_pair i32, d_dx, d_span f64, d_flags u8 (n_targets), unused (may be null) without
+ *   targets; all on the device.  d_valid (n_windows) u8.  Every element of both outputs is written.
+ * Workspace: a row takes 16 n_bins + 1 bytes; the rows go through in slabs of a multiple of 64 that fit, so 64 rows'
+ * worth are the least.  A row gives the same bits in any slab and any batch.  bpmf_fft_spectrum_workspace_size returns
+ * what n_rows = n_windows * C rows take in one slab (n_rows rounded up to 64), or 0 for sizes that the call refuses.
+ * Asynchronous on `stream`.
+ * Returns -1 for a null pointer, S * C == 0, N == 0 or above 2^40, n_windows no multiple of S, n_samples outside
+ * 2 .. 16384, n_bins outside 1 .. n_samples / 2 + 1, n_targets above 1024, multi_component with C above 64, a delta that
+ * is not finite, n_windows * C * max(2 n_bins, n_targets) >= 2^31, or a workspace smaller than 64 rows.
+ * n_windows == 0 launches nothing and returns 0.
+ */
+size_t bpmf_fft_spectrum_workspace_size(size_t n_rows, size_t n_samples, size_t n_bins, size_t n_targets);
+int bpmf_fft_spectrum_dev(const float *d_data, size_t S, size_t C, size_t N, size_t n_windows,
+                          const long long *d_starts, size_t n_samples, const double *d_taper,
+                          const double *d_twiddles, double delta, const int *d_bins, size_t n_bins, const int *d_pair,
+                          const double *d_dx, const double *d_span, const unsigned char *d_flags, size_t n_targets,
+                          int multi_component, void *d_workspace, size_t workspace_bytes, bpmf_stream_t stream,
+                          double *d_out, unsigned char *d_valid);
+
 /* ------------------------------------------- events detected by several templates --- */
 /*
  * The loop of TemplateGroup.remove_multiples (BPMF/dataset.py:5214-5282) on a catalog that is ALREADY in the

@@ -102,6 +102,9 @@ SIGNATURES = {
     "bpmf_multiband_workspace_bytes": (_sz, [_sz, _sz, _sz]),
     "bpmf_multiband_spectrum_dev": (C.c_int, [_vp, _sz, _sz, _sz, _sz, _vp, _sz, _sz, _sz, _vp, _sz, _sz,
                                               C.POINTER(C.c_double), C.POINTER(C.c_uint8), _vp, _sz, _vp, _vp, _vp]),
+    "bpmf_fft_spectrum_workspace_size": (_sz, [_sz, _sz, _sz, _sz]),
+    "bpmf_fft_spectrum_dev": (C.c_int, [_vp, _sz, _sz, _sz, _sz, _vp, _sz, _vp, _vp, C.c_double, _vp, _sz, _vp, _vp,
+                                        _vp, _vp, _sz, C.c_int, _vp, _sz, _vp, _vp, _vp]),
     "bpmf_flag_multiples_workspace_bytes": (_sz, [_sz]),
     "bpmf_flag_multiples_dev": (C.c_int, [_vp, _vp, _vp, _sz, _vp, _sz, C.c_double, _vp, _sz, _vp, _vp]),
     "bpmf_extract_candidates_mad_dev": (C.c_int, [_vp, _vp, _vp, _sz, _sz, _sz, _sz, C.c_uint32, _vp,

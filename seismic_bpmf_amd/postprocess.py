@@ -7,6 +7,8 @@ These are small integer / NumPy routines in the reference too (Python loops in
 BPMF/similarity_search.py and BPMF/template_search.py); the heavy part of the post-CC step, the
 RMS sliding threshold of BPMF/libc.c:516-673, has a device version in threshold.py.
 """
+import functools
+
 import numpy as np
 
 
@@ -1721,3 +1723,142 @@ def spectral_snr_host(signal, noise, noise_valid=None):
     with np.errstate(divide="ignore", invalid="ignore"):
         snr[keep] = signal[keep] / noise[keep]
     return snr
+
+
+# ---- FFT-method displacement spectra (BPMF/spectrum.py: Spectrum.compute_spectrum :507-599, Spectrum.resample
+# ---- :851-887; method "regular" of compute_moment_magnitude) ----
+FFT_SPECTRUM_MIN_SAMPLES = 2
+FFT_SPECTRUM_MAX_SAMPLES = 16384
+FFT_SPECTRUM_MAX_TARGETS = 1024
+FFT_SPECTRUM_EXACT, FFT_SPECTRUM_OUTSIDE = 1, 2        # bits of the plan's `flags`
+
+
+def fft_spectrum_plan(n_samples, sr, frequencies=None, alpha=0.05, taper=None):
+    """What an FFT-method call works with, and its refusals.  Returns a dict: `taper` (n,) float64 =
+    scipy.signal.windows.tukey(n, alpha) (tukey_window, which equals it bit for bit for 0 <= alpha < 1), or the caller's
+    (n,) `taper`; `delta` = 1.0 / sr; `freq` = np.fft.rfftfreq(n, d=delta) (K = n // 2 + 1 bins); `bins` (K_b,) int32,
+    ascending: without `frequencies` every bin, with them the sorted unique j and j + 1 that np.interp uses for a
+    target -- j the last bin with freq[j] <= f, kept inside 0 .. K - 2.  With `frequencies` (F,) also `frequencies`
+    as float64; `pair` (F,) int32, the index of j in `bins` (that of j + 1 is one more); `dx` = f - freq[j] and `span`
+    = freq[j + 1] - freq[j], float64; `exact`: f == freq[j], or f < freq[0], where np.interp returns fp[j]; `outside`:
+    f >= 0.99 freq.max(), which the reference sets to 0; `flags` (F,) uint8 = exact | 2 outside.
+    Raises ValueError: n outside 2 .. 16384; sr not a positive number; more than 1024 targets, none, or one that is not
+    finite; alpha outside [0, 1); a `taper` that is not (n,)."""
+    n = int(n_samples)
+    if not FFT_SPECTRUM_MIN_SAMPLES <= n <= FFT_SPECTRUM_MAX_SAMPLES:
+        raise ValueError(f"fft_spectrum: windows of {FFT_SPECTRUM_MIN_SAMPLES} .. {FFT_SPECTRUM_MAX_SAMPLES} samples; "
+                         f"got {n}")
+    sr = float(sr)
+    if not (sr > 0 and np.isfinite(sr)):
+        raise ValueError(f"fft_spectrum: need sr > 0; got {sr}")
+    if taper is None:
+        if not 0 <= float(alpha) < 1:
+            raise ValueError(f"fft_spectrum: alpha must lie in [0, 1); got {alpha} (pass the window as taper=)")
+        window = tukey_window(n, float(alpha))
+    else:
+        window = np.array(taper, dtype=np.float64)
+        if window.shape != (n,):
+            raise ValueError(f"fft_spectrum: taper must be ({n},); got the shape {window.shape}")
+    delta = 1.0 / sr
+    freq = np.fft.rfftfreq(n, d=delta)
+    plan = {"taper": window, "delta": delta, "freq": freq}
+    if frequencies is None:
+        plan["bins"] = np.arange(len(freq), dtype=np.int32)
+        return plan
+    f = np.array(frequencies, dtype=np.float64)
+    if f.ndim != 1 or not 1 <= len(f) <= FFT_SPECTRUM_MAX_TARGETS or not np.isfinite(f).all():
+        raise ValueError(f"fft_spectrum: frequencies must be 1 .. {FFT_SPECTRUM_MAX_TARGETS} finite numbers in one "
+                         f"dimension; got the shape {f.shape}")
+    j = np.clip(np.searchsorted(freq, f, side="right") - 1, 0, len(freq) - 2)
+    bins = np.unique(np.concatenate([j, j + 1]))
+    plan.update(frequencies=f, bins=bins.astype(np.int32), pair=np.searchsorted(bins, j).astype(np.int32),
+                dx=f - freq[j], span=freq[j + 1] - freq[j], exact=(f == freq[j]) | (f < freq[0]),
+                outside=f >= 0.99 * freq.max())
+    plan["flags"] = (plan["exact"] * FFT_SPECTRUM_EXACT + plan["outside"] * FFT_SPECTRUM_OUTSIDE).astype(np.uint8)
+    return plan
+
+
+def _two_prod(a, b):
+    """a * b as the float64 product and what its rounding left out (Dekker's split; exact without an FMA)."""
+    p = a * b
+    ca, cb = 134217729.0 * a, 134217729.0 * b
+    ah, bh = ca - (ca - a), cb - (cb - b)
+    al, bl = a - ah, b - bh
+    return p, ((ah * bh - p) + ah * bl + al * bh) + al * bl
+
+
+@functools.lru_cache(maxsize=8)
+def _dft_twiddles(n):
+    # sin and cos of a = pi t / (4 n) <= pi / 4, t = 0 .. n, from the angle as a float64 and what that leaves out:
+    # q = t / (4 n) and pi each as a sum of two float64 (the remainder of the division exact), their product to
+    # first order in the small parts (what is dropped is below 2^-100), then sin(hi + lo) = sin(hi) + lo cos(hi) and
+    # cos(hi + lo) = cos(hi) - lo sin(hi): each value within 1.5 * 2^-53 with a libm good to one unit in the last place
+    t = np.arange(n + 1, dtype=np.float64)
+    d = 4.0 * n
+    q = t / d
+    p, e = _two_prod(q, np.full_like(q, d))
+    q_lo = ((t - p) - e) / d
+    pi_hi, pi_lo = 3.141592653589793, 1.2246467991473532e-16
+    hi, e = _two_prod(q, np.full_like(q, pi_hi))
+    lo = e + (pi_hi * q_lo + pi_lo * q)
+    s, c = np.sin(hi), np.cos(hi)
+    s, c = s + lo * c, c - lo * s
+    # 2 pi m / n = (pi / 4) (o + rem / n): the octant o and what is left of it, in integers
+    m = np.arange(n, dtype=np.int64)
+    o, rem = np.divmod(8 * m, n)
+    t = np.where(o % 2 == 0, rem, n - rem)
+    cos = np.choose(o, [c[t], s[t], -s[t], -c[t], -c[t], -s[t], s[t], c[t]])
+    sin = np.choose(o, [s[t], c[t], c[t], s[t], -s[t], -c[t], -c[t], -s[t]])
+    table = np.stack([cos, -sin], axis=1) + 0.0                     # (no -0)
+    table.setflags(write=False)
+    return table
+
+
+def dft_twiddles(n):
+    """(n, 2) float64: cos(2 pi m / n) and -sin(2 pi m / n), m = 0 .. n - 1, every entry within 2^-52 of the true value
+    for every n <= 16384: the argument is reduced to an octant in integers, and the angle left, at most pi / 4, goes
+    into sin and cos as a float64 plus the remainder that the float64 leaves out.  (Read-only; cached.)"""
+    n = int(n)
+    if not 1 <= n <= FFT_SPECTRUM_MAX_SAMPLES:
+        raise ValueError(f"dft_twiddles: 1 .. {FFT_SPECTRUM_MAX_SAMPLES} entries; got {n}")
+    return _dft_twiddles(n)
+
+
+def fft_spectrum_host(windows, *, sr, frequencies=None, alpha=0.05, taper=None, multi_component=False):
+    """The definition of the FFT-method spectra: Spectrum.compute_spectrum (BPMF/spectrum.py:507-599) and
+    Spectrum.resample (:851-887) on plain arrays, the reference's statements in the reference's order.  `windows`
+    (E, S, C, n), float32 or float64 as given, one trace each.  Per trace np.fft.rfft(trace * taper) * delta, taper =
+    tukey(n, alpha) or the caller's array, delta = 1 / sr.  Without `frequencies`: the complex spectrum (E, S, C, K),
+    K = n // 2 + 1, or with `multi_component` sqrt(sum over the components |X_c|^2), summed in component order from 0,
+    (E, S, K).  With `frequencies` (F,): np.interp(frequencies, freq, |spectrum|) with the targets at or beyond
+    0.99 freq.max() set to 0: (E, S, C, F), or (E, S, F) float64.
+    A trace that holds a NaN or an Inf is NaN at every bin (re and im) and at every target that is not set to 0; with
+    `multi_component` so is its station.  This is the definition's own answer, whatever an FFT makes of such a trace.
+    Returns (spectra, freq): freq = `frequencies` as float64, or np.fft.rfftfreq(n, d=delta).  Refusals:
+    fft_spectrum_plan."""
+    x = np.asarray(windows)
+    if x.ndim != 4:
+        raise ValueError("fft_spectrum_host: windows must be (E, S, C, n)")
+    n = x.shape[-1]
+    plan = fft_spectrum_plan(n, sr, frequencies, alpha, taper)
+    spectrum = np.fft.rfft(x * plan["taper"]) * plan["delta"]
+    bad = ~np.isfinite(x).all(axis=-1)
+    spectrum[bad] = complex(np.nan, np.nan)
+    if multi_component:
+        total = np.zeros(x.shape[:2] + (spectrum.shape[-1],), dtype=np.float64)
+        for c in range(x.shape[2]):
+            total += np.abs(spectrum[:, :, c]) ** 2
+        spectrum = np.sqrt(total)
+    if frequencies is None:
+        return spectrum, plan["freq"]
+    modulus = np.abs(spectrum)
+    out = np.empty(modulus.shape[:-1] + (len(plan["frequencies"]),), dtype=np.float64)
+    for index in np.ndindex(out.shape[:-1]):
+        out[index] = np.interp(plan["frequencies"], plan["freq"], modulus[index])
+    out[..., plan["outside"]] = 0.0
+    return out, plan["frequencies"]
+
+
+def fft_windows_host(data, starts, n_samples):
+    """The windows an FFT-method call works on, and `valid`: multiband_windows_host, which fits as it is."""
+    return multiband_windows_host(data, starts, n_samples)

@@ -744,7 +744,7 @@ def multiband_spectra(data_dev, starts, n_samples, frequency_bands, *, sr, buffe
     int(buffer_seconds sr) == 0 or n_samples <= twice that (the reference's data[buf:-buf] is empty there and it
     returns zeros); B outside 1 .. 64; corners outside 1 .. 8; a band with lo <= 0 or lo >= hi; a band with
     (1 - 1e-6) sr / 2 < hi < sr / 2 (obspy silently turns it into a high-pass); rows x B >= 2^31; a workspace too small
-    for 64 rows.  Out of scope: the FFT method, response removal, propagation corrections, averaging and model fits."""
+    for 64 rows.  Out of scope: response removal, propagation corrections, averaging and model fits."""
     import ctypes as C
     import torch
     from . import _lib
@@ -807,7 +807,8 @@ def multiband_snr(signal, noise, noise_valid=None):
     shape (..., B), on their device: 0 where signal and noise are both 0, |signal| / |noise| elsewhere (inf included),
     and 0 where the noise spectrum is missing -- `noise_valid` (...) bool, the `valid` of the noise windows, broadcast
     over the bands (and over the components).  A few elementwise operations on small tensors; the definition is
-    postprocess.spectral_snr_host, which it equals exactly."""
+    postprocess.spectral_snr_host, which it equals exactly.  workflow.spectral_snr is this function under the name
+    that fits two results of fft_spectra, (..., F), as well."""
     import torch
     if not isinstance(signal, torch.Tensor) or not isinstance(noise, torch.Tensor) or signal.shape != noise.shape:
         raise ValueError("multiband_snr: signal and noise must be tensors of equal shape (..., B)")
@@ -817,6 +818,109 @@ def multiband_snr(signal, noise, noise_valid=None):
         nv = torch.as_tensor(noise_valid, dtype=torch.bool, device=s.device)
         keep = keep & nv.reshape(tuple(nv.shape) + (1,) * (s.dim() - nv.dim()))
     return torch.where(keep, s / z, torch.zeros_like(s))
+
+
+spectral_snr = multiband_snr                # the same ratio on two results of fft_spectra
+
+
+FFT_SPECTRUM_WORKSPACE_BYTES = 1 << 30     # fft_spectra: the workspace it asks for at most (and at least 64 rows)
+
+
+def target_frequencies(freq_min, freq_max, num_points):
+    """Spectrum.set_target_frequencies (BPMF/spectrum.py:920-940): np.logspace(log10(freq_min), log10(freq_max),
+    num_points), the `frequencies` of fft_spectra."""
+    return np.logspace(np.log10(freq_min), np.log10(freq_max), num_points)
+
+
+def fft_spectra(data_dev, starts, n_samples, *, sr, frequencies=None, alpha=0.05, taper=None, multi_component=False,
+                workspace_bytes=FFT_SPECTRUM_WORKSPACE_BYTES):
+    """Spectrum.compute_spectrum and Spectrum.resample (BPMF/spectrum.py:507-599, :851-887; method "regular", the
+    default of compute_moment_magnitude) for the windows of E events, cut from the day in HBM, in one call
+    (bpmf_fft_spectrum_dev, csrc/fft_spectrum.hip): per window the Tukey taper of `alpha` (or the caller's (n,) `taper`)
+    and the Fourier transform times 1 / sr; with `frequencies` the modulus is interpolated linearly onto them as
+    np.interp does, and a target at or beyond 0.99 of the last bin's frequency gives 0.  Only the bins next to a
+    target are computed: a DFT pruned to them, a float64 matrix product per row with twiddles from an exact table
+    (postprocess.dft_twiddles), so n_samples need not be a power of two and no whole spectrum is stored.
+
+    `data_dev`: the (S, C, N) day as a tensor on the GPU, taken as float32, in the units the spectra are wanted in (the
+    instrument response is the caller's); `starts` (E,) or (E, S) int64 window starts in samples as in picker_batch;
+    `sr` in Hz; `frequencies` (F,) in Hz (target_frequencies), F <= 1024.  The noise, P and S windows of the
+    reference's extract_windows are three calls, or one on concatenated starts.
+    Returns (spectra, freq, valid) on the day's device and the current stream.  With `frequencies`: `spectra`
+    (E, S, C, F) float64, or (E, S, F) with `multi_component` (per bin the root of the sum over the components of
+    |X_c|^2, in component order, then interpolated); `freq` (F,) float64 = `frequencies`.  Without: the complex128
+    spectrum (E, S, C, n // 2 + 1), or that root (E, S, n // 2 + 1) float64; `freq` = np.fft.rfftfreq(n, 1 / sr).
+    `valid` (E, S) bool.  The definition is postprocess.fft_spectrum_host of postprocess.fft_windows_host; every value
+    lies within sqrt(2) B / sr + 8 * 2^-53 |value| of it, B = (n + 16) 2^-53 sum_j |x_j taper_j| of the row (of the
+    station: the root of its rows' summed B^2), and a window that holds a NaN or an Inf is NaN wherever it is not 0 by the rule
+    above.  A window gives the same bits in any batch and with any `workspace_bytes` (the rows go through in slabs of a
+    multiple of 64 that fit it).  workflow.spectral_snr is compute_signal_to_noise_ratio on two results.
+
+    DEPARTURE: a window that is not wholly inside the day gives zeros and valid = False; the reference would transform
+    the shorter trace it managed to read.
+
+    Refusals (ValueError, before any device call): data_dev not a GPU tensor or not (S, C, N); n_samples outside
+    2 .. 16384; sr not positive; alpha outside [0, 1); a taper that is not (n,); no, more than 1024 or non-finite
+    frequencies; multi_component with more than 64 components; rows x max(2 bins, F) >= 2^31; a workspace too small for
+    64 rows.  Out of scope: response removal, float64 days, a `spectrum_func` callable, propagation corrections,
+    averaging and model fits, `integrate` / `differentiate`."""
+    import ctypes as C
+    import torch
+    from . import _lib
+    if not isinstance(data_dev, torch.Tensor) or not data_dev.is_cuda:
+        raise ValueError("fft_spectra: data_dev must be a tensor on the GPU (there is no CPU path; the definition on "
+                         "the host is postprocess.fft_spectrum_host of postprocess.fft_windows_host)")
+    if data_dev.dim() != 3:
+        raise ValueError("fft_spectra: data_dev must be (S, C, N)")
+    S, Cc, N = (int(v) for v in data_dev.shape)
+    n = int(n_samples)
+    plan = pp.fft_spectrum_plan(n, sr, frequencies, alpha, taper)
+    if isinstance(starts, torch.Tensor):
+        starts = starts.detach().cpu().numpy()
+    st = pp.picker_starts(starts, S)
+    E, K_b = len(st), len(plan["bins"])
+    F = 0 if frequencies is None else len(plan["frequencies"])
+    if S * Cc == 0 or N == 0:
+        raise ValueError("fft_spectra: the data are empty")
+    multi = bool(multi_component)
+    if multi and Cc > 64:
+        raise ValueError(f"fft_spectra: multi_component takes at most 64 components; the day has {Cc}")
+    rows = st.size * Cc
+    if rows * max(2 * K_b, F) >= 2**31:
+        raise ValueError(f"fft_spectra: {rows} rows x {max(2 * K_b, F)} values in one call; fewer than 2^31 values fit")
+    least = int(_lib.lib().bpmf_fft_spectrum_workspace_size(64, n, K_b, F))
+    workspace_bytes = int(workspace_bytes)
+    if workspace_bytes < least:
+        raise ValueError(f"fft_spectra: workspace_bytes = {workspace_bytes}; 64 rows of {n} samples and {K_b} bins "
+                         f"take {least}")
+    dev = data_dev.device
+    with torch.cuda.device(dev):
+        freq = torch.as_tensor(plan["frequencies"] if F else plan["freq"], device=dev)
+        lead = (E, S) if multi else (E, S, Cc)
+        if F:
+            spectra = torch.empty(lead + (F,), dtype=torch.float64, device=dev)
+        else:
+            spectra = torch.empty(lead + (K_b,), dtype=torch.float64 if multi else torch.complex128, device=dev)
+        valid = torch.empty((E, S), dtype=torch.uint8, device=dev)
+        if E:
+            lib = _lib.lib()
+            x = data_dev.to(dtype=torch.float32).contiguous()
+            up = {k: torch.as_tensor(np.ascontiguousarray(v), device=dev) for k, v in (
+                ("starts", st.reshape(-1)), ("taper", plan["taper"]), ("twiddles", np.array(pp.dft_twiddles(n))),
+                ("bins", plan["bins"]))}
+            if F:
+                up.update({k: torch.as_tensor(np.ascontiguousarray(plan[k]), device=dev)
+                           for k in ("pair", "dx", "span", "flags")})
+            ptr = {k: C.c_void_p(v.data_ptr()) for k, v in up.items()}
+            n_bytes = min(workspace_bytes, int(lib.bpmf_fft_spectrum_workspace_size(rows, n, K_b, F)))
+            ws = torch.empty((n_bytes,), dtype=torch.uint8, device=dev)
+            rc = lib.bpmf_fft_spectrum_dev(
+                C.c_void_p(x.data_ptr()), S, Cc, N, st.size, ptr["starts"], n, ptr["taper"], ptr["twiddles"],
+                plan["delta"], ptr["bins"], K_b, ptr.get("pair"), ptr.get("dx"), ptr.get("span"), ptr.get("flags"), F,
+                int(multi), C.c_void_p(ws.data_ptr()), n_bytes, C.c_void_p(torch.cuda.current_stream(dev).cuda_stream),
+                C.c_void_p(spectra.data_ptr()), C.c_void_p(valid.data_ptr()))
+            _lib.check(rc, "bpmf_fft_spectrum_dev")
+        return spectra, freq, valid.to(torch.bool)
 
 
 def _peak_amplitude_window(sr, offset_win_peak_amp_sec, duration_win_peak_amp_sec):

@@ -15,8 +15,9 @@ from ._lib import (BpmfHipError, device_count, device_info, device_memory_held, 
                    release_device_memory, set_option, get_option, compat_profile)
 from .beampower import BeamformerGPU, beamform  # noqa: F401
 from .matched_filter import MatchedFilterGPU, accept_cpu_arch, matched_filter, matched_filter_full  # noqa: F401
-from .workflow import (bandpass_filter, fft_spectra, find_picks, multiband_snr, multiband_spectra,  # noqa: F401
-                       normalize_batch, pick_events, picker_batch, spectral_snr, svdwf_stack, target_frequencies,
-                       templates_from_events)
+from .workflow import (approximate_moment_magnitudes, bandpass_filter, differentiate_spectra,  # noqa: F401
+                       fft_spectra, find_picks, integrate_spectra, multiband_snr, multiband_spectra,
+                       network_average_spectra, normalize_batch, pick_events, picker_batch, source_spectra,
+                       spectral_snr, svdwf_stack, target_frequencies, templates_from_events)
 
 __version__ = "0.1.0"

@@ -105,6 +105,9 @@ SIGNATURES = {
     "bpmf_fft_spectrum_workspace_size": (_sz, [_sz, _sz, _sz, _sz]),
     "bpmf_fft_spectrum_dev": (C.c_int, [_vp, _sz, _sz, _sz, _sz, _vp, _sz, _vp, _vp, C.c_double, _vp, _sz, _vp, _vp,
                                         _vp, _vp, _sz, C.c_int, _vp, _sz, _vp, _vp, _vp]),
+    "bpmf_source_spectra_dev": (C.c_int, [_vp] * 10 + [_sz, _sz, _sz, _sz, C.c_uint, C.c_double, C.c_double, C.c_double,
+                                          C.c_double, C.c_int, C.c_int, C.c_int, C.c_int, _sz, C.c_double, C.c_double,
+                                          C.c_int, _vp] + [_vp] * 12),
     "bpmf_flag_multiples_workspace_bytes": (_sz, [_sz]),
     "bpmf_flag_multiples_dev": (C.c_int, [_vp, _vp, _vp, _sz, _vp, _sz, C.c_double, _vp, _sz, _vp, _vp]),
     "bpmf_extract_candidates_mad_dev": (C.c_int, [_vp, _vp, _vp, _sz, _sz, _sz, _sz, C.c_uint32, _vp,

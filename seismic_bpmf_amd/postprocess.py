@@ -1862,3 +1862,259 @@ def fft_spectrum_host(windows, *, sr, frequencies=None, alpha=0.05, taper=None, 
 def fft_windows_host(data, starts, n_samples):
     """The windows an FFT-method call works on, and `valid`: multiband_windows_host, which fits as it is."""
     return multiband_windows_host(data, starts, n_samples)
+
+
+# ---- Propagation corrections, network-average spectra and the approximate moment magnitude (BPMF/spectrum.py:
+# ---- set_Q_model :37-63, compute_correction_factor :97-198, correct_geometrical_spreading :200-227,
+# ---- correct_attenuation :229-256 with update_attenuation_factor :78-95, compute_network_average_spectrum :258-386,
+# ---- _snr_based_weights :1290-1338, approximate_moment_magnitude :1341-1496) ----
+SOURCE_SPECTRA_MAX_CHANNELS = 256          # S * C of one event
+SOURCE_SPECTRA_MAX_FREQUENCIES = 1024      # as fft_spectra
+SOURCE_SPECTRA_MAX_AVERAGING_BANDS = 8
+RADIATION_P, RADIATION_S = np.sqrt(4.0 / 15.0), np.sqrt(2.0 / 5.0)
+MEDIUM_KEYS = ("rho_source_kgm3", "rho_receiver_kgm3", "vp_source_ms", "vp_receiver_ms", "vs_source_ms",
+               "vs_receiver_ms", "Q_1HZ", "attenuation_n")
+
+
+def geometry_constants(medium, radiation_p=RADIATION_P, radiation_s=RADIATION_S):
+    """(c_p, c_s): 4 pi sqrt(rho_receiver) sqrt(rho_source) sqrt(v_receiver) v_source^2.5 of compute_correction_factor,
+    multiplied in the reference's order, for P and S; the geometrical factor of a station at `dist` km is
+    c * (1000 * dist) / radiation."""
+    def constant(v_source, v_receiver):
+        return (4.0 * np.pi * np.sqrt(medium["rho_receiver_kgm3"]) * np.sqrt(medium["rho_source_kgm3"])
+                * np.sqrt(v_receiver) * v_source ** (5.0 / 2.0))
+    return (constant(medium["vp_source_ms"], medium["vp_receiver_ms"]),
+            constant(medium["vs_source_ms"], medium["vs_receiver_ms"]))
+
+
+def attenuation_plan(frequencies, medium, q_phase_prefactor=None, attenuation="reference"):
+    """Which travel time and which Q row a phase's attenuation factor exp(((pi tt) f) / Q_row) takes: returns
+    (tt_phase, q_rows) with tt_phase = ("s", "s") or ("p", "s") for (P, S) and q_rows (2, F).  Q(f) = Q_1HZ f^n (the
+    reference's interp1d of it at its own frequencies is the identity).  attenuation="reference" is what
+    correct_attenuation does through update_attenuation_factor: BOTH phases take the S travel time, the P factor
+    divides by Q * prefactor["s"] and the S factor by Q * prefactor["p"].  attenuation="physical" pairs tt_p with
+    Q * prefactor["p"] and tt_s with Q * prefactor["s"]."""
+    if attenuation not in ("reference", "physical"):
+        raise ValueError(f"attenuation must be 'reference' or 'physical'; got {attenuation!r}")
+    f = np.asarray(frequencies, dtype=np.float64)
+    if f.ndim != 1 or not 1 <= len(f) <= SOURCE_SPECTRA_MAX_FREQUENCIES or not np.isfinite(f).all():
+        raise ValueError(f"frequencies must be 1 .. {SOURCE_SPECTRA_MAX_FREQUENCIES} finite numbers in one dimension")
+    prefactor = dict(q_phase_prefactor or {})
+    Q = medium["Q_1HZ"] * np.power(f, medium["attenuation_n"])
+    q_p, q_s = Q * prefactor.get("p", 1.0), Q * prefactor.get("s", 1.0)
+    if attenuation == "reference":
+        return ("s", "s"), np.stack([q_s, q_p])
+    return ("p", "s"), np.stack([q_p, q_s])
+
+
+def propagation_factors_host(frequencies, source_receiver_dist_km, tt_p_sec, tt_s_sec, medium, q_phase_prefactor=None,
+                             attenuation="reference", radiation_p=RADIATION_P, radiation_s=RADIATION_S):
+    """The factors that correct_geometrical_spreading and correct_attenuation multiply a spectrum by, in that order,
+    each with its own rounding: `geometry` (E, S, 2) and `attenuation` (E, S, 2, F), phase 0 = P, 1 = S.
+    geometry = c * (1000 * dist) / radiation (geometry_constants); attenuation = exp(((pi * tt) * f) / Q_row)
+    (attenuation_plan, where the reference's pairing of travel times and Q rows is stated)."""
+    dist = np.asarray(source_receiver_dist_km, dtype=np.float64)
+    tt = {"p": np.asarray(tt_p_sec, dtype=np.float64), "s": np.asarray(tt_s_sec, dtype=np.float64)}
+    if dist.ndim != 2 or tt["p"].shape != dist.shape or tt["s"].shape != dist.shape:
+        raise ValueError("propagation_factors_host: distances and travel times must be (E, S) and equal in shape")
+    f = np.asarray(frequencies, dtype=np.float64)
+    which, q_rows = attenuation_plan(f, medium, q_phase_prefactor, attenuation)
+    c = geometry_constants(medium)
+    radiation = (radiation_p, radiation_s)
+    geometry = np.stack([c[k] * (1000.0 * dist) / radiation[k] for k in range(2)], axis=-1)
+    with np.errstate(all="ignore"):
+        att = np.stack([np.exp(np.pi * tt[which[k]][..., None] * f / q_rows[k]) for k in range(2)], axis=2)
+    return geometry, att
+
+
+def _source_channels(spectra, n_stations):
+    """(E, S, F) or (E, S, C, F) -> ((E, S * C, F) view, C)."""
+    x = np.asarray(spectra, dtype=np.float64)
+    if x.ndim not in (3, 4) or x.shape[1] != n_stations:
+        raise ValueError(f"spectra must be (E, S, F) or (E, S, C, F) with S = {n_stations}; got {x.shape}")
+    C = 1 if x.ndim == 3 else x.shape[2]
+    return x.reshape(x.shape[0], n_stations * C, x.shape[-1]), C
+
+
+def network_average_spectrum_host(spectra, snr, present, dist_err_pct, *, snr_threshold, average_log=True,
+                                  min_num_valid_channels_per_freq_bin=0, max_relative_distance_err_pct=25.0,
+                                  reduce="mean"):
+    """Spectrum.compute_network_average_spectrum (:258-386) for E events at once, without np.ma: `spectra`, `snr`
+    (E, S, F) or (E, S, C, F) float64 (a channel is (s, c), in that order), `present` (E, S) bool (False: the station
+    has no spectrum, its window was not valid), `dist_err_pct` (E, S) = 100 sqrt(hmax^2 + vmax^2) / dist.
+
+    A station is `used` if present and not dist_err_pct > max.  Per bin over the used channels: masked where
+    snr < snr_threshold (a NaN SNR is not masked); num_valid counts the unmasked, BEFORE the two rules that follow:
+    a bin with num_valid < min_num is masked in every channel, and with average_log np.ma.log10 also masks values
+    <= 0 and every value whose log10 is not finite (NaN and inf: np.ma masks a non-finite result of a domained
+    function, so a NaN reaches an average only with average_log=False).  Mean: the channels' values (0 where masked) added in channel order, times 1.0, divided by the
+    count; median: NaN if an unmasked value is NaN, else the middle value or the half-sum of the two middle values;
+    with average_log the average is exp(that * log(10)) of the log10 values.  std is np.ma.std, ddof = 0, about the
+    MEAN in both cases: sqrt(sum((v - mean)^2) / count).  np.ma's division masks a quotient that is not finite: so a
+    mean that is NaN or infinite is masked (a median is not: it can be an unmasked NaN), and std is then 0, unmasked
+    (np.ma.var sums deviations that the masked mean has masked, and sets its own mask from the counts alone).  A bin without an unmasked channel is masked; an event without a used station is masked
+    everywhere.  Returns a dict: `average`, `std` (E, F) float64, NaN where `mask`
+    (E, F) bool; `num_valid` (E, F) int32; `used` (E, S) bool."""
+    if reduce not in ("mean", "median"):
+        raise ValueError(f"reduce must be 'mean' or 'median'; got {reduce!r}")
+    present = np.asarray(present, dtype=bool)
+    if present.ndim != 2:
+        raise ValueError("present must be (E, S)")
+    E, S = present.shape
+    x, C = _source_channels(spectra, S)
+    r, C2 = _source_channels(snr, S)
+    err = np.asarray(dist_err_pct, dtype=np.float64)
+    if r.shape != x.shape or err.shape != (E, S) or x.shape[0] != E:
+        raise ValueError("spectra and snr must be equal in shape, dist_err_pct (E, S) as present")
+    F = x.shape[-1]
+    used = present & ~(err > max_relative_distance_err_pct)
+    average, std = np.full((E, F), np.nan), np.full((E, F), np.nan)
+    mask, num_valid = np.ones((E, F), dtype=bool), np.zeros((E, F), dtype=np.int32)
+    log10 = np.log(10.0)
+    with np.errstate(all="ignore"):
+        for e in range(E):
+            ch = np.flatnonzero(np.repeat(used[e], C))
+            if len(ch) == 0:
+                continue
+            v, m = x[e, ch], r[e, ch] < snr_threshold
+            num_valid[e] = (~m).sum(axis=0)
+            m = m | (num_valid[e] < min_num_valid_channels_per_freq_bin)[None, :]
+            if average_log:
+                m = m | (v <= 0.0) | ~np.isfinite(np.log10(v))
+                v = np.log10(v)
+            count = (~m).sum(axis=0)
+            filled = np.where(m, 0.0, v)
+            mean = np.add.reduce(filled, axis=0) * 1.0 / count
+            if reduce == "mean":
+                centre = mean
+            else:
+                ordered = np.sort(np.where(m, np.inf, v), axis=0)           # NaN last, masked (inf) before it
+                hi = np.minimum(count // 2, len(ch) - 1)
+                lo = np.where(count % 2 == 1, hi, np.maximum(hi - 1, 0))
+                centre = (np.take_along_axis(ordered, lo[None], 0)[0] + np.take_along_axis(ordered, hi[None], 0)[0]) / 2.0
+                centre[(np.isnan(v) & ~m).any(axis=0)] = np.nan
+            d = np.where(m, 0.0, v - mean)
+            variance = np.add.reduce(d * d, axis=0) / count
+            value = np.exp(centre * log10) if average_log else centre
+            mask[e] = (count == 0) | (~np.isfinite(mean) if reduce == "mean" else False)
+            average[e] = np.where(mask[e], np.nan, value)
+            std[e] = np.where((count == 0) | ~np.isfinite(variance), np.nan, np.sqrt(variance))
+            std[e][(count > 0) & ~np.isfinite(mean)] = 0.0
+    return {"average": average, "mask": mask, "std": std, "num_valid": num_valid, "used": used}
+
+
+def snr_based_weights_host(snr, snr_threshold, weight_max=3.0, max_num_bad_measurements=6):
+    """_snr_based_weights (:1290-1338) on a float32 vector: min(snr, 1.001 threshold, weight_max), all in float32;
+    with at least max_num_bad_measurements values >= threshold every value < threshold gets 0, otherwise all but the
+    max_num_bad_measurements largest get 0.  Equal values are ordered by index (the reference's np.argsort leaves
+    their order open; in every tested input only zeros tie, whose weight is 0 either way)."""
+    snr = np.asarray(snr, dtype=np.float32)
+    thr = np.float32(snr_threshold)
+    weights = np.minimum(np.minimum(snr, np.float32(1.001 * snr_threshold)), np.float32(weight_max))
+    if np.sum(snr >= thr) >= max_num_bad_measurements:
+        weights[snr < thr] = 0.0
+    else:
+        order = np.argsort(snr, kind="stable")
+        weights[order[:len(order) - max_num_bad_measurements if len(order) > max_num_bad_measurements else 0]] = 0.0
+    return weights
+
+
+def _skipna_sum(values):
+    """pandas' Series.sum: NaN counts as 0, then NumPy's sum of the contiguous row."""
+    return np.where(np.isnan(values), 0.0, values).sum()
+
+
+def approximate_moment_magnitude_host(corrected, snr, present, frequencies, epicentral_dist_km, *, snr_threshold=10.0,
+                                      num_averaging_bands=1, low_snr_freq_min_hz=2.0,
+                                      magnitude_log_moment_scaling=2.0 / 3.0, weight_max=3.0,
+                                      max_num_bad_measurements=6):
+    """approximate_moment_magnitude (:1341-1496) of one phase for E events, dtypes included.  `corrected`, `snr`
+    (E, S, F) or (E, S, C, F) float64; `present` (E, S) bool; `frequencies` (F,); `epicentral_dist_km` (E, S).  The
+    reference indexes the distances by spectrum id, so its code runs only with multi_component_spectrum=True; here a
+    channel (s, c) takes the distance of its station s.
+
+    Per channel of a present station: the valid bands are those with snr > snr_threshold (strict); with k > 0 of them
+    the measurement is the value at the lowest one, or the median of the lowest min(k, num_averaging_bands) (in the
+    order of `frequencies`, which must ascend), and its SNR is snr_threshold; with none, over the bands with
+    frequency > low_snr_freq_min_hz, NaN terms counting as 0: 10 ** (sum(snr log10(value)) / sum(snr)) and
+    sum(snr snr) / sum(snr), the sum replaced by 1.0 where it is 0 (so an empty selection gives 1 and 0, where the
+    reference's unused argmax would raise).  The SNR is rounded to float32 and set to 0 where the measurement is 0.
+    Weights: snr_based_weights_host, times (rounded to float32 from the float64 product) the reciprocal of the
+    epicentral distance clipped to the 25th and 75th np.percentile (linear) of ALL S stations of the event.
+    log10_M0 = sum(log10(measurement) * weight over weight > 0) in float64 / the float32 sum of the weights, both in
+    NumPy's order over the present channels; Mw* = scaling * (log10_M0 - 9.1).
+    Returns a dict: `Mw_star`, `log10_M0` (E,) float64 (NaN without a positive weight); `measured_disp` (E, S * C)
+    float64 (NaN for an absent station); `weights`, `measurement_snr` (E, S * C) float32 (0 for an absent station)."""
+    present = np.asarray(present, dtype=bool)
+    E, S = present.shape
+    x, C = _source_channels(corrected, S)
+    r, _ = _source_channels(snr, S)
+    f = np.asarray(frequencies, dtype=np.float64)
+    epi = np.asarray(epicentral_dist_km, dtype=np.float64)
+    nab = int(num_averaging_bands)
+    if r.shape != x.shape or f.shape != (x.shape[-1],) or epi.shape != (E, S):
+        raise ValueError("corrected and snr must be equal in shape, frequencies (F,), epicentral_dist_km (E, S)")
+    if not 1 <= nab <= SOURCE_SPECTRA_MAX_AVERAGING_BANDS:
+        raise ValueError(f"num_averaging_bands must be 1 .. {SOURCE_SPECTRA_MAX_AVERAGING_BANDS}; got {nab}")
+    if np.any(np.diff(f) <= 0):
+        raise ValueError("frequencies must ascend")
+    NC = S * C
+    high = f > low_snr_freq_min_hz
+    measured = np.full((E, NC), np.nan)
+    msnr = np.zeros((E, NC), dtype=np.float32)
+    weights = np.zeros((E, NC), dtype=np.float32)
+    log10_m0 = np.full(E, np.nan)
+    with np.errstate(all="ignore"):
+        for e in range(E):
+            ch = np.flatnonzero(np.repeat(present[e], C))
+            if len(ch) == 0:
+                continue
+            disp, m32 = np.zeros(len(ch)), np.zeros(len(ch), dtype=np.float32)
+            for j, c in enumerate(ch):
+                valid = np.flatnonzero(r[e, c] > snr_threshold)
+                if len(valid):
+                    chosen = x[e, c, valid[:min(len(valid), nab)]]
+                    disp[j] = np.median(chosen) if len(chosen) > 1 else chosen[0]
+                    m32[j] = snr_threshold
+                else:
+                    w_, p_ = r[e, c, high], x[e, c, high]
+                    total = _skipna_sum(w_)
+                    total = 1.0 if total == 0.0 else total
+                    disp[j] = 10.0 ** (_skipna_sum(w_ * np.log10(p_)) / total)
+                    m32[j] = _skipna_sum(w_ * w_) / total
+            m32[disp == 0.0] = 0.0
+            w = snr_based_weights_host(m32, snr_threshold, weight_max, max_num_bad_measurements)
+            wd = 1.0 / np.clip(epi[e], a_min=np.percentile(epi[e], 25.0), a_max=np.percentile(epi[e], 75.0))
+            w *= np.repeat(wd, C)[ch]
+            peaks = np.zeros(len(ch))
+            peaks[w > 0.0] = np.log10(disp[w > 0.0]) * w[w > 0.0]
+            log10_m0[e] = peaks.sum() / w.sum()
+            measured[e, ch], msnr[e, ch], weights[e, ch] = disp, m32, w
+    return {"Mw_star": magnitude_log_moment_scaling * (log10_m0 - 9.1), "log10_M0": log10_m0, "measured_disp": measured,
+            "weights": weights, "measurement_snr": msnr}
+
+
+def source_spectra_host(signal, noise, present, noise_present, dist_km, tt_sec, location_err_km, frequencies, q_row,
+                        geometry_constant, radiation, **average_options):
+    """Stages 1-3 of one phase as the device call chains them: spectral_snr_host, the two corrections (the spectrum
+    times the geometrical factor, rounded, times the attenuation factor) and network_average_spectrum_host with
+    dist_err_pct = 100 * (location_err / dist).  A channel of an absent station has corrected = snr = 0.  `tt_sec` and
+    `q_row` are the travel time and the (F,) Q row that attenuation_plan names for the phase.  Returns the dict of
+    network_average_spectrum_host with `corrected` and `snr` (shaped as `signal`) added."""
+    signal = np.asarray(signal, dtype=np.float64)
+    present = np.asarray(present, dtype=bool)
+    dist, tt = np.asarray(dist_km, dtype=np.float64), np.asarray(tt_sec, dtype=np.float64)
+    f, q = np.asarray(frequencies, dtype=np.float64), np.asarray(q_row, dtype=np.float64)
+    wide = (slice(None), slice(None)) + (None,) * (signal.ndim - 2)
+    snr = spectral_snr_host(signal, noise, noise_present)
+    with np.errstate(all="ignore"):
+        geometry = geometry_constant * (1000.0 * dist) / radiation
+        att = np.exp(np.pi * tt[..., None] * f / q)
+        corrected = signal * geometry[wide]
+        corrected = corrected * (att if signal.ndim == 3 else att[:, :, None, :])
+        err_pct = 100.0 * (np.asarray(location_err_km, dtype=np.float64)[:, None] / dist)
+    corrected[~present] = 0.0
+    snr[~present] = 0.0
+    out = network_average_spectrum_host(corrected, snr, present, err_pct, **average_options)
+    out.update(corrected=corrected, snr=snr)
+    return out

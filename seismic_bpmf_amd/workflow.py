@@ -744,7 +744,9 @@ def multiband_spectra(data_dev, starts, n_samples, frequency_bands, *, sr, buffe
     int(buffer_seconds sr) == 0 or n_samples <= twice that (the reference's data[buf:-buf] is empty there and it
     returns zeros); B outside 1 .. 64; corners outside 1 .. 8; a band with lo <= 0 or lo >= hi; a band with
     (1 - 1e-6) sr / 2 < hi < sr / 2 (obspy silently turns it into a high-pass); rows x B >= 2^31; a workspace too small
-    for 64 rows.  Out of scope: response removal, propagation corrections, averaging and model fits."""
+    for 64 rows.  Propagation corrections, the network average and Mw* follow in network_average_spectra and
+    approximate_moment_magnitudes (source_spectra runs both).  Out of scope: response removal, the `resample` onto
+    other target frequencies, and the model fit (fit_average_spectrum: see network_average_spectra)."""
     import ctypes as C
     import torch
     from . import _lib
@@ -862,8 +864,10 @@ def fft_spectra(data_dev, starts, n_samples, *, sr, frequencies=None, alpha=0.05
     Refusals (ValueError, before any device call): data_dev not a GPU tensor or not (S, C, N); n_samples outside
     2 .. 16384; sr not positive; alpha outside [0, 1); a taper that is not (n,); no, more than 1024 or non-finite
     frequencies; multi_component with more than 64 components; rows x max(2 bins, F) >= 2^31; a workspace too small for
-    64 rows.  Out of scope: response removal, float64 days, a `spectrum_func` callable, propagation corrections,
-    averaging and model fits, `integrate` / `differentiate`."""
+    64 rows.  Propagation corrections, the network average and Mw* follow in network_average_spectra and
+    approximate_moment_magnitudes (source_spectra runs both); `integrate` / `differentiate` are integrate_spectra and
+    differentiate_spectra.  Out of scope: response removal, float64 days, a `spectrum_func` callable, and the model
+    fit (fit_average_spectrum: see network_average_spectra)."""
     import ctypes as C
     import torch
     from . import _lib
@@ -921,6 +925,230 @@ def fft_spectra(data_dev, starts, n_samples, *, sr, frequencies=None, alpha=0.05
                 C.c_void_p(spectra.data_ptr()), C.c_void_p(valid.data_ptr()))
             _lib.check(rc, "bpmf_fft_spectrum_dev")
         return spectra, freq, valid.to(torch.bool)
+
+
+SS_SNR, SS_CORRECT, SS_AVERAGE, SS_MW = 1, 2, 4, 8      # the stages of bpmf_source_spectra_dev
+
+
+def _source_spectra_shape(name, spectra, other, valid):
+    """(E, S, C, F) of two spectra tensors of equal shape (E, S, F) or (E, S, C, F) and their (E, S) `valid`; the
+    refusals that need no device."""
+    import torch
+    for t in (spectra, other):
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.float64:
+            raise ValueError(f"{name}: the spectra must be float64 tensors (as fft_spectra and multiband_spectra "
+                             "return them)")
+    if spectra.dim() not in (3, 4) or spectra.shape != other.shape:
+        raise ValueError(f"{name}: the spectra must be (E, S, F) or (E, S, C, F) and equal in shape; got "
+                         f"{tuple(spectra.shape)} and {tuple(other.shape)}")
+    E, S, F = int(spectra.shape[0]), int(spectra.shape[1]), int(spectra.shape[-1])
+    Cc = 1 if spectra.dim() == 3 else int(spectra.shape[2])
+    if tuple(np.shape(valid)) != (E, S):
+        raise ValueError(f"{name}: valid must be (E, S) = ({E}, {S}); got {tuple(np.shape(valid))}")
+    if not 1 <= S * Cc <= pp.SOURCE_SPECTRA_MAX_CHANNELS:
+        raise ValueError(f"{name}: an event takes 1 .. {pp.SOURCE_SPECTRA_MAX_CHANNELS} channels; got S * C = {S * Cc}")
+    if not 1 <= F <= pp.SOURCE_SPECTRA_MAX_FREQUENCIES:
+        raise ValueError(f"{name}: 1 .. {pp.SOURCE_SPECTRA_MAX_FREQUENCIES} frequencies; got {F}")
+    if E * S * Cc * F >= 2**31:
+        raise ValueError(f"{name}: {E} events x {S * Cc} channels x {F} frequencies; fewer than 2^31 values fit")
+    if not spectra.is_cuda or not other.is_cuda or spectra.device != other.device:
+        raise ValueError(f"{name}: the spectra must be tensors on one GPU (there is no CPU path; the definitions on "
+                         "the host are postprocess.source_spectra_host and approximate_moment_magnitude_host)")
+    return E, S, Cc, F
+
+
+def _per_station(name, what, value, shape, dev, dtype):
+    import torch
+    if tuple(np.shape(value)) != shape:
+        raise ValueError(f"{name}: {what} must be {shape}; got {tuple(np.shape(value))}")
+    value = value if isinstance(value, torch.Tensor) else np.array(value)      # (a copy: the array may be read-only)
+    return torch.as_tensor(value).to(device=dev, dtype=dtype).contiguous()
+
+
+def network_average_spectra(signal, noise, *, phase, valid, noise_valid=None, dist_km, tt_p_sec, tt_s_sec,
+                            location_err_km, frequencies, medium, q_phase_prefactor=None, attenuation="reference",
+                            radiation=None, snr_threshold, average_log=True, min_num_valid_channels_per_freq_bin=0,
+                            max_relative_distance_err_pct=25.0, reduce="mean"):
+    """What compute_moment_magnitude does between the spectra and the model fit (BPMF/spectrum.py:1801-1867) for one
+    phase ("p" or "s") of E events, in one call on the device (bpmf_source_spectra_dev, csrc/source_spectra.hip):
+    compute_signal_to_noise_ratio, correct_geometrical_spreading, correct_attenuation and
+    compute_network_average_spectrum.
+
+    `signal`, `noise`: (E, S, F) or (E, S, C, F) float64 tensors on the GPU, as fft_spectra / multiband_spectra return
+    them for the phase's and the noise windows, on the `frequencies` (F,) given (a resample of multi-band spectra onto
+    other targets is the caller's); `valid`, `noise_valid` (E, S) bool: their `valid` (noise_valid None: all there).
+    `dist_km`, `tt_p_sec`, `tt_s_sec` (E, S): source-receiver distances and travel times; `location_err_km` (E,):
+    sqrt(hmax_unc^2 + vmax_unc^2); `medium`: the reference's medium_properties (postprocess.MEDIUM_KEYS);
+    `radiation`: the phase's radiation coefficient (None: sqrt(4/15) for P, sqrt(2/5) for S).
+    attenuation="reference" keeps what the reference does (postprocess.attenuation_plan): BOTH phases are corrected
+    with the S travel time, the P factor with Q * prefactor["s"] and the S factor with Q * prefactor["p"];
+    attenuation="physical" pairs tt_p with Q_p and tt_s with Q_s.
+
+    Returns a dict of tensors on the inputs' device and the current stream: `corrected`, `snr` (shaped as `signal`),
+    `average`, `std` (E, F) float64 (NaN where `mask`), `mask` (E, F) bool, `num_valid` (E, F) int32 and `used` (E, S)
+    bool.  The (E, F) averages are exactly what Spectrum.fit_average_spectrum takes.  That fit (SciPy's curve_fit: TRF
+    with a 2-point Jacobian on parameters of scale 1e11 .. 1e15 and 1 .. 30 with x_scale = 1) is not offered: its
+    answer is a property of SciPy's termination rules, not a definition.  The definition is
+    postprocess.source_spectra_host; bounds in DESIGN.md section 4.  An event gives the same bits alone and in any batch.
+
+    Refusals (ValueError, before any device call): spectra that are no float64 tensors of equal shape (E, S, F) or
+    (E, S, C, F) on one GPU; S * C above 256; F above 1024; E S C F >= 2^31; a per-station table that is not (E, S);
+    a phase, reduce or attenuation that is not one of the two; frequencies that are not (F,) finite numbers."""
+    import ctypes as C
+    import torch
+    from . import _lib
+    name = "network_average_spectra"
+    if phase not in ("p", "s"):
+        raise ValueError(f"{name}: phase must be 'p' or 's'; got {phase!r}")
+    if reduce not in ("mean", "median"):
+        raise ValueError(f"{name}: reduce must be 'mean' or 'median'; got {reduce!r}")
+    k = ("p", "s").index(phase)
+    f = np.array(frequencies.detach().cpu().numpy() if isinstance(frequencies, torch.Tensor) else frequencies,
+                 dtype=np.float64)                                     # (a copy: it is uploaded, and may be read-only)
+    which, q_rows = pp.attenuation_plan(f, medium, q_phase_prefactor, attenuation)
+    if isinstance(signal, torch.Tensor) and signal.dim() in (3, 4) and signal.shape[-1] != len(f):
+        raise ValueError(f"{name}: the spectra hold {signal.shape[-1]} frequencies, `frequencies` {len(f)}")
+    E, S, Cc, F = _source_spectra_shape(name, signal, noise, valid)
+    constant = float(pp.geometry_constants(medium)[k])
+    radiation = float((pp.RADIATION_P, pp.RADIATION_S)[k] if radiation is None else radiation)
+    dev = signal.device
+    with torch.cuda.device(dev):
+        tab = {"valid": _per_station(name, "valid", valid, (E, S), dev, torch.uint8),
+               "noise_valid": _per_station(name, "noise_valid", np.ones((E, S), bool) if noise_valid is None
+                                           else noise_valid, (E, S), dev, torch.uint8),
+               "dist": _per_station(name, "dist_km", dist_km, (E, S), dev, torch.float64),
+               "tt": _per_station(name, "tt_p_sec / tt_s_sec", tt_p_sec if which[k] == "p" else tt_s_sec, (E, S), dev,
+                                  torch.float64),
+               "err": _per_station(name, "location_err_km", location_err_km, (E,), dev, torch.float64),
+               "f": torch.as_tensor(f, device=dev), "q": torch.as_tensor(np.ascontiguousarray(q_rows[k]), device=dev)}
+        x, z = signal.contiguous(), noise.contiguous()
+        out = {"corrected": torch.empty_like(x), "snr": torch.empty_like(x),
+               "average": torch.empty((E, F), dtype=torch.float64, device=dev),
+               "mask": torch.empty((E, F), dtype=torch.uint8, device=dev),
+               "std": torch.empty((E, F), dtype=torch.float64, device=dev),
+               "num_valid": torch.empty((E, F), dtype=torch.int32, device=dev),
+               "used": torch.empty((E, S), dtype=torch.uint8, device=dev)}
+        if E:
+            p = {key: C.c_void_p(t.data_ptr()) for key, t in list(tab.items()) + list(out.items())}
+            rc = _lib.lib().bpmf_source_spectra_dev(
+                C.c_void_p(x.data_ptr()), C.c_void_p(z.data_ptr()), p["valid"], p["noise_valid"], p["dist"], None,
+                p["tt"], p["err"], p["f"], p["q"], E, S, Cc, F, SS_SNR | SS_CORRECT | SS_AVERAGE, constant, radiation,
+                float(snr_threshold), float(max_relative_distance_err_pct), int(min_num_valid_channels_per_freq_bin),
+                int(bool(average_log)), int(reduce == "median"), 1, 0, 0.0, 0.0, 0,
+                C.c_void_p(torch.cuda.current_stream(dev).cuda_stream), p["corrected"], p["snr"], p["average"],
+                p["mask"], p["std"], p["num_valid"], p["used"], None, None, None, None, None)
+            _lib.check(rc, "bpmf_source_spectra_dev")
+        out["mask"], out["used"] = out["mask"].to(torch.bool), out["used"].to(torch.bool)
+        return out
+
+
+def approximate_moment_magnitudes(corrected, snr, *, valid, frequencies, epicentral_dist_km, snr_threshold=10.0,
+                                  num_averaging_bands=1, low_snr_freq_min_hz=2.0,
+                                  magnitude_log_moment_scaling=2.0 / 3.0, weight_max=3.0, max_num_bad_measurements=6):
+    """approximate_moment_magnitude (BPMF/spectrum.py:1341-1496, with _snr_based_weights :1290-1338) of one phase of E
+    events in one call on the device (bpmf_source_spectra_dev, stage 8): `corrected` and `snr` as
+    network_average_spectra returns them, `valid` (E, S) bool, `frequencies` (F,) ascending, `epicentral_dist_km`
+    (E, S).  The reference's dtypes are kept: the measurements' SNR and the weights are float32, the weights' sum a
+    float32 sum in NumPy's order.  The reference indexes the distances by spectrum id and so runs only with
+    multi_component_spectrum=True; here a channel of (E, S, C, F) spectra takes the distance of its station.
+    Returns a dict of tensors: `Mw_star`, `log10_M0` (E,) float64 (NaN for an event without a positive weight),
+    `measured_disp` (E, S * C) float64 (NaN for a station that is not valid), `weights`, `measurement_snr` (E, S * C)
+    float32.  The definition is postprocess.approximate_moment_magnitude_host; bounds in DESIGN.md section 4.
+    Refusals (ValueError, before any device call): as network_average_spectra; num_averaging_bands outside 1 .. 8;
+    frequencies that do not ascend; max_num_bad_measurements < 0."""
+    import ctypes as C
+    import torch
+    from . import _lib
+    name = "approximate_moment_magnitudes"
+    f = np.ascontiguousarray(frequencies.detach().cpu().numpy() if isinstance(frequencies, torch.Tensor)
+                             else frequencies, dtype=np.float64)
+    if f.ndim != 1 or not np.isfinite(f).all() or np.any(np.diff(f) <= 0):
+        raise ValueError(f"{name}: frequencies must be (F,) finite, ascending numbers")
+    nab = int(num_averaging_bands)
+    if not 1 <= nab <= pp.SOURCE_SPECTRA_MAX_AVERAGING_BANDS:
+        raise ValueError(f"{name}: num_averaging_bands must be 1 .. {pp.SOURCE_SPECTRA_MAX_AVERAGING_BANDS}; got {nab}")
+    if int(max_num_bad_measurements) < 0:
+        raise ValueError(f"{name}: max_num_bad_measurements must not be negative")
+    if isinstance(corrected, torch.Tensor) and corrected.dim() in (3, 4) and corrected.shape[-1] != len(f):
+        raise ValueError(f"{name}: the spectra hold {corrected.shape[-1]} frequencies, `frequencies` {len(f)}")
+    E, S, Cc, F = _source_spectra_shape(name, corrected, snr, valid)
+    first_high = int(np.searchsorted(f, low_snr_freq_min_hz, side="right"))        # the bands with f > the minimum
+    dev = corrected.device
+    with torch.cuda.device(dev):
+        v = _per_station(name, "valid", valid, (E, S), dev, torch.uint8)
+        epi = _per_station(name, "epicentral_dist_km", epicentral_dist_km, (E, S), dev, torch.float64)
+        x, r = corrected.contiguous(), snr.contiguous()
+        out = {"Mw_star": torch.empty((E,), dtype=torch.float64, device=dev),
+               "log10_M0": torch.empty((E,), dtype=torch.float64, device=dev),
+               "measured_disp": torch.empty((E, S * Cc), dtype=torch.float64, device=dev),
+               "weights": torch.empty((E, S * Cc), dtype=torch.float32, device=dev),
+               "measurement_snr": torch.empty((E, S * Cc), dtype=torch.float32, device=dev)}
+        if E:
+            p = {key: C.c_void_p(t.data_ptr()) for key, t in out.items()}
+            rc = _lib.lib().bpmf_source_spectra_dev(
+                None, None, C.c_void_p(v.data_ptr()), None, None, C.c_void_p(epi.data_ptr()), None, None, None, None,
+                E, S, Cc, F, SS_MW, 0.0, 1.0, float(snr_threshold), 0.0, 0, 0, 0, nab, first_high,
+                float(magnitude_log_moment_scaling), float(weight_max), int(max_num_bad_measurements),
+                C.c_void_p(torch.cuda.current_stream(dev).cuda_stream), C.c_void_p(x.data_ptr()),
+                C.c_void_p(r.data_ptr()), None, None, None, None, None, p["Mw_star"], p["log10_M0"],
+                p["measured_disp"], p["weights"], p["measurement_snr"])
+            _lib.check(rc, "bpmf_source_spectra_dev")
+        return out
+
+
+def source_spectra(*, p=None, s=None, noise, valid_p=None, valid_s=None, noise_valid=None, dist_km,
+                   epicentral_dist_km, tt_p_sec, tt_s_sec, location_err_km, frequencies, medium, snr_threshold,
+                   q_phase_prefactor=None, attenuation="reference", average_log=True,
+                   min_num_valid_channels_per_freq_bin=0, max_relative_distance_err_pct=25.0, reduce="mean",
+                   num_averaging_bands=1, low_snr_freq_min_hz=2.0, magnitude_log_moment_scaling=2.0 / 3.0,
+                   weight_max=3.0, max_num_bad_measurements=6):
+    """network_average_spectra, then approximate_moment_magnitudes, for each phase given (`p`, `s`: the phase's
+    spectra; `valid_p`, `valid_s`: their `valid`): a day's events go from the spectra in HBM to (E, F) network-average
+    source spectra and a per-event Mw* in two calls per phase.  Returns {"p": {...}, "s": {...}} for the phases given,
+    each the two functions' dicts in one.  The phases are NOT combined: the reference's combined Mw* is, through a
+    misplaced `if` (BPMF/spectrum.py:1879-1880), the last phase's value alone; the caller averages as they see fit."""
+    given = [(ph, x, v) for ph, x, v in (("p", p, valid_p), ("s", s, valid_s)) if x is not None]
+    if not given:
+        raise ValueError("source_spectra: give the spectra of at least one phase (p=, s=)")
+    out = {}
+    for ph, x, v in given:
+        if v is None:
+            raise ValueError(f"source_spectra: valid_{ph} is needed beside {ph}=")
+        out[ph] = network_average_spectra(
+            x, noise, phase=ph, valid=v, noise_valid=noise_valid, dist_km=dist_km, tt_p_sec=tt_p_sec,
+            tt_s_sec=tt_s_sec, location_err_km=location_err_km, frequencies=frequencies, medium=medium,
+            q_phase_prefactor=q_phase_prefactor, attenuation=attenuation, snr_threshold=snr_threshold,
+            average_log=average_log, min_num_valid_channels_per_freq_bin=min_num_valid_channels_per_freq_bin,
+            max_relative_distance_err_pct=max_relative_distance_err_pct, reduce=reduce)
+        out[ph].update(approximate_moment_magnitudes(
+            out[ph]["corrected"], out[ph]["snr"], valid=v, frequencies=frequencies,
+            epicentral_dist_km=epicentral_dist_km, snr_threshold=snr_threshold,
+            num_averaging_bands=num_averaging_bands, low_snr_freq_min_hz=low_snr_freq_min_hz,
+            magnitude_log_moment_scaling=magnitude_log_moment_scaling, weight_max=weight_max,
+            max_num_bad_measurements=max_num_bad_measurements))
+    return out
+
+
+def _spectra_and_frequencies(name, spectra, frequencies):
+    import torch
+    if not isinstance(spectra, torch.Tensor) or not spectra.is_cuda or not spectra.is_floating_point():
+        raise ValueError(f"{name}: spectra must be a floating-point tensor on the GPU")
+    f = torch.as_tensor(frequencies if isinstance(frequencies, torch.Tensor) else np.array(frequencies))
+    f = f.to(device=spectra.device, dtype=spectra.dtype)
+    if f.dim() != 1 or spectra.dim() < 1 or spectra.shape[-1] != f.shape[0]:
+        raise ValueError(f"{name}: frequencies must be (F,) with F the spectra's last axis")
+    return f
+
+
+def integrate_spectra(spectra, frequencies):
+    """Spectrum.integrate (BPMF/spectrum.py:650-687): the spectra (..., F), single ones or network averages, divided
+    by their frequencies -- one rounded division each, on the spectra's device."""
+    return spectra / _spectra_and_frequencies("integrate_spectra", spectra, frequencies)
+
+
+def differentiate_spectra(spectra, frequencies):
+    """Spectrum.differentiate (BPMF/spectrum.py:689-727): the spectra (..., F) times their frequencies."""
+    return spectra * _spectra_and_frequencies("differentiate_spectra", spectra, frequencies)
 
 
 def _peak_amplitude_window(sr, offset_win_peak_amp_sec, duration_win_peak_amp_sec):

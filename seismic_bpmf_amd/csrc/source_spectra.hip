@@ -332,7 +332,9 @@ extern "C" int bpmf_source_spectra_dev(const double* d_signal, const double* d_n
         return -1;
     }
     const bool snr = flags & SS_SNR, correct = flags & SS_CORRECT, average = flags & SS_AVERAGE, mw = flags & SS_MW;
-    if (!d_valid || !d_corrected || !d_snr || ((snr || correct) && !d_signal) ||
+    // d_corrected: written by stage 2, read by 4 and 8; d_snr: written by stage 1, read by 4 and 8
+    if (!d_valid || ((correct || average || mw) && !d_corrected) || ((snr || average || mw) && !d_snr) ||
+        ((snr || correct) && !d_signal) ||
         (snr && (!d_noise || !d_noise_valid)) ||
         (correct && (!d_dist || !d_travel_time || !d_frequencies || !d_q)) ||
         (average && (!d_dist || !d_location_err || !d_average || !d_mask || !d_std || !d_num_valid || !d_used)) ||

@@ -2006,8 +2006,10 @@ def network_average_spectrum_host(spectra, snr, present, dist_err_pct, *, snr_th
 def snr_based_weights_host(snr, snr_threshold, weight_max=3.0, max_num_bad_measurements=6):
     """_snr_based_weights (:1290-1338) on a float32 vector: min(snr, 1.001 threshold, weight_max), all in float32;
     with at least max_num_bad_measurements values >= threshold every value < threshold gets 0, otherwise all but the
-    max_num_bad_measurements largest get 0.  Equal values are ordered by index (the reference's np.argsort leaves
-    their order open; in every tested input only zeros tie, whose weight is 0 either way)."""
+    max_num_bad_measurements largest get 0.  Equal values are ordered by index: of a tied group across the cut, those
+    of the lowest indices get 0.  The reference's np.argsort (quicksort) leaves their order open, and from 17 values
+    on does not keep index order, so this rule is the definition's own; the device is held to it on non-zero ties
+    that straddle the cut at 9, 20 and 40 channels (tests/source_spectra_cases.py: snr_ties_*)."""
     snr = np.asarray(snr, dtype=np.float32)
     thr = np.float32(snr_threshold)
     weights = np.minimum(np.minimum(snr, np.float32(1.001 * snr_threshold)), np.float32(weight_max))

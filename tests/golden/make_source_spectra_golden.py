@@ -19,6 +19,10 @@ tests/source_spectra_cases.py.  For every case of sc.RECORDED and phase ("p", "s
   multi_component_spectrum=True), for option o of sc.MW_OPTIONS: `mw_<k>_<o>` (E,) float64, `msnr_<k>_<o>` and
   `rawweights_<k>_<o>` (E, S) float32: what the `snr_based_weights` callable was handed and returned (0 for an absent
   station), `mwraised_<k>_<o>` (E,) bool: the call raised (an empty selection of bands: the reference's unused argmax);
+* for every case of sc.STAGE4_RECORDED (corrected spectra, SNR and epicentral distances handed to
+  approximate_moment_magnitude as they are, phase "p") the same four arrays as `mw_<case>_<o>`, `msnr_<case>_<o>`,
+  `rawweights_<case>_<o>`, `mwraised_<case>_<o>`; events with a NaN or inf distance are recorded as they come and are
+  not compared (there the reference clips a pandas Series, which reads a NaN bound as no bound);
 * `numpy_version`, `pandas_version`.
 
 Usage: python tests/golden/make_source_spectra_golden.py
@@ -177,6 +181,47 @@ def main():
             for key, values in rows.items():
                 out[key] = np.stack([np.asarray(v) for v in values])
             print(k)
+    # the stage-4 cases: corrected spectra, SNR and distances handed to approximate_moment_magnitude as they are
+    for name in sc.STAGE4_RECORDED:
+        x = sc.stage4_inputs(name)
+        E, S = x["present"].shape
+        names = [f"ST{s:02d}" for s in range(S)]
+        rows = {}
+        for e in range(E):
+            event = DuckEvent(pd, names, x["epi"][e], x["epi"][e], x["epi"][e], x["epi"][e], 0.0, 0.0)
+            spec = Spectrum(event=event)
+            spec.frequencies = np.array(x["frequencies"])
+            spec.phases = ["noise", "p"]
+            spec.multi_component_spectrum = True
+            present = np.flatnonzero(x["present"][e])
+            spec.p_spectrum = {names[s]: {"spectrum": np.array(x["corrected"][e, s]), "freq": spec.frequencies}
+                               for s in present}
+            spec.snr_p_spectrum = {names[s]: {"snr": np.array(x["snr"][e, s]), "freq": spec.frequencies}
+                                   for s in present}
+            for o, option in enumerate(sc.MW_OPTIONS):
+                seen = {}
+
+                def capture(snr, snr_threshold, **kw):
+                    seen["snr"] = snr.copy()
+                    seen["weights"] = _snr_based_weights(snr, snr_threshold, **kw).copy()
+                    return seen["weights"].copy()
+
+                msnr, raw = np.zeros(S, np.float32), np.zeros(S, np.float32)
+                try:
+                    with np.errstate(all="ignore"), contextlib.redirect_stdout(io.StringIO()):
+                        value = approximate_moment_magnitude(
+                            spec, snr_threshold=sc.THRESHOLD, num_averaging_bands=option[0],
+                            low_snr_freq_min_hz=option[1], magnitude_log_moment_scaling=sc.SCALING, phases=["p"],
+                            snr_based_weights=capture)["p"]
+                    msnr[present], raw[present] = seen["snr"], seen["weights"]
+                    raised = False
+                except ValueError:
+                    value, raised = np.nan, True
+                for key, v in (("mw", value), ("msnr", msnr), ("rawweights", raw), ("mwraised", raised)):
+                    rows.setdefault(f"{key}_{name}_{o}", [None] * E)[e] = v
+        for key, values in rows.items():
+            out[key] = np.stack([np.asarray(v) for v in values])
+        print(name)
     out["numpy_version"] = np.array(np.__version__)
     out["pandas_version"] = np.array(pd.__version__)
     np.savez_compressed(OUT, **out)

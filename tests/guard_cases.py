@@ -903,8 +903,56 @@ def extract_peaks_calls(lib):
                  {"count": ((2,), np.int32), "records": ((PEAKS_CAPACITY + 3, 4), np.int32)}, invoke, verify)]
 
 
+SS_LANES = 64                            # lanes of a workgroup of csrc/source_spectra.hip: the median's column is (NC, 64) f64
+SS_AVERAGE_OPTION, SS_MW_OPTION = 1, 1   # indices into source_spectra_cases.AVERAGE_OPTIONS (log, median) / MW_OPTIONS
+
+
+def source_spectra_calls(lib):
+    """All four stages in one call (flags 15), the median asked for: 15 channels x 65 bins (nothing a multiple of 64),
+    and 129 channels x 3 bins (129 x 64 x 8 bytes of dynamic LDS: just over the 64 KB that need the opt-in).  Twelve
+    outputs of four element widths, no workspace."""
+    import source_spectra_cases as sc
+    from seismic_bpmf_amd import postprocess as pp
+    option, mw_option = sc.AVERAGE_OPTIONS[SS_AVERAGE_OPTION], sc.MW_OPTIONS[SS_MW_OPTION]
+    calls = []
+    for name in sc.GUARD_CASES:
+        _, E, S, Cc, F, _ = sc.CASES[name]
+        x, arguments = sc.inputs(name), sc.phase_arguments(name, "p")
+        arrays, params = sc.c_inputs(name, "p")
+        params.update(average_log=int(option[0]), median=int(option[1] == "median"), min_num_valid=option[2],
+                      max_err_pct=option[3], bands=mw_option[0],
+                      first_high=int(np.searchsorted(x["frequencies"], mw_option[1], side="right")))
+        with np.errstate(all="ignore"):
+            want = pp.source_spectra_host(**arguments, **sc.average_kwargs(option))
+            want_mw = pp.approximate_moment_magnitude_host(want["corrected"], want["snr"], x["present"],
+                                                           x["frequencies"], x["epi"], **sc.mw_kwargs(mw_option))
+            geometry = arguments["geometry_constant"] * (1000.0 * x["dist"]) / arguments["radiation"]
+            att = np.exp(np.pi * arguments["tt_sec"][..., None] * x["frequencies"] / arguments["q_row"])
+
+        def invoke(lib, p, nb, stream, E=E, S=S, Cc=Cc, F=F, params=params):
+            return sc.c_call(lib, p, E, S, Cc, F, 15, stream, **params)
+
+        def verify(out, want=want, want_mw=want_mw, arguments=arguments, geometry=geometry, att=att, Cc=Cc, F=F):
+            got = {k: out[k] for k in ("average", "std", "num_valid")}
+            got.update(mask=out["mask"] != 0, used=out["used"] != 0, snr=out["snr"].reshape(want["snr"].shape),
+                       corrected=out["corrected"].reshape(want["corrected"].shape))
+            assert not (out["mask"] > 1).any() and not (out["used"] > 1).any()
+            assert np.array_equal(got["snr"], want["snr"], equal_nan=True)
+            assert sc.corrected_ok(got["corrected"], arguments["signal"], geometry[:, :, None, None],
+                                   att[:, :, None, :], arguments["present"]) == 0.0
+            discrete, r_avg, r_std = sc.check_average(got, want, option, Cc)
+            assert discrete and r_avg <= 1.0 and r_std <= 1.0, (discrete, r_avg, r_std)
+            got_mw = {k: out[k] for k in ("Mw_star", "log10_M0", "measured_disp", "weights", "measurement_snr")}
+            discrete, r_disp, r_m0, r_mw = sc.check_mw(got_mw, want_mw, F)
+            assert discrete and r_disp <= 1.0 and r_m0 <= 1.0 and r_mw <= 1.0, (discrete, r_disp, r_m0, r_mw)
+
+        calls.append(Call(f"source_spectra:{name}", "bpmf_source_spectra_dev", arrays, sc.output_specs(E, S, Cc, F),
+                          invoke, verify))
+    return calls
+
+
 TIER2 = [peak_amplitudes_calls, templates_calls, normalize_batch_calls, resample_calls, find_picks_calls,
-         window_stats_calls, extract_peaks_calls]
+         window_stats_calls, extract_peaks_calls, source_spectra_calls]
 
 TIER1 = [tdt_rms_calls, multiband_calls, svdwf_calls, bandpass_calls, multiples_calls, intertemplate_calls,
          median_mad_calls, tdt_mad_calls, kurtosis_calls, mf_calls, bp_run_calls, relocate_calls]

@@ -194,6 +194,39 @@ def test_each_tier_2_case_ends_in_a_partial_row_window_or_tile(lib):
     assert gc.PEAKS_N % 256 != 0
 
 
+def test_the_source_spectra_calls_miss_every_multiple_of_64_and_cross_the_lds_opt_in(lib):
+    import source_spectra_cases as sc
+    from seismic_bpmf_amd import postprocess as pp
+    small, long_column = (sc.CASES[n][1:5] for n in sc.GUARD_CASES)
+    assert small == (3, 5, 3, 65) and (small[1] * small[2]) % gc.SS_LANES == 15 and small[3] % gc.SS_LANES == 1
+    E, S, Cc, F = long_column
+    assert S * Cc == 129 and F == 3 and S * Cc <= pp.SOURCE_SPECTRA_MAX_CHANNELS
+    assert S * Cc * gc.SS_LANES * 8 == 66048 > 64 * 1024 >= (S * Cc - 1) * gc.SS_LANES * 8       # the median's column
+    assert sc.AVERAGE_OPTIONS[gc.SS_AVERAGE_OPTION][:2] == (True, "median")
+    calls = gc.source_spectra_calls(lib)
+    assert len(calls) == 2
+    for call, name in zip(calls, sc.GUARD_CASES):
+        assert sorted(call.outputs) == sorted(sc.POINTER_OUTPUTS) and call.variants == [{}] and call.refusal is None
+        assert {np.dtype(spec[1]).itemsize for spec in call.outputs.values()} == {1, 4, 8}
+        assert sorted(np.dtype(spec[1]).name for spec in call.outputs.values()).count("float32") == 2
+        # the definition's own answer passes the call's verify
+        want = pp.source_spectra_host(**sc.phase_arguments(name, "p"),
+                                      **sc.average_kwargs(sc.AVERAGE_OPTIONS[gc.SS_AVERAGE_OPTION]))
+        x = sc.inputs(name)
+        with np.errstate(all="ignore"):
+            mw = pp.approximate_moment_magnitude_host(want["corrected"], want["snr"], x["present"], x["frequencies"],
+                                                      x["epi"], **sc.mw_kwargs(sc.MW_OPTIONS[gc.SS_MW_OPTION]))
+        out = {**{k: want[k] for k in ("average", "std", "num_valid")}, **mw,
+               "mask": want["mask"].astype(np.uint8), "used": want["used"].astype(np.uint8),
+               "snr": want["snr"].reshape(call.outputs["snr"][0]),
+               "corrected": want["corrected"].reshape(call.outputs["corrected"][0])}
+        call.verify(out)
+        assert (~want["mask"]).any() and np.isfinite(mw["Mw_star"]).any()
+        out["num_valid"] = out["num_valid"] + 1
+        with pytest.raises(AssertionError):
+            call.verify(out)
+
+
 def test_tier_1_cases_that_need_no_plan_build_on_the_host(lib):
     """Every builder but the two that create a backprojection plan: their workspace sizes come from pure host
     functions, their definitions from the host."""

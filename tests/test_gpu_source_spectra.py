@@ -114,7 +114,7 @@ def assert_mw(label, got, want, n_bands):
 
 # every shape of the issue: E = 3 with S = 5, C = 1, F = 4; 63 / 64 / 65 channels and bins; the ceilings; (E, S, F)
 # and (E, S, C, F); events without a station, bins without a channel, even and odd counts, zeros, NaN, missing noise
-@pytest.mark.parametrize("name", sc.GPU_CASES)
+@pytest.mark.parametrize("name", sc.STAGES_1_TO_3_CASES)
 def test_stages_1_to_3_equal_the_definition(name):
     C = max(sc.CASES[name][3], 1)
     options = range(len(sc.AVERAGE_OPTIONS)) if name != "ceiling" else (0, 1)
@@ -159,6 +159,27 @@ def test_stage_4_equals_the_definition(name):
         for o in range(len(sc.MW_OPTIONS)):
             got = device_mw(name, chain["corrected"], chain["snr"], o)
             assert_mw(f"{name} {phase} {sc.MW_OPTIONS[o]}", got, host_mw(name, phase, o), F)
+
+
+@pytest.mark.parametrize("name", list(sc.STAGE4_CASES))
+def test_stage_4_equals_the_definition_on_the_cases_built_directly(name):
+    """4 to 8 averaging bands, tied, zero and non-finite distances at S = 2, 3, 4, 5 and 9, and tied SNRs across the
+    weight cut-off at 9, 20 and 40 channels (source_spectra_cases.stage4_inputs; what each case reaches is asserted on
+    the definition in tests/test_source_spectra_host.py).  No event is excluded."""
+    from seismic_bpmf_amd import postprocess as pp, workflow
+    x = sc.stage4_inputs(name)
+    F = sc.STAGE4_CASES[name][4]
+    junk(4 * x["corrected"].nbytes)
+    corrected, snr = up(x["corrected"]), up(x["snr"])
+    for o, max_bad in sc.stage4_runs(name):
+        kw = sc.mw_kwargs(sc.MW_OPTIONS[o], max_bad)
+        with np.errstate(all="ignore"):
+            want = pp.approximate_moment_magnitude_host(x["corrected"], x["snr"], x["present"], x["frequencies"],
+                                                        x["epi"], **kw)
+        got = down(workflow.approximate_moment_magnitudes(corrected, snr, valid=x["present"],
+                                                          frequencies=x["frequencies"], epicentral_dist_km=x["epi"],
+                                                          **kw))
+        assert_mw(f"{name} {sc.MW_OPTIONS[o]} max_bad={max_bad}", got, want, F)
 
 
 @pytest.mark.parametrize("name", ["small", "edge", "components", "c65"])

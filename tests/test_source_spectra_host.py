@@ -6,6 +6,10 @@ tests/golden/make_source_spectra_golden.py with NumPy and pandas of the versions
 Every float is demanded bit for bit: the definitions restate the same NumPy calls in the same order.  (Measured worst
 relative difference: 0 -- nothing needed the 4 x allowance the plan provided for.)
 
+The cases built directly for stage 4 (4 to 8 averaging bands, tied and non-finite distances, tied SNRs) and case
+`tables` come with assertions, on the definition, that each reaches what it is there for: without them the device
+comparison could pass vacuously.
+
 Then: the input conditions under which the GPU tests may demand equal discrete outputs for every event; the planted
 defects, each of which must fail the GPU comparison's own check (source_spectra_cases.check_average, corrected_ok,
 check_mw); and the refusals of the Python and C surfaces that need no device."""
@@ -162,6 +166,23 @@ def test_input_conditions_of_the_gpu_cases(name):
             present.shape[0], -1, C).reshape(snr.shape[:-1])[..., None], equal_nan=True)
 
 
+@pytest.mark.parametrize("name", [n for n in sc.STAGE4_CASES if not n.startswith("snr_ties")])
+def test_input_conditions_of_the_stage_4_cases(name):
+    """As above for the cases built directly (the snr_ties cases tie on purpose: there the rule "by index" is what is
+    tested)."""
+    x = sc.stage4_inputs(name)
+    for o, max_bad in sc.stage4_runs(name):
+        msnr = stage4_definition(name, o, max_bad)["measurement_snr"]
+        for e in range(len(msnr)):
+            v = msnr[e][x["present"][e]]
+            low = v[(v > 0) & (v < np.float32(sc.THRESHOLD))]
+            assert len(np.unique(low)) == len(low), (name, o, e)
+            for edge in (sc.THRESHOLD, 1.001 * sc.THRESHOLD, sc.WEIGHT_MAX):
+                edge = np.float32(edge)
+                near = np.abs(v - edge) <= 2 * np.spacing(edge)
+                assert (v[near] == edge).all(), (name, o, e)
+
+
 # ---- planted defects: each must fail the GPU comparison's own check ----
 def defective_average(arguments, option, defect=None):
     """source_spectra_host restated with one defect planted (None: it must equal the definition)."""
@@ -235,7 +256,7 @@ AVERAGE_DEFECTS = [("<=", 0), ("count_after_domain", 0), ("ddof", 0), ("upper_mi
 
 @pytest.mark.parametrize("o", range(len(sc.AVERAGE_OPTIONS)))
 def test_the_restated_definition_is_the_definition(o):
-    for name in ("edge", "components"):
+    for name in ("edge", "components", "tables"):
         arguments = sc.phase_arguments(name, "s")
         got, want = defective_average(arguments, sc.AVERAGE_OPTIONS[o]), chain(name, "s", o)
         assert all(same(got[k], want[k]) for k in want), [k for k in want if not same(got[k], want[k])]
@@ -249,29 +270,86 @@ def test_a_planted_defect_in_stages_1_to_3_fails_the_gpu_check(defect, o):
     assert not gpu_check_of_stages_1_to_3(got, chain("edge", "p", o), arguments, sc.AVERAGE_OPTIONS[o], 1)
 
 
-def defective_magnitude(name, phase, o, defect):
-    """approximate_moment_magnitude_host restated for (E, S, F) spectra with one defect planted."""
-    x, c = sc.inputs(name), chain(name, phase)
-    kw = sc.mw_kwargs(sc.MW_OPTIONS[o])
-    thr, nab, f = kw["snr_threshold"], kw["num_averaging_bands"], x["frequencies"]
+SLOT_LEFT = 0.0        # what a slot of the sorted distances holds when no entry was ranked into it
+
+
+def rank_sorted(v, defect=None):
+    """The distances in np.sort's order as the device builds it: every entry is stored at its rank, NaN last, equal
+    entries by index.  Defects: 'ties_by_value' (equal entries share a rank: one slot is written twice, another keeps
+    SLOT_LEFT), 'nan_first'."""
+    def before(a, b):
+        if defect == "nan_first":
+            return (np.isnan(a) and not np.isnan(b)) or a < b
+        return (not np.isnan(a)) if np.isnan(b) else a < b
+    out = np.full(len(v), SLOT_LEFT)
+    for s in range(len(v)):
+        rank = sum(before(v[j], v[s]) or (defect != "ties_by_value" and not before(v[s], v[j]) and j < s)
+                   for j in range(len(v)))
+        out[rank] = v[s]
+    return out
+
+
+def percentile_linear(ordered, q, defect=None):
+    """np.percentile(method="linear") of sorted values: NaN if the last is NaN, else NumPy's two-sided lerp."""
+    n = len(ordered)
+    vi = n * q + (1.0 - q) - 1.0
+    lo = int(np.floor(vi))
+    hi = min(lo + 1, n - 1)
+    t, a, b = vi - lo, ordered[lo], ordered[hi]
+    diff = b - a
+    value = b - diff * (1.0 - t) if t >= 0.5 and defect != "one_sided_lerp" else a + diff * t
+    return np.nan if np.isnan(ordered[-1]) else value
+
+
+def median_of_chosen(chosen, defect=None):
+    ordered, n = np.sort(chosen), len(chosen)
+    if n == 1:
+        return chosen[0]
+    if np.isnan(chosen).any():
+        return np.nan
+    if defect == "upper_middle_of_even" and n % 2 == 0 and n >= 4:
+        return ordered[n // 2]
+    return (ordered[(n - 1) // 2] + ordered[n // 2]) / 2.0
+
+
+def weights_by_rank(m, thr, weight_max, max_bad, defect=None):
+    """snr_based_weights_host restated: ties by index ('ties_last_index_first': the other way round)."""
+    w = np.minimum(np.minimum(m, np.float32(1.001 * thr)), np.float32(weight_max))
+    if (m >= np.float32(thr)).sum() >= max_bad:
+        w[m < np.float32(thr)] = 0.0
+        return w
+    index = np.arange(len(m))
+    order = np.lexsort((-index if defect == "ties_last_index_first" else index, m))
+    w[order[:max(len(m) - max_bad, 0)]] = 0.0
+    return w
+
+
+def restated_magnitude(corrected, snr, present, f, epi, kw, defect=None):
+    """approximate_moment_magnitude_host restated, its sorts, percentiles, medians and SNR ranks written out, with one
+    defect planted (None: it must equal the definition)."""
+    thr, nab, max_bad = kw["snr_threshold"], kw["num_averaging_bands"], kw["max_num_bad_measurements"]
     high = f > kw["low_snr_freq_min_hz"]
-    E, S = x["present"].shape
-    out = {"measured_disp": np.full((E, S), np.nan), "measurement_snr": np.zeros((E, S), np.float32),
-           "weights": np.zeros((E, S), np.float32), "log10_M0": np.full(E, np.nan)}
+    E, S = present.shape
+    F = corrected.shape[-1]
+    x, r_all = np.asarray(corrected).reshape(E, -1, F), np.asarray(snr).reshape(E, -1, F)
+    NC = x.shape[1]
+    C = NC // S
+    out = {"measured_disp": np.full((E, NC), np.nan), "measurement_snr": np.zeros((E, NC), np.float32),
+           "weights": np.zeros((E, NC), np.float32), "log10_M0": np.full(E, np.nan)}
     log = np.log if defect == "ln" else np.log10
     with np.errstate(all="ignore"):
         for e in range(E):
-            ch = np.flatnonzero(x["present"][e])
+            ch = np.flatnonzero(np.repeat(present[e], C))
             if not len(ch):
                 continue
             disp = np.zeros(len(ch))
             m = np.zeros(len(ch), dtype=np.float64 if defect == "float64_snr" else np.float32)
             for j, s in enumerate(ch):
-                r, v = c["snr"][e, s], c["corrected"][e, s]
+                r, v = r_all[e, s], x[e, s]
                 valid = np.flatnonzero(r >= thr if defect == ">=" else r > thr)
                 if len(valid):
                     pick = valid[::-1][:nab] if defect == "highest" else valid[:nab]
-                    disp[j] = np.median(v[pick]) if len(pick) > 1 else v[pick[0]]
+                    disp[j] = median_of_chosen(v[pick], defect)
                     m[j] = thr
                 else:
                     total = pp._skipna_sum(r[high])
@@ -281,27 +359,47 @@ def defective_magnitude(name, phase, o, defect):
             m[disp == 0.0] = 0.0
             if defect == "float64_snr":
                 w = np.minimum(np.minimum(m, 1.001 * thr), sc.WEIGHT_MAX)
-                if (m >= thr).sum() >= sc.MAX_BAD:
+                if (m >= thr).sum() >= max_bad:
                     w[m < thr] = 0.0
                 else:
-                    w[np.argsort(m, kind="stable")[:max(len(m) - sc.MAX_BAD, 0)]] = 0.0
+                    w[np.argsort(m, kind="stable")[:max(len(m) - max_bad, 0)]] = 0.0
             elif defect == "strict_good":
                 w = np.minimum(np.minimum(m, np.float32(1.001 * thr)), np.float32(sc.WEIGHT_MAX))
-                if (m > np.float32(thr)).sum() >= sc.MAX_BAD:
+                if (m > np.float32(thr)).sum() >= max_bad:
                     w[m < np.float32(thr)] = 0.0
                 else:
-                    w[np.argsort(m, kind="stable")[:max(len(m) - sc.MAX_BAD, 0)]] = 0.0
+                    w[np.argsort(m, kind="stable")[:max(len(m) - max_bad, 0)]] = 0.0
             else:
-                w = pp.snr_based_weights_host(m, thr, sc.WEIGHT_MAX, sc.MAX_BAD)
-            epi = x["epi"][e][ch] if defect == "percentiles_of_used" else x["epi"][e]
-            wd = 1.0 / np.clip(x["epi"][e], a_min=np.percentile(epi, 25.0), a_max=np.percentile(epi, 75.0))
+                w = weights_by_rank(m, thr, sc.WEIGHT_MAX, max_bad, defect)
+            of_valid = defect == "percentiles_of_used" or (defect == "percentiles_of_valid_at_3" and S == 3)
+            ordered = rank_sorted(epi[e][present[e]] if of_valid else epi[e], defect)
+            low, up = percentile_linear(ordered, 0.25, defect), percentile_linear(ordered, 0.75, defect)
+            wd = np.repeat(1.0 / np.minimum(np.maximum(epi[e], low), up), C)
             w = (w * wd[ch]).astype(np.float32)
             peaks = np.zeros(len(ch))
             peaks[w > 0.0] = log(disp[w > 0.0]) * w[w > 0.0]
             out["log10_M0"][e] = peaks.sum() / w.sum()
             out["measured_disp"][e, ch], out["measurement_snr"][e, ch], out["weights"][e, ch] = disp, m, w
-    out["Mw_star"] = sc.SCALING * (out["log10_M0"] - 9.1)
+    out["Mw_star"] = kw["magnitude_log_moment_scaling"] * (out["log10_M0"] - 9.1)
     return out
+
+
+def defective_magnitude(name, phase, o, defect):
+    x, c = sc.inputs(name), chain(name, phase)
+    return restated_magnitude(c["corrected"], c["snr"], x["present"], x["frequencies"], x["epi"],
+                              sc.mw_kwargs(sc.MW_OPTIONS[o]), defect)
+
+
+def stage4_definition(name, o, max_bad=sc.MAX_BAD):
+    x = sc.stage4_inputs(name)
+    return pp.approximate_moment_magnitude_host(x["corrected"], x["snr"], x["present"], x["frequencies"], x["epi"],
+                                                **sc.mw_kwargs(sc.MW_OPTIONS[o], max_bad))
+
+
+def stage4_restated(name, o, max_bad=sc.MAX_BAD, defect=None):
+    x = sc.stage4_inputs(name)
+    return restated_magnitude(x["corrected"], x["snr"], x["present"], x["frequencies"], x["epi"],
+                              sc.mw_kwargs(sc.MW_OPTIONS[o], max_bad), defect)
 
 
 def gpu_check_of_stage_4(got, want, n_bands):
@@ -324,6 +422,181 @@ def test_a_planted_defect_in_stage_4_fails_the_gpu_check(defect):
     name = "edge" if defect == "strict_good" else "batch"       # 9 stations: 7 at the threshold, 6 kept by the order
     got, want = defective_magnitude(name, "p", 1, defect), magnitude(name, "p", 1)
     assert not gpu_check_of_stage_4(got, want, sc.CASES[name][4])
+
+
+def test_the_tables_case_reaches_what_it_is_there_for():
+    x = sc.inputs("tables")
+    got = {o: chain("tables", "p", o) for o in range(len(sc.AVERAGE_OPTIONS))}
+    with np.errstate(all="ignore"):
+        pct = 100.0 * (x["location_err"][:, None] / x["dist"])
+    assert np.isposinf(pct[0, 2]) and not got[0]["used"][0, 2] and not got[5]["used"][0, 2] and got[0]["used"][0].sum() == 5
+    assert np.isnan(pct[1]).all() and got[0]["used"][1].all() and got[7]["used"][1].all()      # not (NaN > max)
+    assert np.isnan(pct[2, 1]) and (np.delete(pct[2], 1) == 0).all() and got[7]["used"][2].all()
+    assert (got[0]["corrected"][2, 1] == 0).all()                                # a geometrical factor of 0
+    assert np.isposinf(got[0]["corrected"][3, 4]).all()                          # an attenuation factor of inf
+    assert (got[2]["mask"][3] & (got[2]["std"][3] == 0)).any()                   # an infinite mean: masked, std 0
+    negative = got[0]["corrected"][4] < 0
+    assert negative[0].all() and negative[3, ::2].all() and (got[0]["snr"][4][negative] > 0).all()
+    assert not same(got[0]["average"][4], got[2]["average"][4])                  # average_log masks them, the mean takes them
+    for o in (4, 5):                                                             # min_num_valid 3 on num_valid 2, 3, 4
+        assert got[o]["num_valid"][6, :3].tolist() == [2, 3, 4] and got[o]["mask"][6, :3].tolist() == [True, False, False]
+    assert not got[0]["mask"][6, :3].any()
+
+
+# ---- the stage-4 cases: recorded answers, what they reach, the restated definition, planted defects ----
+def finite_distance_events(name):
+    return np.isfinite(sc.stage4_inputs(name)["epi"]).all(axis=1)
+
+
+@pytest.mark.parametrize("name", sc.STAGE4_RECORDED)
+def test_stage_4_cases_equal_the_reference(golden, name):
+    """Bit for bit, for every event whose distances are finite.  With a NaN or inf distance a percentile is NaN, and
+    the definition (np.clip on arrays: NaN everywhere) stands alone: the reference clips a pandas Series, which takes
+    a NaN bound as no bound."""
+    x = sc.stage4_inputs(name)
+    finite = finite_distance_events(name)
+    assert finite.sum() >= len(finite) - 2
+    for o in range(len(sc.MW_OPTIONS)):
+        got = stage4_definition(name, o)
+        ran = ~golden[f"mwraised_{name}_{o}"] & finite
+        if sc.MW_OPTIONS[o][1] < 1e8:          # (an empty selection of bands: the reference's unused argmax raises)
+            assert ran[x["present"].any(axis=1) & finite].all()
+        assert same(got["Mw_star"][ran], golden[f"mw_{name}_{o}"][ran]), (name, o)
+        assert same(got["measurement_snr"][ran], golden[f"msnr_{name}_{o}"][ran]), (name, o)
+        assert same((got["weights"] > 0)[ran], (golden[f"rawweights_{name}_{o}"] > 0)[ran]), (name, o)
+
+
+def test_the_bands_case_reaches_every_count_of_averaging_bands():
+    """For every num_averaging_bands 1 .. 8: channels with more valid bands, with as many, and (from 3 on: there is no
+    whole number between 1 and 2) with fewer but more than one; and an answer that differs from that of one band
+    fewer.  The chosen bands are not a contiguous block and their values not sorted."""
+    x = sc.stage4_inputs("bands")
+    k = (x["snr"] > sc.THRESHOLD).sum(axis=-1)[x["present"]]
+    assert set(k.tolist()) == set(range(sc.BANDS_MAX + 1))
+    by_nab = {option[0]: stage4_definition("bands", o) for o, option in enumerate(sc.MW_OPTIONS) if option[1] < 1e8}
+    assert sorted(by_nab) == list(range(1, 9))
+    for nab in range(1, 9):
+        assert (k > nab).any() and (k == nab).any() and (nab < 3 or ((k > 1) & (k < nab)).any())
+        if nab > 1:
+            a, b = by_nab[nab]["measured_disp"], by_nab[nab - 1]["measured_disp"]
+            assert not same(a, b), nab
+            assert not same(by_nab[nab]["Mw_star"], by_nab[nab - 1]["Mw_star"]), nab
+    scattered = unsorted = 0
+    for e, s in zip(*np.nonzero(x["present"])):
+        valid = np.flatnonzero(x["snr"][e, s] > sc.THRESHOLD)[:8]
+        scattered += len(valid) > 1 and (np.diff(valid) > 1).any()
+        unsorted += len(valid) > 2 and (np.diff(x["corrected"][e, s, valid]) < 0).any()
+    assert scattered > 20 and unsorted > 20
+    # the four events with a property of their own
+    first = [np.flatnonzero(x["snr"][8, s] > sc.THRESHOLD)[:2] for s in range(1, 7)]
+    assert all(x["corrected"][8, s + 1, v[0]] == x["corrected"][8, s + 1, v[1]] for s, v in enumerate(first))
+    for nab in range(1, 9):
+        assert np.isnan(by_nab[nab]["measured_disp"][9, [0, 5]]).all() and np.isnan(by_nab[nab]["Mw_star"][9])
+        assert np.isnan(x["corrected"][10]).any() and not np.isnan(by_nab[nab]["measured_disp"][10]).any()
+        assert np.isfinite(by_nab[nab]["Mw_star"][10])
+        assert np.isposinf(by_nab[nab]["measured_disp"][11, 1])
+    # k = 3: +inf is the value, then half of a half-sum, then the last of three, not their median
+    assert np.isposinf(by_nab[1]["measured_disp"][11, 3]) and np.isposinf(by_nab[2]["measured_disp"][11, 3])
+    assert np.isfinite(by_nab[3]["measured_disp"][11, 3])
+
+
+def test_the_distance_cases_reach_both_lerp_branches_every_fraction_and_a_nan():
+    fractions = set()
+    for name in sc.STAGE4_CASES:
+        if not name.startswith("distances"):
+            continue
+        x = sc.stage4_inputs(name)
+        S = x["epi"].shape[1]
+        fractions |= {t for _, _, t in sc.percentile_ranks(S)}
+        events = dict(zip(sc.DISTANCE_EVENTS, range(len(sc.DISTANCE_EVENTS))))
+        epi = x["epi"]
+        with np.errstate(all="ignore"):
+            assert np.isnan(np.percentile(epi[events["nan"]], 25.0))
+        assert len(set(epi[events["distinct"]].tolist())) == S and len(set(epi[events["all_equal"]].tolist())) == 1
+        (lo, hi, _), _ = sc.percentile_ranks(S)
+        tied = np.sort(epi[events["tie_on_the_interpolated_ranks"]])
+        assert tied[lo] == tied[hi]
+        assert len(set(epi[events["tie_elsewhere"]].tolist())) == S - 1
+        assert (np.diff(epi[events["ascending"]]) > 0).all() and (np.diff(epi[events["descending"]]) < 0).all()
+        assert np.isposinf(epi[events["inf"]]).sum() == 1
+        assert (epi[events["zero"]] == 0).sum() == 1 and not np.signbit(epi[events["zero"]]).any()
+        assert (epi[events["minus_zero"]] == 0).sum() == 1 and np.signbit(epi[events["minus_zero"]]).sum() == 1
+        e = events["extremes_not_valid"]
+        assert not x["present"][e, np.argmin(epi[e])] and not x["present"][e, np.argmax(epi[e])]
+    assert fractions == {0.0, 0.25, 0.5, 0.75}                    # t < 0.5 and t >= 0.5: both sides of the lerp
+
+
+def straddled(result, present_channels):
+    """Events in which channels of one non-zero measurement SNR got both a zero and a positive weight."""
+    events = 0
+    for e in range(len(result["weights"])):
+        m, w = result["measurement_snr"][e][present_channels[e]], result["weights"][e][present_channels[e]]
+        events += any((w[m == v] == 0).any() and (w[m == v] > 0).any() for v in np.unique(m[m > 0]))
+    return events
+
+
+@pytest.mark.parametrize("name", [n for n in sc.STAGE4_CASES if n.startswith("snr_ties")])
+def test_a_tied_group_straddles_the_cut_for_each_max_bad(name):
+    """The cut `rank < n - max_bad` applies only when fewer than max_bad SNRs reach the threshold, and is empty from
+    max_bad = n on; max_bad = 0 zeroes everything below the threshold by the other rule.  So a tied group can
+    straddle the cut for 1 <= max_bad <= n - 1, and must, for 1, 6 and n - 1; for 0, n and n + 1 the weights are all
+    0, or all positive, whatever the order."""
+    x = sc.stage4_inputs(name)
+    C = max(sc.STAGE4_CASES[name][3], 1)
+    channels = np.repeat(x["present"], C, axis=1)
+    n_all = channels.shape[1]
+    assert n_all in (9, 20, 40) and (channels.sum(axis=1) < n_all).any()
+    for o, max_bad in sc.stage4_runs(name):
+        got = stage4_definition(name, o, max_bad)
+        assert (got["measurement_snr"][channels] > 0).all()
+        assert (got["measurement_snr"][channels] < np.float32(sc.THRESHOLD)).all()
+        n = channels.sum(axis=1)
+        positive = ((got["weights"] > 0) & channels).sum(axis=1)
+        assert np.array_equal(positive, np.minimum(n, max_bad))
+        if max_bad in (1, 6, n_all - 1):
+            assert straddled(got, channels) >= 1, (name, max_bad)
+        else:
+            assert max_bad in (0, n_all, n_all + 1) or max_bad >= n.min() - 1
+
+
+@pytest.mark.parametrize("name", list(sc.STAGE4_CASES))
+def test_the_restated_magnitude_is_the_definition_on_the_stage_4_cases(name):
+    F = sc.STAGE4_CASES[name][4]
+    for o, max_bad in sc.stage4_runs(name):
+        got, want = stage4_restated(name, o, max_bad), stage4_definition(name, o, max_bad)
+        assert all(same(got[k], want[k]) for k in want), (o, max_bad, [k for k in want if not same(got[k], want[k])])
+        assert gpu_check_of_stage_4(got, want, F)
+
+
+# (defect, case, index into MW_OPTIONS, max_num_bad_measurements)
+STAGE4_DEFECTS = [("ties_by_value", "distances_S4", 0, sc.MAX_BAD), ("ties_by_value", "distances_S9", 0, sc.MAX_BAD),
+                  ("nan_first", "distances_S5", 0, sc.MAX_BAD), ("nan_first", "distances_S9", 0, sc.MAX_BAD),
+                  ("percentiles_of_valid_at_3", "distances_S3", 0, sc.MAX_BAD),
+                  ("one_sided_lerp", "distances_S2", 0, sc.MAX_BAD), ("one_sided_lerp", "distances_S3", 0, sc.MAX_BAD),
+                  ("upper_middle_of_even", "bands", 4, sc.MAX_BAD), ("upper_middle_of_even", "bands", 6, sc.MAX_BAD),
+                  ("upper_middle_of_even", "bands", 8, sc.MAX_BAD),
+                  ("ties_last_index_first", "snr_ties_S9", 0, 6), ("ties_last_index_first", "snr_ties_S20", 0, 1),
+                  ("ties_last_index_first", "snr_ties_S20_C2", 0, 39)]
+
+
+@pytest.mark.parametrize("defect,name,o,max_bad", STAGE4_DEFECTS, ids=[f"{d[0]}-{d[1]}-{d[2]}-{d[3]}" for d in STAGE4_DEFECTS])
+def test_a_planted_defect_fails_the_gpu_check_on_the_stage_4_cases(defect, name, o, max_bad):
+    """The one-sided lerp a + diff t differs from NumPy's two-sided one by an ulp of a float64 bound, which the
+    float32 weights do not show; it shows where a distance is +inf: inf - inf 0.25 is NaN, a + inf 0.75 is inf."""
+    got, want = stage4_restated(name, o, max_bad, defect), stage4_definition(name, o, max_bad)
+    assert not gpu_check_of_stage_4(got, want, sc.STAGE4_CASES[name][4])
+
+
+def test_the_checks_demand_equal_bits_where_their_allowance_is_not_finite():
+    want = np.array([1.0, 2.0, np.nan, np.inf])
+    for allow in (np.inf, np.nan):
+        assert sc.worst_ratio(want, want, allow) == 0.0
+        assert sc.worst_ratio(np.array([1.0, np.nextafter(2.0, 3.0), np.nan, np.inf]), want, allow) == np.inf
+    mixed = np.array([1.0, np.inf, 0.0, 0.0])
+    assert sc.worst_ratio(np.array([1.5, 2.0, np.nan, np.inf]), want, mixed) == 0.5
+    assert sc.worst_ratio(np.array([1.5, 2.5, np.nan, np.inf]), want, mixed) == np.inf
+    assert sc.worst_ratio(np.array([1.0, 2.0, 0.0, np.inf]), want, 1.0) == np.inf        # the NaN pattern differs
+    assert sc.worst_ratio(np.array([1.0, 2.0, np.nan, -np.inf]), want, 1.0) == np.inf
 
 
 # ---- refusals and shapes that need no device ----
@@ -406,12 +679,15 @@ def test_the_c_entry_point_refuses_what_the_header_says():
     lib = _lib.lib()
     one = C.c_void_p(8)
 
-    def call(E=1, S=1, Cc=1, F=1, flags=8, bands=1, first=0, bad=6, valid=one):
-        return lib.bpmf_source_spectra_dev(None, None, valid, None, None, one, None, None, None, None, E, S, Cc, F,
-                                           flags, 0.0, 1.0, 8.0, 0.0, 0, 0, 0, bands, first, 1.0, 3.0, bad, None, one,
-                                           one, None, None, None, None, None, one, one, one, one, one)
+    def call(E=1, S=1, Cc=1, F=1, flags=8, bands=1, first=0, bad=6, valid=one, corrected=one, snr=one, signal=None):
+        return lib.bpmf_source_spectra_dev(signal, None, valid, None, None, one, None, None, None, None, E, S, Cc, F,
+                                           flags, 0.0, 1.0, 8.0, 0.0, 0, 0, 0, bands, first, 1.0, 3.0, bad, None,
+                                           corrected, snr, None, None, None, None, None, one, one, one, one, one)
     assert call(E=0) == 0
+    # (d_corrected and d_snr are needed by the stages that read or write them: 2, 4, 8 and 1, 4, 8)
     for kw in (dict(flags=0), dict(flags=16), dict(valid=None), dict(S=257), dict(S=43, Cc=6), dict(F=1025),
-               dict(bands=0), dict(bands=9), dict(first=2), dict(bad=-1), dict(flags=4), dict(E=2**31, F=2)):
+               dict(bands=0), dict(bands=9), dict(first=2), dict(bad=-1), dict(flags=4), dict(E=2**31, F=2),
+               dict(corrected=None), dict(snr=None), dict(flags=1, snr=None, signal=one),
+               dict(flags=2, corrected=None, signal=one)):
         assert call(**kw) == -1, kw
         assert b"bpmf_source_spectra_dev" in lib.bpmf_last_error()

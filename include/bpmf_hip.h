@@ -950,6 +950,58 @@ int bpmf_flag_multiples_dev(const double *d_t_sorted, const int32_t *d_rows_sort
                             double dt_criterion, void *d_workspace, size_t workspace_bytes,
                             bpmf_stream_t stream, uint8_t *d_unique_out);
 
+/* ------------------------------------------------------------------- pair geometry --- */
+/*
+ * Source-receiver distances, utils.compute_distances (BPMF/utils.py:1419-1498) with Vincenty's inverse on WGS84
+ * (|d lambda| < 1e-12, 200 iterations at most) in place of cartopy's geodesic (csrc/geometry.hip; host definition:
+ * seismic_bpmf_amd.postprocess.compute_distances_host).
+ *   d_sources (4, K) f64, d_receivers (4, R) f64: longitude (degrees), sin and cos of the reduced latitude
+ *     atan((1 - f) tan(latitude)), depth (km).  The receiver is the geodesic's first point.
+ *   d_epicentral (K, R) f32 or NULL: float32(metres / 1000).  d_metres (K, R) f64 or NULL: the geodesic's length.
+ *   d_hypocentral (K, R) f32: sqrt(epicentral^2 + (depth_source - depth_receiver)^2) -- depth_float64 == 0: all in
+ *     float32 (the depths must be float32 values); otherwise epicentral^2 in float32, the rest in float64, rounded
+ *     to float32 at the end: NumPy's promotion when any depth is float64.
+ *   d_nonconverged (1) i32: the pairs the iteration gave up on (within about 0.6 degrees of antipodal); they get
+ *     pi (a + b) / 2.  Zeroed by the call.
+ * No workspace, no host synchronisation; an element depends on its own pair alone.  Returns -1 for a NULL required
+ * pointer or K == 0 or R == 0, before any launch.
+ */
+int bpmf_geo_distances_dev(const double *d_sources, size_t K, const double *d_receivers, size_t R,
+                           int depth_float64, bpmf_stream_t stream, float *d_hypocentral, float *d_epicentral,
+                           double *d_metres, int32_t *d_nonconverged);
+
+/*
+ * The pair matrices of a TemplateGroup (BPMF/dataset.py:4568-4688), each (T, T) f32, every element written (host
+ * definition: seismic_bpmf_amd.postprocess.template_geometry_host):
+ *   d_intertemplate_dist[t, u]  as bpmf_geo_distances_dev gives it for source t and receiver u, float32 depths;
+ *   d_dir_errors[t, u]          float32(sqrt(3.52 |u^T C_t u|)), u = (X_u - X_t) / |X_u - X_t| (0 where u is at t), the
+ *                               sums over j, then i, in index order; 15.0 for a template without covariance;
+ *   d_ellipsoid_dist[t, u]      (dist[t, u] - dir_errors[t, u]) - dir_errors[u, t] in float32.
+ *   d_geo (4, T) f64: longitude, sin and cos of the reduced latitude, depth (km), of the float32 coordinates.
+ *   d_xyz (3, T) f64: the Cartesian coordinates of the directions (the reference: Mercator metres and depth in km).
+ *   d_cov (9, T) f64 or NULL: element (i, j) of template t at [(3 i + j) T + t]; NULL: no template has one.
+ *   d_has_cov (T) u8 or NULL (all have one).  d_nonconverged (1) i32 or NULL: as above.
+ * Returns -1 for a NULL required pointer or T == 0, before any launch.
+ */
+int bpmf_template_geometry_dev(const double *d_geo, const double *d_xyz, const double *d_cov,
+                               const uint8_t *d_has_cov, size_t T, bpmf_stream_t stream,
+                               float *d_intertemplate_dist, float *d_dir_errors, float *d_ellipsoid_dist,
+                               int32_t *d_nonconverged);
+
+/*
+ * The (T, T) u8 masks the catalogue stages read off ellipsoid_dist (T, T) f32; comparisons in float64.
+ *   BPMF_PAIR_MASK_MULTIPLES      mask[i, j] = ellipsoid_dist[i, j] < criterion, and with d_intertemplate_cc
+ *                                 (T, T) f32 not NULL: & (cc[i, j] >= similarity) -- postprocess.multiples_pair_mask;
+ *   BPMF_PAIR_MASK_INTERTEMPLATE  mask[i, j] = !(ellipsoid_dist[j, i] > criterion): the COLUMN the reference reads
+ *                                 (dataset.py:4815) -- postprocess.intertemplate_pair_mask; d_intertemplate_cc NULL.
+ * A NaN fails `<` and `>`: 0 in the first mode, 1 in the second.  Returns -1 for an unknown mode, a NULL required
+ * pointer or T == 0, before any launch.
+ */
+#define BPMF_PAIR_MASK_MULTIPLES 0
+#define BPMF_PAIR_MASK_INTERTEMPLATE 1
+int bpmf_pair_mask_dev(const float *d_ellipsoid_dist, const float *d_intertemplate_cc, size_t T, int mode,
+                       double criterion, double similarity, bpmf_stream_t stream, uint8_t *d_mask);
+
 /* ------------------------------------------------------------ running kurtosis --- */
 /*
  * Device version of BPMF.clib.kurtosis (BPMF/clib.py:86-102 -> BPMF/libc.c:11-53): kurto[ch][n],

@@ -110,6 +110,9 @@ SIGNATURES = {
                                           C.c_int, _vp] + [_vp] * 12),
     "bpmf_flag_multiples_workspace_bytes": (_sz, [_sz]),
     "bpmf_flag_multiples_dev": (C.c_int, [_vp, _vp, _vp, _sz, _vp, _sz, C.c_double, _vp, _sz, _vp, _vp]),
+    "bpmf_geo_distances_dev": (C.c_int, [_vp, _sz, _vp, _sz, C.c_int, _vp, _vp, _vp, _vp, _vp]),
+    "bpmf_template_geometry_dev": (C.c_int, [_vp, _vp, _vp, _vp, _sz, _vp, _vp, _vp, _vp, _vp]),
+    "bpmf_pair_mask_dev": (C.c_int, [_vp, _vp, _sz, C.c_int, C.c_double, C.c_double, _vp, _vp]),
     "bpmf_extract_candidates_mad_dev": (C.c_int, [_vp, _vp, _vp, _sz, _sz, _sz, _sz, C.c_uint32, _vp,
                                                   _vp, _vp]),
     "bpmf_row_median_mad_dev": (C.c_int, [_vp, _sz, _sz, C.c_int, _vp, _vp, _vp, _vp]),

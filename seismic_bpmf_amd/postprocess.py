@@ -1214,23 +1214,28 @@ def multiples_pair_mask(ellipsoid_dist, distance_criterion, intertemplate_cc=Non
     return np.ascontiguousarray(ok)
 
 
-def multiples_arguments(origin_time_sec, template_rows, cc, pair_ok):
+def multiples_arguments(origin_time_sec, template_rows, cc, pair_ok, n_templates=None):
     """The arguments of flag_multiples, checked and typed: (t float64 (n,), rows int32 (n,), cc float32 (n,),
     pair_ok bool (T, T)).  ValueError for mismatched lengths, a pair_ok that is not square, a row outside [0, T)
-    or a cc that is not finite (the keeper is the largest cc: a NaN has no order)."""
+    or a cc that is not finite (the keeper is the largest cc: a NaN has no order).  pair_ok=None with `n_templates`:
+    the mask lives elsewhere (on the device) and only its size is known; None comes back in its place."""
     t = np.ascontiguousarray(np.asarray(origin_time_sec, dtype=np.float64).reshape(-1))
     rows = np.asarray(template_rows).reshape(-1)
     if rows.size and not np.issubdtype(rows.dtype, np.integer):
         raise ValueError("flag_multiples: template_rows must be integers")
     c = np.ascontiguousarray(np.asarray(cc, dtype=np.float32).reshape(-1))
-    ok = np.asarray(pair_ok)
-    if ok.ndim != 2 or ok.shape[0] != ok.shape[1]:
-        raise ValueError(f"flag_multiples: pair_ok must be (T, T); got {ok.shape}")
-    ok = np.ascontiguousarray(ok.astype(bool))
+    if pair_ok is None and n_templates is not None:
+        ok, T = None, int(n_templates)
+    else:
+        ok = np.asarray(pair_ok)
+        if ok.ndim != 2 or ok.shape[0] != ok.shape[1]:
+            raise ValueError(f"flag_multiples: pair_ok must be (T, T); got {ok.shape}")
+        ok = np.ascontiguousarray(ok.astype(bool))
+        T = ok.shape[0]
     if not (t.shape == rows.shape == c.shape):
         raise ValueError("flag_multiples: origin_time_sec, template_rows and cc must have one entry per event")
-    if rows.size and (rows.min() < 0 or rows.max() >= ok.shape[0]):
-        raise ValueError(f"flag_multiples: a template row lies outside [0, {ok.shape[0]})")
+    if rows.size and (rows.min() < 0 or rows.max() >= T):
+        raise ValueError(f"flag_multiples: a template row lies outside [0, {T})")
     if not np.isfinite(c).all():
         raise ValueError("flag_multiples: cc must be finite")
     return t, np.ascontiguousarray(rows.astype(np.int32)), c, ok
@@ -1277,6 +1282,217 @@ def flag_multiples(origin_time_sec, template_rows, cc, pair_ok, dt_criterion):
     out = np.empty(n, dtype=bool)
     out[order] = unique
     return out
+
+
+# ---- pair geometry (BPMF/utils.py: compute_distances :1419-1498; BPMF/dataset.py: compute_intertemplate_dist,
+# ---- compute_dir_errors, compute_ellipsoid_dist :4568-4688, the weights of compute_intertemplate_cc :4787-4816) ----
+DIR_ERROR_CHI2_68_3DF = 3.52          # s_68_3df of compute_dir_errors
+DIR_ERROR_DEFAULT_KM = 15.0           # a template without cov_mat
+
+
+def _coordinates(name, lon, lat, dep):
+    """(lon, lat float64, dep as given) of one side of compute_distances, checked: 1-D, one length, finite, latitudes
+    within [-90, 90]."""
+    lon, lat, dep = (np.atleast_1d(np.asarray(x)) for x in (lon, lat, dep))
+    if not (lon.ndim == lat.ndim == dep.ndim == 1 and lon.shape == lat.shape == dep.shape):
+        raise ValueError(f"{name}: longitudes, latitudes and depths must be 1-D and of one length; got {lon.shape}, "
+                         f"{lat.shape}, {dep.shape}")
+    for what, x in (("longitudes", lon), ("latitudes", lat), ("depths", dep)):
+        if x.dtype.kind not in "fiu":
+            raise ValueError(f"{name}: {what} must be real numbers; got {x.dtype}")
+    lon, lat = lon.astype(np.float64), lat.astype(np.float64)
+    if dep.dtype != np.float32:
+        dep = dep.astype(np.float64)
+    if not (np.isfinite(lon).all() and np.isfinite(lat).all() and np.isfinite(dep).all()):
+        raise ValueError(f"{name}: coordinates must be finite")
+    if lat.size and (lat.min() < -90.0 or lat.max() > 90.0):
+        raise ValueError(f"{name}: latitudes must lie in [-90, 90]")
+    return lon, lat, dep
+
+
+def distances_arguments(src_lon, src_lat, src_dep, rcv_lon, rcv_lat, rcv_dep):
+    """The arguments of compute_distances_host, checked and typed: (source lon, lat, dep, receiver lon, lat, dep,
+    depth_float64).  Longitudes and latitudes are widened to float64 as given.  depth_float64 is False when both depth
+    arrays are float32 -- the hypocentral step then stays in float32, as NumPy's promotion has it in the reference --
+    and True otherwise (the depths are then float64)."""
+    s = _coordinates("compute_distances: sources", src_lon, src_lat, src_dep)
+    r = _coordinates("compute_distances: receivers", rcv_lon, rcv_lat, rcv_dep)
+    depth_float64 = not (s[2].dtype == np.float32 and r[2].dtype == np.float32)
+    if depth_float64:
+        s, r = (s[0], s[1], s[2].astype(np.float64)), (r[0], r[1], r[2].astype(np.float64))
+    return s + r + (depth_float64,)
+
+
+def hypocentral_from_metres(metres, src_dep, rcv_dep):
+    """The two rounding steps of utils.compute_distances behind its geodesic call, on (K, R) float64 `metres`:
+    epicentral = float32(metres / 1000.0); hypocentral = sqrt(epicentral ** 2 + (src_dep - rcv_dep[s]) ** 2) column by
+    column in NumPy's promoted dtype -- float32 throughout for float32 depths, float64 from the sum on for float64
+    depths -- stored as float32.  Returns (hypocentral, epicentral)."""
+    metres = np.asarray(metres, dtype=np.float64)
+    epicentral = np.zeros(metres.shape, dtype=np.float32)
+    hypocentral = np.zeros(metres.shape, dtype=np.float32)
+    for s in range(metres.shape[1]):
+        epicentral[:, s] = metres[:, s] / 1000.0
+        hypocentral[:, s] = np.sqrt(epicentral[:, s] ** 2 + (src_dep - rcv_dep[s]) ** 2)
+    return hypocentral, epicentral
+
+
+def compute_distances_host(src_lon, src_lat, src_dep, rcv_lon, rcv_lat, rcv_dep, return_epicentral_distances=False,
+                           nonconverged="raise"):
+    """utils.compute_distances (BPMF/utils.py:1419-1498) with geodesic_distance_m in place of
+    ``cartopy.geodesic.Geodesic().inverse``: (K, R) float32 hypocentral distances in km between K sources and R
+    receivers, and with `return_epicentral_distances` the (K, R) float32 epicentral distances as well.  Degrees and
+    km in.  As in the reference the RECEIVER is the geodesic's first point, and the roundings are its own
+    (hypocentral_from_metres).  `nonconverged`: what a nearly antipodal pair does (geodesic_distance_m).  This is the
+    definition workflow.compute_distances (csrc/geometry.hip) is tested against."""
+    slon, slat, sdep, rlon, rlat, rdep, _ = distances_arguments(src_lon, src_lat, src_dep, rcv_lon, rcv_lat, rcv_dep)
+    if nonconverged not in ("raise", "antipodal"):
+        raise ValueError("nonconverged must be 'raise' or 'antipodal'")
+    metres = np.zeros((slon.shape[0], rlon.shape[0]), dtype=np.float64)
+    for s in range(rlon.shape[0]):
+        if slon.shape[0]:
+            metres[:, s] = geodesic_distance_m(rlon[s], rlat[s], slon, slat, nonconverged=nonconverged)
+    hypocentral, epicentral = hypocentral_from_metres(metres, sdep, rdep)
+    return (hypocentral, epicentral) if return_epicentral_distances else hypocentral
+
+
+def mercator_xy(lon, lat, central_longitude, a=WGS84_A, f=WGS84_F):
+    """Ellipsoidal Mercator with k_0 = 1 (PROJ's `merc`, Snyder 1987 eq. 7-6 / 7-7), the projection
+    ``cartopy.crs.Mercator(central_longitude, min_latitude, max_latitude)`` selects -- its two latitude arguments only
+    set the map's bounds:  x = a dlon, dlon = lon - central_longitude wrapped to [-180, 180] degrees, in radians;
+    y = a (asinh(tan phi) - e atanh(e sin phi)), e^2 = f (2 - f).  Degrees in, metres out (float64); a pole gives an
+    infinite y.  Restated from the documentation of PROJ and Snyder's worked example, NOT verified against cartopy
+    itself (tests/test_template_geometry_cartopy_live.py does that where cartopy is installed)."""
+    lon = np.asarray(lon, dtype=np.float64)
+    lat = np.asarray(lat, dtype=np.float64)
+    e = np.sqrt(f * (2.0 - f))
+    dlon = lon - np.float64(central_longitude)
+    dlon = np.where(np.abs(dlon) > 180.0, (dlon + 180.0) % 360.0 - 180.0, dlon)
+    phi = np.deg2rad(lat)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        y = a * (np.arcsinh(np.tan(phi)) - e * np.arctanh(e * np.sin(phi)))
+    y = np.where(np.abs(lat) == 90.0, np.copysign(np.inf, lat), y)
+    return a * np.deg2rad(dlon), y
+
+
+def template_geometry_arguments(longitude, latitude, depth, cov_mat=None, has_cov=None, depth_unit="reference"):
+    """The arguments of template_geometry_host, checked and typed as the reference types them: (lon, lat, dep float32
+    (T,), xyz float64 (T, 3), cov float64 (T, 3, 3) or None, has_cov bool (T,)).  xyz: Mercator x, y in metres about
+    the mean of the float32 longitudes, and the depth -- in km ("reference") or in metres ("metres")."""
+    if depth_unit not in ("reference", "metres"):
+        raise ValueError("template_geometry: depth_unit must be 'reference' or 'metres'")
+    lon, lat, dep = _coordinates("template_geometry", longitude, latitude, depth)
+    T = lon.shape[0]
+    if T == 0:
+        raise ValueError("template_geometry: no template")
+    lon, lat, dep = np.float32(lon), np.float32(lat), np.float32(dep)
+    if not np.isfinite(dep).all():
+        raise ValueError("template_geometry: coordinates must be finite")
+    cov = None
+    if cov_mat is not None:
+        cov = np.asarray(cov_mat, dtype=np.float64)
+        if cov.shape != (T, 3, 3):
+            raise ValueError(f"template_geometry: cov_mat must be ({T}, 3, 3); got {cov.shape}")
+        cov = np.ascontiguousarray(cov)
+    if has_cov is None:
+        has = np.full(T, cov is not None)
+    else:
+        has = np.asarray(has_cov)
+        if has.shape != (T,):
+            raise ValueError(f"template_geometry: has_cov must be ({T},); got {has.shape}")
+        has = has.astype(bool)
+        if has.any() and cov is None:
+            raise ValueError("template_geometry: has_cov names templates but cov_mat is None")
+    if cov is not None and not np.isfinite(cov[has]).all():
+        raise ValueError("template_geometry: cov_mat must be finite where has_cov is set")
+    x, y = mercator_xy(lon, lat, np.mean(lon))
+    z = dep.astype(np.float64) * 1000.0 if depth_unit == "metres" else dep.astype(np.float64)
+    return lon, lat, dep, np.stack([x, y, z], axis=1), cov, has
+
+
+def dir_errors_host(xyz, cov, has_cov):
+    """compute_dir_errors (BPMF/dataset.py:4639-4660) behind its projection: (T, T) float32, row t the length of
+    template t's uncertainty ellipsoid towards every template.  Per pair in float64: d = X[u] - X[t];
+    n = sqrt((dx^2 + dy^2) + dz^2); d / n with NaN (u at t) replaced by 0; cov_dir = |sum_i (sum_j C_ij u_j) u_i| with
+    j, then i, summed in index order, unfused (the reference's BLAS leaves that order open);
+    float32(sqrt(3.52 cov_dir)).  A row without covariance is 15.0."""
+    T = xyz.shape[0]
+    out = np.zeros((T, T), dtype=np.float32)
+    for t in range(T):
+        if not has_cov[t]:
+            out[t, :] = DIR_ERROR_DEFAULT_KM
+            continue
+        d = xyz - xyz[t, :]
+        n = np.sqrt((d[:, 0] * d[:, 0] + d[:, 1] * d[:, 1]) + d[:, 2] * d[:, 2])
+        with np.errstate(divide="ignore", invalid="ignore"):
+            u = d / n[:, np.newaxis]
+        u[np.isnan(u)] = 0.0
+        c = cov[t]
+        rows = [(c[i, 0] * u[:, 0] + c[i, 1] * u[:, 1]) + c[i, 2] * u[:, 2] for i in range(3)]
+        cov_dir = np.abs((rows[0] * u[:, 0] + rows[1] * u[:, 1]) + rows[2] * u[:, 2])
+        out[t, :] = np.sqrt(DIR_ERROR_CHI2_68_3DF * cov_dir)
+    return out
+
+
+def template_geometry_host(longitude, latitude, depth, cov_mat=None, has_cov=None, depth_unit="reference"):
+    """The pair matrices of a TemplateGroup (BPMF/dataset.py:4568-4688) without cartopy: a dict of
+    `intertemplate_dist`, `dir_errors` and `ellipsoid_dist`, each (T, T) float32 in km.
+
+    The coordinates are cast to float32 first, as the reference does.  intertemplate_dist =
+    compute_distances_host(templates, templates) (a nearly antipodal pair gets pi (a + b) / 2);  dir_errors =
+    dir_errors_host on the Mercator coordinates about central_longitude = np.mean of the float32 longitudes
+    (mercator_xy: restated from the documentation, not verified against cartopy);  ellipsoid_dist =
+    (intertemplate_dist - dir_errors) - dir_errors.T in float32.  `cov_mat` (T, 3, 3), `has_cov` (T,) bool (default:
+    every template has one if cov_mat is given, none otherwise).
+
+    Kept as the reference has it: the direction's X and Y are Mercator METRES (stretched by 1 / cos(latitude)) while Z
+    is the depth in KILOMETRES, so every direction is nearly horizontal and dir_errors is essentially the horizontal
+    extent of the ellipsoid.  depth_unit="metres" multiplies the depths by 1000 before the directions are formed: the
+    consistent alternative, which the reference does not compute."""
+    lon, lat, dep, xyz, cov, has = template_geometry_arguments(longitude, latitude, depth, cov_mat, has_cov, depth_unit)
+    dist = compute_distances_host(lon, lat, dep, lon, lat, dep, nonconverged="antipodal")
+    err = dir_errors_host(xyz, cov, has)
+    return {"intertemplate_dist": dist, "dir_errors": err, "ellipsoid_dist": (dist - err) - err.T}
+
+
+def intertemplate_pair_mask(ellipsoid_dist, distance_threshold):
+    """The pairs compute_intertemplate_cc correlates (BPMF/dataset.py:4815-4816): mask[t, u] =
+    not (ellipsoid_dist[u, t] > distance_threshold).  The reference reads COLUMN tids[t] of its frame, and the matrix is
+    not bitwise symmetric; a NaN is not above the threshold and stays in.  (T, T) in, (T, T) bool out."""
+    dist = np.asarray(ellipsoid_dist)
+    if dist.ndim != 2 or dist.shape[0] != dist.shape[1]:
+        raise ValueError(f"intertemplate_pair_mask: ellipsoid_dist must be (T, T); got {dist.shape}")
+    return np.ascontiguousarray(~(dist.T > distance_threshold))
+
+
+def intertemplate_station_weights(source_receiver_dist, availability, availability_per_cha, n_stations):
+    """The channel weights of compute_intertemplate_cc (BPMF/dataset.py:4787-4814), (T, S, C) float32: per template the
+    `n_stations` closest AVAILABLE stations -- filled up, when fewer are available, with the closest of the others --
+    carry their per-channel availabilities as 0 / 1, and the whole is divided by its sum (no channel at all: 0 / 0,
+    NaN, as the reference).  `source_receiver_dist` (T, S), `availability` (T, S) bool, `availability_per_cha`
+    (T, S, C) bool.  Sorting is stable (equal distances: station order), where pandas' quicksort leaves ties to the
+    platform; NaN distances sort last."""
+    dist = np.asarray(source_receiver_dist)
+    avail = np.asarray(availability).astype(bool)
+    per_cha = np.asarray(availability_per_cha).astype(bool)
+    if dist.ndim != 2 or avail.shape != dist.shape or per_cha.ndim != 3 or per_cha.shape[:2] != dist.shape:
+        raise ValueError("intertemplate_station_weights: source_receiver_dist and availability must be (T, S) and "
+                         f"availability_per_cha (T, S, C); got {dist.shape}, {avail.shape}, {per_cha.shape}")
+    n_stations = int(n_stations)
+    if n_stations < 0:
+        raise ValueError("intertemplate_station_weights: n_stations must not be negative")
+    T, S, C = per_cha.shape
+    weights = np.zeros((T, S, C), dtype=np.float32)
+    for t in range(T):
+        pool = np.flatnonzero(avail[t])
+        closest = pool[np.argsort(dist[t, pool], kind="stable")][:n_stations]
+        if len(closest) < n_stations:
+            others = np.setdiff1d(np.arange(S), closest)
+            closest = np.hstack((closest, others[np.argsort(dist[t, others], kind="stable")][:n_stations - len(closest)]))
+        weights[t, closest, :] = np.int32(per_cha[t, closest, :])
+    with np.errstate(divide="ignore", invalid="ignore"):
+        weights /= np.sum(weights, axis=(1, 2), keepdims=True)
+    return weights
 
 
 # ---- SVD-Wiener stack of a template's detections (BPMF/utils.py: bandpass_filter :24-90, SVDWF :667-772;

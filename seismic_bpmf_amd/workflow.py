@@ -1354,7 +1354,8 @@ def flag_multiples(origin_time_sec, template_rows, cc, pair_ok, dt_criterion=4.0
     (bpmf_flag_multiples_dev, csrc/multiples.hip): which events stay `unique_event` when several templates detect the
     same event.  Arguments and result as postprocess.flag_multiples, the host definition it equals element for element:
     `origin_time_sec` (n,) float64, `template_rows` (n,) rows of `pair_ok`, `cc` (n,) float32 and finite, `pair_ok`
-    (T, T) bool (postprocess.multiples_pair_mask); returns an (n,) bool NumPy array in the order of the input.
+    (T, T) bool (postprocess.multiples_pair_mask) -- or a (T, T) uint8 / bool tensor on the GPU (template_pair_masks),
+    which is read where it lies; returns an (n,) bool NumPy array in the order of the input.
 
     The events are visited in the stable order of their origin times (np.argsort(kind="stable"): equal times keep the
     input order, where the reference's pandas quicksort leaves the order to the platform).  One call of the library,
@@ -1364,8 +1365,17 @@ def flag_multiples(origin_time_sec, template_rows, cc, pair_ok, dt_criterion=4.0
     import ctypes as C
     import torch
     from . import _lib
-    t, rows, c, ok = pp.multiples_arguments(origin_time_sec, template_rows, cc, pair_ok)
-    n, T = t.shape[0], ok.shape[0]
+    d_ok = None
+    if isinstance(pair_ok, torch.Tensor):      # a device mask (template_pair_masks) is used where it lies
+        d_ok = _device_pair_mask("flag_multiples", "pair_ok", pair_ok)
+        t, rows, c, ok = pp.multiples_arguments(origin_time_sec, template_rows, cc, None, n_templates=d_ok.shape[0])
+        n, T = t.shape[0], d_ok.shape[0]
+        if device is not None and _cuda_device("flag_multiples", device, "postprocess.flag_multiples") != d_ok.device:
+            raise ValueError(f"flag_multiples: pair_ok lies on {d_ok.device}, not on {device}")
+        device = d_ok.device
+    else:
+        t, rows, c, ok = pp.multiples_arguments(origin_time_sec, template_rows, cc, pair_ok)
+        n, T = t.shape[0], ok.shape[0]
     dev = torch.device("cuda" if device is None else device)
     if dev.type != "cuda":
         raise ValueError("flag_multiples: no CPU implementation here (the host mirror is postprocess.flag_multiples)")
@@ -1383,7 +1393,8 @@ def flag_multiples(origin_time_sec, template_rows, cc, pair_ok, dt_criterion=4.0
     d_t = torch.as_tensor(t[order], device=dev)
     d_rows = torch.as_tensor(rows[order], device=dev)
     d_cc = torch.as_tensor(c[order], device=dev)
-    d_ok = torch.as_tensor(ok.view(np.uint8), device=dev)
+    if d_ok is None:
+        d_ok = torch.as_tensor(ok.view(np.uint8), device=dev)
     ws = torch.empty(lib.bpmf_flag_multiples_workspace_bytes(n), dtype=torch.uint8, device=dev)
     flags = torch.empty(n, dtype=torch.uint8, device=dev) if out is None else out
     with torch.cuda.device(dev):
@@ -1396,6 +1407,189 @@ def flag_multiples(origin_time_sec, template_rows, cc, pair_ok, dt_criterion=4.0
     unique = np.empty(n, dtype=bool)
     unique[order] = flags.cpu().numpy().astype(bool)
     return unique
+
+
+# ------------------------------------------------------------------ pair geometry (csrc/geometry.hip) ---
+def _cuda_device(name, device, definition):
+    """The torch device of `device` (None: the current GPU); ValueError for anything that is not a GPU."""
+    import torch
+    dev = torch.device("cuda" if device is None else device)
+    if dev.type != "cuda":
+        raise ValueError(f"{name}: no CPU implementation here (the host definition is {definition})")
+    if dev.index is None:
+        dev = torch.device("cuda", torch.cuda.current_device())
+    return dev
+
+
+def _device_pair_mask(name, what, mask):
+    """A (T, T) mask that already lies on a GPU, as the uint8 tensor the kernels read."""
+    import torch
+    if not mask.is_cuda or mask.dtype not in (torch.uint8, torch.bool) or mask.dim() != 2 or \
+            mask.shape[0] != mask.shape[1] or mask.shape[0] == 0 or not mask.is_contiguous():
+        raise ValueError(f"{name}: a tensor {what} must be a contiguous (T, T) uint8 or bool tensor on a GPU")
+    return mask.view(torch.uint8)
+
+
+def _geo_table(lon, lat, dep):
+    """(4, n) float64: longitude, sin and cos of the reduced latitude, depth -- what the kernels read per point."""
+    su, cu = pp.reduced_latitude_sin_cos(lat)
+    return np.ascontiguousarray(np.stack([lon, su, cu, dep.astype(np.float64)]))
+
+
+def compute_distances(src_lon, src_lat, src_dep, rcv_lon, rcv_lat, rcv_dep, return_epicentral_distances=False,
+                      nonconverged="raise", device=None, *, return_metres=False, count_out=None):
+    """utils.compute_distances (BPMF/utils.py:1419-1498) on the device (bpmf_geo_distances_dev, csrc/geometry.hip):
+    the (K, R) float32 hypocentral distances in km between K sources and R receivers as a tensor on the GPU, and with
+    `return_epicentral_distances` a tuple with the (K, R) float32 epicentral distances as well (`return_metres`: and
+    the geodesic's float64 metres).  Arguments as postprocess.compute_distances_host, the definition: Vincenty's
+    inverse on WGS84 in place of cartopy, the reference's roundings, float32 throughout when both depth arrays are
+    float32.  The float32 results are the definition's two rounding steps applied to the device's own metres, which
+    lie within a few ulp of the host's.
+
+    nonconverged="raise" reads the 4-byte count of pairs the iteration gave up on (nearly antipodal points) and raises
+    ValueError if there is any; "antipodal" gives them pi (a + b) / 2 and does not synchronise.  `count_out`: an
+    optional int32 tensor of one element on the GPU that receives the count."""
+    import ctypes as C
+    import torch
+    from . import _lib
+    slon, slat, sdep, rlon, rlat, rdep, depth_f64 = pp.distances_arguments(src_lon, src_lat, src_dep, rcv_lon,
+                                                                           rcv_lat, rcv_dep)
+    if nonconverged not in ("raise", "antipodal"):
+        raise ValueError("nonconverged must be 'raise' or 'antipodal'")
+    dev = _cuda_device("compute_distances", device, "postprocess.compute_distances_host")
+    K, R = slon.shape[0], rlon.shape[0]
+    if count_out is not None and (not isinstance(count_out, torch.Tensor) or count_out.dtype != torch.int32 or
+                                  count_out.numel() != 1 or count_out.device != dev):
+        raise ValueError(f"compute_distances: count_out must be an int32 tensor of one element on {dev}")
+    hypo = torch.empty((K, R), dtype=torch.float32, device=dev)
+    epi = torch.empty((K, R), dtype=torch.float32, device=dev) if return_epicentral_distances else None
+    metres = torch.empty((K, R), dtype=torch.float64, device=dev) if return_metres else None
+    if K and R:
+        d_src = torch.as_tensor(_geo_table(slon, slat, sdep), device=dev)
+        d_rcv = torch.as_tensor(_geo_table(rlon, rlat, rdep), device=dev)
+        count = torch.empty(1, dtype=torch.int32, device=dev) if count_out is None else count_out
+        with torch.cuda.device(dev):
+            rc = _lib.lib().bpmf_geo_distances_dev(
+                C.c_void_p(d_src.data_ptr()), K, C.c_void_p(d_rcv.data_ptr()), R, 1 if depth_f64 else 0,
+                C.c_void_p(torch.cuda.current_stream(dev).cuda_stream), C.c_void_p(hypo.data_ptr()),
+                C.c_void_p(epi.data_ptr() if epi is not None else None),
+                C.c_void_p(metres.data_ptr() if metres is not None else None), C.c_void_p(count.data_ptr()))
+        _lib.check(rc, "bpmf_geo_distances_dev")
+        if nonconverged == "raise":
+            n_bad = int(count.item())
+            if n_bad:
+                raise ValueError(f"compute_distances: no convergence for {n_bad} pair(s) (nearly antipodal points)")
+    elif count_out is not None:
+        count_out.zero_()
+    out = (hypo,) + ((epi,) if epi is not None else ()) + ((metres,) if metres is not None else ())
+    return out if len(out) > 1 else hypo
+
+
+def template_geometry(longitude, latitude, depth, cov_mat=None, has_cov=None, depth_unit="reference", device=None):
+    """The pair matrices of a TemplateGroup (BPMF/dataset.py:4568-4688) on the device (bpmf_template_geometry_dev,
+    csrc/geometry.hip): a dict of `intertemplate_dist`, `dir_errors` and `ellipsoid_dist`, (T, T) float32 tensors on
+    the GPU.  Arguments as postprocess.template_geometry_host, the definition, whose docstring states what is kept
+    as the reference has it (Mercator metres beside depths in km; depth_unit="metres" is the alternative) and that
+    the Mercator projection is restated from its documentation, not verified against cartopy.  The host projects the T
+    points and uploads them; the T^2 pairs are the kernel's.  dir_errors equals the definition bit for bit, the
+    distances are its roundings of the device's own geodesic, and ellipsoid_dist is the float32
+    (dist - dir_errors) - dir_errors.T of the device's matrices.  No synchronisation."""
+    import ctypes as C
+    import torch
+    from . import _lib
+    lon, lat, dep, xyz, cov, has = pp.template_geometry_arguments(longitude, latitude, depth, cov_mat, has_cov,
+                                                                  depth_unit)
+    dev = _cuda_device("template_geometry", device, "postprocess.template_geometry_host")
+    T = lon.shape[0]
+    d_geo = torch.as_tensor(_geo_table(lon.astype(np.float64), lat.astype(np.float64), dep), device=dev)
+    d_xyz = torch.as_tensor(np.ascontiguousarray(xyz.T), device=dev)
+    d_cov = d_has = None
+    if cov is not None and has.any():
+        # rows without a covariance are never read as numbers: they are zeroed so that nothing non-finite travels
+        d_cov = torch.as_tensor(np.ascontiguousarray(np.where(has[:, None, None], cov, 0.0).reshape(T, 9).T), device=dev)
+        d_has = torch.as_tensor(has.view(np.uint8), device=dev)
+    out = {k: torch.empty((T, T), dtype=torch.float32, device=dev)
+           for k in ("intertemplate_dist", "dir_errors", "ellipsoid_dist")}
+    with torch.cuda.device(dev):
+        rc = _lib.lib().bpmf_template_geometry_dev(
+            C.c_void_p(d_geo.data_ptr()), C.c_void_p(d_xyz.data_ptr()),
+            C.c_void_p(d_cov.data_ptr() if d_cov is not None else None),
+            C.c_void_p(d_has.data_ptr() if d_has is not None else None), T,
+            C.c_void_p(torch.cuda.current_stream(dev).cuda_stream), C.c_void_p(out["intertemplate_dist"].data_ptr()),
+            C.c_void_p(out["dir_errors"].data_ptr()), C.c_void_p(out["ellipsoid_dist"].data_ptr()), C.c_void_p(None))
+    _lib.check(rc, "bpmf_template_geometry_dev")
+    return out
+
+
+def _float32_comparand(value):
+    """The float64 against which a float32 matrix is compared so that the result is NumPy's for `matrix < value`: a
+    Python number is weak and compares as float32, a NumPy scalar keeps its own type."""
+    if isinstance(value, np.generic):
+        return float(value)
+    with np.errstate(over="ignore"):
+        return float(np.float32(value))
+
+
+def template_pair_masks(ellipsoid_dist, *, distance_criterion=None, intertemplate_cc=None, similarity_criterion=-1.0,
+                        distance_threshold=None, device=None):
+    """The (T, T) masks the catalogue stages read off `ellipsoid_dist`, as uint8 tensors on the GPU
+    (bpmf_pair_mask_dev, csrc/geometry.hip), in a dict:
+      "pair_ok"    with `distance_criterion`: postprocess.multiples_pair_mask -- ellipsoid_dist < distance_criterion,
+                   and only when similarity_criterion > -1 also intertemplate_cc >= similarity_criterion -- what
+                   flag_multiples takes;
+      "pair_mask"  with `distance_threshold`: postprocess.intertemplate_pair_mask -- not (ellipsoid_dist[u, t] >
+                   distance_threshold), the column the reference reads -- what intertemplate_cc takes.
+    `ellipsoid_dist` (and `intertemplate_cc`): (T, T) float32, the GPU tensor of template_geometry as it is, or a host
+    array, which is uploaded.  The comparisons are NumPy's on float32 matrices (a NaN fails both: 0 in pair_ok, 1 in
+    pair_mask).  No synchronisation."""
+    import ctypes as C
+    import torch
+    from . import _lib
+    if distance_criterion is None and distance_threshold is None:
+        raise ValueError("template_pair_masks: give distance_criterion (pair_ok), distance_threshold (pair_mask) or both")
+    want_sim = distance_criterion is not None and similarity_criterion > -1.0
+    if want_sim and intertemplate_cc is None:
+        raise ValueError("template_pair_masks: similarity_criterion > -1 needs intertemplate_cc")
+
+    def square(name, x, shape=None):
+        if isinstance(x, torch.Tensor):
+            if x.dtype != torch.float32 or x.dim() != 2 or x.shape[0] != x.shape[1] or not x.is_cuda:
+                raise ValueError(f"template_pair_masks: a tensor {name} must be (T, T) float32 on a GPU")
+        else:
+            x = np.asarray(x)
+            if x.dtype != np.float32 or x.ndim != 2 or x.shape[0] != x.shape[1]:
+                raise ValueError(f"template_pair_masks: {name} must be (T, T) float32; got {x.dtype} {x.shape}")
+        if x.shape[0] == 0 or (shape is not None and tuple(x.shape) != tuple(shape)):
+            raise ValueError(f"template_pair_masks: {name} has shape {tuple(x.shape)}")
+        return x
+
+    ell = square("ellipsoid_dist", ellipsoid_dist)
+    sim = square("intertemplate_cc", intertemplate_cc, ell.shape) if want_sim else None
+    if device is None and isinstance(ell, torch.Tensor):
+        device = ell.device
+    dev = _cuda_device("template_pair_masks", device, "postprocess.multiples_pair_mask / intertemplate_pair_mask")
+    for name, x in (("ellipsoid_dist", ell), ("intertemplate_cc", sim)):
+        if isinstance(x, torch.Tensor) and x.device != dev:
+            raise ValueError(f"template_pair_masks: {name} lies on {x.device}, not on {dev}")
+    d_ell = torch.as_tensor(ell, device=dev).contiguous()
+    d_sim = torch.as_tensor(sim, device=dev).contiguous() if sim is not None else None
+    T = d_ell.shape[0]
+    jobs = []
+    if distance_criterion is not None:
+        jobs.append(("pair_ok", 0, distance_criterion, d_sim, similarity_criterion if want_sim else -1.0))
+    if distance_threshold is not None:
+        jobs.append(("pair_mask", 1, distance_threshold, None, -1.0))
+    out = {}
+    for key, mode, criterion, cc, similarity in jobs:
+        mask = torch.empty((T, T), dtype=torch.uint8, device=dev)
+        with torch.cuda.device(dev):
+            rc = _lib.lib().bpmf_pair_mask_dev(
+                C.c_void_p(d_ell.data_ptr()), C.c_void_p(cc.data_ptr() if cc is not None else None), T, mode,
+                _float32_comparand(criterion), _float32_comparand(similarity),
+                C.c_void_p(torch.cuda.current_stream(dev).cuda_stream), C.c_void_p(mask.data_ptr()))
+        _lib.check(rc, "bpmf_pair_mask_dev")
+        out[key] = mask
+    return out
 
 
 def _detections_events(detections, *, sr, step, t0_sec):
@@ -2078,7 +2272,7 @@ def intertemplate_cc(waveforms_arr, weights, max_lag=10, device=None, pair_mask=
 
     waveforms_arr (T,S,C,L).  weights: (T, S, C) with pair_mask (T, T) -- row t's channel weights and
     the pairs within the distance threshold, the factors the reference multiplies together
-    (dataset.py:4789-4816) -- or the full (T, T, S, C) array / a callable t -> (T, S, C).  Factorised
+    (dataset.py:4789-4816; pair_mask may be the uint8 / bool GPU tensor of template_pair_masks, read where it lies) -- or the full (T, T, S, C) array / a callable t -> (T, S, C).  Factorised
     weights (given, or recognised in a full array) run as ONE batched launch
     (bpmf_intertemplate_cc_dev); anything else -- weights that do not factorise, more than 63 lags, a channel too long
     for the kernel's LDS budget (intertp_batched_fits, decided here before anything is launched) -- takes the
@@ -2090,18 +2284,29 @@ def intertemplate_cc(waveforms_arr, weights, max_lag=10, device=None, pair_mask=
     if not callable(weights) and intertp_batched_fits(shape[1] * shape[2], shape[3], max_lag):
         w = np.asarray(weights, dtype=np.float32)
         fact = None
-        if w.ndim == 3:
+        d_mask = None
+        if w.ndim == 3 and isinstance(pair_mask, torch.Tensor):      # a device mask (template_pair_masks), as it is
+            d_mask = _device_pair_mask("intertemplate_cc", "pair_mask", pair_mask)
+            if d_mask.shape[0] != w.shape[0]:
+                raise ValueError(f"intertemplate_cc: pair_mask must be ({w.shape[0]}, {w.shape[0]})")
+            fact = (w, None)
+        elif w.ndim == 3:
             T = w.shape[0]
             fact = (w, np.ones((T, T), bool) if pair_mask is None else np.asarray(pair_mask, dtype=bool))
         elif w.ndim == 4 and pair_mask is None:
             fact = factorise_pair_weights(w)
         if fact is not None:
             base, mask = fact
-            mf = MatchedFilterGPU(device=device)
+            mf = MatchedFilterGPU(device=d_mask.device.index if d_mask is not None and device is None else device)
             wf = mf._dev(np.ascontiguousarray(waveforms_arr, dtype=np.float32), torch.float32)
             T, S, Cc, Lw = wf.shape
             base_d = mf._dev(np.ascontiguousarray(base, dtype=np.float32), torch.float32)
-            mask_d = torch.as_tensor(np.ascontiguousarray(mask, dtype=np.uint8), device=wf.device)
+            if d_mask is not None:
+                if d_mask.device != wf.device:
+                    raise ValueError(f"intertemplate_cc: pair_mask lies on {d_mask.device}, not on {wf.device}")
+                mask_d = d_mask
+            else:
+                mask_d = torch.as_tensor(np.ascontiguousarray(mask, dtype=np.uint8), device=wf.device)
             lib = mf.lib
             ws = torch.empty(lib.bpmf_intertemplate_workspace_bytes(T, S, Cc, max_lag), dtype=torch.uint8,
                              device=wf.device)
@@ -2116,6 +2321,8 @@ def intertemplate_cc(waveforms_arr, weights, max_lag=10, device=None, pair_mask=
             _lib.check(rc, "bpmf_intertemplate_cc_dev")
             o = out.cpu().numpy()
             return (o + o.T) / 2.0 if symmetrise else o
+    if isinstance(pair_mask, torch.Tensor):                  # (the loop below is driven from the host)
+        pair_mask = pair_mask.cpu().numpy()
     if not callable(weights) and np.ndim(weights) == 3:     # factorised weights the batched kernel does not take
         w = np.asarray(weights, dtype=np.float32)
         T = w.shape[0]

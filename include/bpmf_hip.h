@@ -340,6 +340,10 @@ size_t bpmf_bp_workspace_bytes(const bpmf_bp_plan *plan, size_t N, size_t C);
 int bpmf_bp_launch_info(const int32_t *moveouts, const float *w_sources, size_t K, size_t S, size_t P,
                         size_t N, int reduce, size_t n_events, int64_t *out);
 
+/* Non-finite features (DESIGN.md s4 "Non-finite features"): a beam is NaN / +-Inf exactly as IEEE makes the oracle's
+ * sum (a zero-weight station, a dropped flexible term and a strict beam that is not computed cost nothing); under
+ * reduce max a NaN beam is never the maximum, +Inf is (lowest source id), -Inf never beats the (0, id_offset) floor
+ * and d_beam_out is never NaN. */
 int bpmf_bp_run_dev(const bpmf_bp_plan *plan, const float *d_features,
                     const float *d_w_phases, size_t N, size_t C, int out_of_bounds,
                     int reduce, void *d_workspace, size_t workspace_bytes,
@@ -384,7 +388,10 @@ int bpmf_bp_run_multi(const float *features, const int32_t *moveouts, const floa
  * option is set: focus and column are written for the build's conventions.  A plan without LDS windows
  * (bp_direct.hip) runs its events' max-beams one after the other inside the call; everything else is batched.
  * Workspace: bpmf_bp_relocate_workspace_bytes(plan, E, N, C) bytes -- E prestacks (S P N floats each), the
- * partial rows of the group-range split and, for SPATIAL, the (E, N) max-beam rows. */
+ * partial rows of the group-range split and, for SPATIAL, the (E, N) max-beam rows.
+ * Non-finite features: the focus is taken on the max-beams, so a NaN beam is never the maximum and +Inf is (np.argmax
+ * on a volume with a NaN is deliberately not followed); a NaN in the column at the focus makes the whole likelihood
+ * row NaN, an Inf maximum gives 0 on the finite entries and NaN at the Inf. */
 #define BPMF_BP_RELOCATE_SPATIAL 0
 #define BPMF_BP_RELOCATE_TEMPORAL 1
 size_t bpmf_bp_relocate_workspace_bytes(const bpmf_bp_plan *plan, size_t E, size_t N, size_t C);

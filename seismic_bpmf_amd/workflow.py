@@ -1878,6 +1878,29 @@ def beam_detections_device(beam, arg, *, mpd, threshold=None, window=None, n_dev
     return peaks, src, nodes
 
 
+_FOCUS_BLOCK = 1 << 22      # elements of the volume scanned per step of _first_maximum
+
+
+def _first_maximum(vol):
+    """(src_idx, time_idx) of the point of maximum focusing of a (K, N) beam volume on the device: the first maximum in
+    source-major order among the beams that are not NaN -- a NaN beam is never the maximum and +Inf is, the rule of the
+    running maximum behind reduce="max" (DESIGN.md s4 "Non-finite features"); (0, 0) for a volume of nothing but NaN.
+    On a volume without NaN this is np.unravel_index(vol.argmax(), vol.shape).  Scanned in blocks of whole rows, so the
+    only temporaries are block-sized; one synchronisation."""
+    import torch
+    K, N = vol.shape
+    rows = max(1, _FOCUS_BLOCK // N)
+    best, where = [], []
+    for k0 in range(0, K, rows):
+        part = vol[k0:k0 + rows].reshape(-1)
+        part = torch.where(part != part, float("-inf"), part)
+        i = torch.argmax(part)                   # the first maximum of the block
+        best.append(part[i])
+        where.append(i + k0 * N)
+    first = int(torch.stack(where)[torch.argmax(torch.stack(best))])      # the first block that reaches the maximum
+    return divmod(first, N)
+
+
 def relocation_focus(beamformer, features, weights_phases, uncertainty_method="spatial",
                      out_of_bounds="flexible"):
     """The beamforming step of the reference's event relocation, ``Event.relocate_beam``
@@ -1891,20 +1914,29 @@ def relocation_focus(beamformer, features, weights_phases, uncertainty_method="s
     likelihood (K floats downloaded instead of K*N).  "temporal" (``reduce="max"``): returns
     ``(src_idx, time_idx, maxbeam)`` with time_idx = maxbeam.argmax() (first maximum) and
     src_idx = maxbeam_sources[time_idx].  `out_of_bounds` defaults to the reference's "flexible"
-    (:2186)."""
+    (:2186).
+
+    Non-finite features: a NaN beam is never the maximum and a +Inf beam is, under both methods (the max-beam
+    of "temporal" is never NaN).  The reference's np.argmax stops at the first NaN of a volume that holds one;
+    that is deliberately not followed -- a focus on a NaN is useless, and it is what relocate_events and the
+    reference's own "temporal" method return.  The column comes back as it is, NaN beams included."""
     import torch
     if uncertainty_method == "spatial":
         vol = beamformer.run(features, weights_phases, "none", out_of_bounds)        # (K, N) on the device
-        flat = vol.reshape(-1)
-        first = int(torch.argmax(flat))      # the first maximum (the first NaN if there is one), as np.argmax;
-                                             # a reduction: no K x N temporaries
-        src_idx, time_idx = divmod(first, vol.shape[1])
+        src_idx, time_idx = _first_maximum(vol)
         return src_idx, time_idx, vol[:, time_idx].cpu().numpy()
     if uncertainty_method == "temporal":
         beam, arg = beamformer.run(features, weights_phases, "max", out_of_bounds)
         time_idx = int(torch.argmax(beam))
         return int(arg[time_idx]), time_idx, beam.cpu().numpy()
     raise ValueError("uncertainty_method should be 'spatial' or 'temporal'")
+
+
+def _likelihood_of_column(col):
+    """postprocess.likelihood on a device column: float32 subtract / divide / clip; a NaN in the column makes min and
+    max NaN and with them the whole row, as np.min / np.max do."""
+    lo, hi = col.min(), col.max()
+    return ((col - lo) / (hi - lo)).clamp_(0.0, 1.0)
 
 
 def relocation_likelihood(beamformer, features, weights_phases, out_of_bounds="flexible", domain=None):
@@ -1915,15 +1947,17 @@ def relocation_likelihood(beamformer, features, weights_phases, out_of_bounds="f
     float32 subtract / divide / clip, the operations NumPy performs, evaluated on the column where it
     lies.  Only `likelihood[domain]` (or the whole (K,) vector when `domain` is None) comes back.
 
+    Non-finite features: the focus is relocation_focus's (a NaN beam is never the maximum, +Inf is; the
+    reference's np.argmax on a volume with a NaN is deliberately not followed).  A NaN in the column makes the
+    whole likelihood NaN; an Inf maximum gives 0 on the finite entries and NaN at the Inf -- what
+    postprocess.likelihood gives for that column.
+
     Returns (src_idx, time_idx, likelihood): feed `likelihood` and the domain's coordinates to
     postprocess.compute_location_uncertainty for (hunc, vunc)."""
     import torch
     vol = beamformer.run(features, weights_phases, "none", out_of_bounds)
-    first = int(torch.argmax(vol.reshape(-1)))
-    src_idx, time_idx = divmod(first, vol.shape[1])
-    col = vol[:, time_idx]
-    lo, hi = col.min(), col.max()
-    like = ((col - lo) / (hi - lo)).clamp_(0.0, 1.0)
+    src_idx, time_idx = _first_maximum(vol)
+    like = _likelihood_of_column(vol[:, time_idx])
     if domain is not None:
         like = like[torch.as_tensor(np.asarray(domain, dtype=np.int64), device=like.device)]
     return src_idx, time_idx, like.cpu().numpy()
@@ -2052,7 +2086,11 @@ def relocate_events(beamformer, features, weights_phases, uncertainty_method="sp
                   time_idx[e] = maxbeam[e].argmax(), src_idx[e] = maxbeam_sources[e, time_idx[e]].
     For every event the result is what relocation_focus / relocation_likelihood return for it alone, bit for
     bit, ties included (first maximum in source-major order).  An event whose maximum is not > 0 although its
-    window is not all zero (negative features or weights) is redone on its volume by the per-event path.
+    window is not all zero (negative features or weights, or nothing but NaN beams) is redone on its volume by
+    the per-event path.  Non-finite features: a NaN beam is never the maximum and +Inf is, the
+    max-beams are never NaN; the reference's np.argmax on a volume with a NaN is deliberately not followed.  A
+    NaN in the column at the focus makes the event's likelihood row NaN, an Inf maximum gives 0 on the finite
+    entries and NaN at the Inf.  (``uncertainties=True`` on such a row is not defined.)
     Events run in chunks sized from the free device memory; the results do not depend on the chunks.
 
     ``uncertainties=True`` finishes ``Event.relocate_beam`` (dataset.py:2207-2245) in the same call, on the device
@@ -2169,10 +2207,9 @@ def relocate_events(beamformer, features, weights_phases, uncertainty_method="sp
         if not bool((win != 0).any()):
             continue
         vol = bf.run(win.contiguous(), wp, "none", out_of_bounds)
-        k, ti = divmod(int(t.argmax(vol.reshape(-1))), N)
+        k, ti = _first_maximum(vol)
         col = vol[:, ti]
-        lo, hi = col.min(), col.max()
-        like[e] = ((col - lo) / (hi - lo)).clamp_(0.0, 1.0)
+        like[e] = _likelihood_of_column(col)
         if cols is not None:
             cols[e] = col
         res["src_idx"][e], res["time_idx"][e], res["max_beam"][e] = k, ti, float(col[k])

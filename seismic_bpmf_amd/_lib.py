@@ -15,6 +15,7 @@ _i = C.POINTER(C.c_int32)
 _u64 = C.POINTER(C.c_uint64)
 _sz = C.c_size_t
 _vp = C.c_void_p
+Handle = C.c_void_p      # an opaque handle the library fills in and takes back (bpmf_bp_plan_create)
 
 # name -> (restype, argtypes); must list every symbol of include/bpmf_hip.h
 class BpPlanStats(C.Structure):
@@ -165,6 +166,30 @@ def check(rc, what):
     if rc != 0:
         msg = lib().bpmf_last_error().decode("utf-8", "replace")
         raise BpmfHipError(f"{what} failed (status {rc}): {msg}")
+
+
+STREAM = object()    # among the arguments of call(): the current stream of the call's device
+
+
+def call(name, dev, *args):
+    """Call the status-returning entry point `name` with `dev` current and check its status (BpmfHipError).  A tensor
+    argument goes as its data_ptr(), STREAM as the pointer of the current stream on `dev`, everything else (None
+    included) as it is: SIGNATURES converts.  ValueError for a tensor that is not contiguous or not on `dev` -- the
+    library would read it as if it were."""
+    import torch
+    dev = torch.device(dev)
+    index = torch.cuda.current_device() if dev.index is None else dev.index
+    argv = list(args)
+    with torch.cuda.device(index):
+        for pos, a in enumerate(args):
+            if a is STREAM:
+                argv[pos] = torch.cuda.current_stream(index).cuda_stream
+            elif isinstance(a, torch.Tensor):
+                if not a.is_cuda or a.device.index != index or not a.is_contiguous():
+                    raise ValueError(f"{name}: argument {pos} must be a contiguous tensor on cuda:{index}; got a "
+                                     f"{'' if a.is_contiguous() else 'non-'}contiguous one on {a.device}")
+                argv[pos] = a.data_ptr()
+        check(getattr(lib(), name)(*argv), name)
 
 
 def last_error():

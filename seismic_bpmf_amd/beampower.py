@@ -123,7 +123,7 @@ class BeamformerGPU:
         self.source_id_offset = int(source_id_offset)
         self._tables_host = (mv, ws)     # relocate_batch gathers beam columns from the tables as they are
         self._tables_dev = None
-        self._plan = C.c_void_p()
+        self._plan = _lib.Handle()
         rc = self.lib.bpmf_bp_plan_create(mv.ctypes.data_as(_lib._i), ws.ctypes.data_as(_lib._f),
                                           self.K, self.S, self.P, idx, int(source_id_offset),
                                           C.byref(self._plan))
@@ -143,7 +143,7 @@ class BeamformerGPU:
     def close(self):
         if getattr(self, "_plan", None) is not None and self._plan.value:
             self.lib.bpmf_bp_plan_destroy(self._plan)
-            self._plan = C.c_void_p()
+            self._plan = _lib.Handle()
 
     def __del__(self):
         try:
@@ -174,18 +174,12 @@ class BeamformerGPU:
             beam, arg = out if out is not None else (
                 t.empty(N, dtype=t.float32, device=self.device),
                 t.empty(N, dtype=t.int32, device=self.device))
-            arg_ptr = arg.data_ptr()
         else:
             beam = out if out is not None else t.empty((self.K, N), dtype=t.float32,
                                                        device=self.device)
-            arg, arg_ptr = None, None
-        stream = t.cuda.current_stream(self.device).cuda_stream
-        with t.cuda.device(self.device):
-            rc = self.lib.bpmf_bp_run_dev(self._plan, f.data_ptr(), wp.data_ptr(), N, Cc,
-                                          _OOB[out_of_bounds], _REDUCE[reduce],
-                                          self._ws.data_ptr(), self._ws.numel(),
-                                          C.c_void_p(stream), beam.data_ptr(), arg_ptr)
-        _lib.check(rc, "bpmf_bp_run_dev")
+            arg = None
+        _lib.call("bpmf_bp_run_dev", self.device, self._plan, f, wp, N, Cc, _OOB[out_of_bounds], _REDUCE[reduce],
+                  self._ws, self._ws.numel(), _lib.STREAM, beam, arg)
         self._keepalive = (f, wp)
         return (beam, arg) if reduce == "max" else beam
 
@@ -205,19 +199,10 @@ class BeamformerGPU:
             mv, ws = self._tables_host
             self._tables_dev = (t.as_tensor(mv, device=self.device), t.as_tensor(ws, device=self.device))
         mv_d, ws_d = self._tables_dev if method == "spatial" else (None, None)
-
-        def ptr(x):
-            return None if x is None else x.data_ptr()
-
-        stream = t.cuda.current_stream(self.device).cuda_stream
-        with t.cuda.device(self.device):
-            rc = self.lib.bpmf_bp_relocate_batch_dev(
-                self._plan, features.data_ptr(), int(event_stride), int(row_stride), ptr(starts),
-                weights_phases.data_ptr(), ptr(mv_d), ptr(ws_d), int(E), int(N), int(Cc), _OOB[out_of_bounds],
-                self._METHOD[method], workspace.data_ptr(), workspace.numel(), C.c_void_p(stream),
-                time_idx.data_ptr(), src_idx.data_ptr(), max_beam.data_ptr(), ptr(likelihood), ptr(columns),
-                ptr(maxbeam), ptr(maxbeam_sources))
-        _lib.check(rc, "bpmf_bp_relocate_batch_dev")
+        _lib.call("bpmf_bp_relocate_batch_dev", self.device, self._plan, features, int(event_stride), int(row_stride),
+                  starts, weights_phases, mv_d, ws_d, int(E), int(N), int(Cc), _OOB[out_of_bounds], self._METHOD[method],
+                  workspace, workspace.numel(), _lib.STREAM, time_idx, src_idx, max_beam, likelihood, columns, maxbeam,
+                  maxbeam_sources)
 
     def set_source_coordinates(self, longitude, latitude, depth):
         """Coordinates of this plan's source rows, three (K,) arrays: degrees, degrees, km -- what
@@ -238,32 +223,20 @@ class BeamformerGPU:
         same stream: `out` (5, E) float64 receives hunc, vunc, longitude, latitude, depth and `n_domain` (E,)
         int32 the size of the domain.  workflow.relocate_events(uncertainties=True) is the call with checks."""
         from . import postprocess as pp
-        t = self.torch
         if getattr(self, "_coord_tables", None) is None:
             raise ValueError("no source coordinates: call set_source_coordinates(longitude, latitude, depth) first")
-
-        def ptr(x):
-            return None if x is None else x.data_ptr()
-
-        stream = t.cuda.current_stream(self.device).cuda_stream
-        with t.cuda.device(self.device):
-            rc = self.lib.bpmf_bp_location_uncertainty_dev(
-                self._plan, self._METHOD[method], int(E), int(N), src_idx.data_ptr(), ptr(likelihood), ptr(maxbeam),
-                ptr(maxbeam_sources), ptr(max_beam), self._coord_tables.data_ptr(), pp.domain_scale_per_longitude(),
-                float(side_km) / 2.0, float(effective_kT), float(gibbs_cutoff), workspace.data_ptr(),
-                workspace.numel(), C.c_void_p(stream), out[0].data_ptr(), out[1].data_ptr(), n_domain.data_ptr(),
-                out[2].data_ptr(), out[3].data_ptr(), out[4].data_ptr(), ptr(domain_mask))
-        _lib.check(rc, "bpmf_bp_location_uncertainty_dev")
+        _lib.call("bpmf_bp_location_uncertainty_dev", self.device, self._plan, self._METHOD[method], int(E), int(N),
+                  src_idx, likelihood, maxbeam, maxbeam_sources, max_beam, self._coord_tables,
+                  pp.domain_scale_per_longitude(), float(side_km) / 2.0, float(effective_kT), float(gibbs_cutoff),
+                  workspace, workspace.numel(), _lib.STREAM, out[0], out[1], n_domain, out[2], out[3], out[4],
+                  domain_mask)
 
     # -- multi-GPU exchange step of reduce="max" (SURVEY.md section 8e) ----------------
     def pack_max(self, beam, arg):
         """(beam, arg) -> int64 keys whose max is (largest beam, lowest source id)."""
         t = self.torch
         packed = t.empty(beam.numel(), dtype=t.int64, device=self.device)
-        stream = t.cuda.current_stream(self.device).cuda_stream
-        _lib.check(self.lib.bpmf_bp_pack_max_dev(beam.data_ptr(), arg.data_ptr(), beam.numel(), 1,
-                                                 C.c_void_p(stream), packed.data_ptr()),
-                   "bpmf_bp_pack_max_dev")
+        _lib.call("bpmf_bp_pack_max_dev", self.device, beam, arg, beam.numel(), 1, _lib.STREAM, packed)
         return packed
 
     def unpack_max(self, packed):
@@ -271,8 +244,5 @@ class BeamformerGPU:
         n = packed.numel()
         beam = t.empty(n, dtype=t.float32, device=self.device)
         arg = t.empty(n, dtype=t.int32, device=self.device)
-        stream = t.cuda.current_stream(self.device).cuda_stream
-        _lib.check(self.lib.bpmf_bp_unpack_max_dev(packed.data_ptr(), n, 1, C.c_void_p(stream),
-                                                   beam.data_ptr(), arg.data_ptr()),
-                   "bpmf_bp_unpack_max_dev")
+        _lib.call("bpmf_bp_unpack_max_dev", self.device, packed, n, 1, _lib.STREAM, beam, arg)
         return beam, arg

@@ -4,7 +4,7 @@
 //
 // Only the bins next to a target frequency are ever read, so the transform is a DFT PRUNED to the caller's list of
 // bins: per row a (n x K_b) float64 product with twiddles from an exact table of n entries (cos, -sin of 2 pi m / n).
-// A row is one window (e, s, c): r = (e S + s) C + c, the n samples data[s, c, start[e S + s] + j].  Rows go through in
+// A row is one window (e, s, c): r = (e S + s) C + c, cut by the rule of day_rows.h.  Rows go through in
 // slabs of a multiple of 64 that fit the caller's workspace:
 //   1. fs_dft_kernel       a workgroup of 4 waves takes 64 rows x up to 64 bins (blockIdx.y: the group of 64 bins;
 //                          32 or 16 where no more are asked for).
@@ -26,6 +26,7 @@
 // Operands are padded with zeros (samples behind n - 1, rows past the last, bins past K_b); nothing is read past a
 // buffer.  Plain vector stores, no atomics; every element of both outputs is written.
 #include "common.h"
+#include "day_rows.h"
 #include <cmath>
 #include "../../include/bpmf_hip.h"
 
@@ -34,7 +35,6 @@ namespace bpmf {
 constexpr int FS_MIN_SAMPLES = 2;
 constexpr int FS_MAX_SAMPLES = 16384;
 constexpr int FS_MAX_TARGETS = 1024;
-constexpr long long FS_INDEX_LIMIT = 1ll << 40;
 constexpr int FS_ROWS = 64;                             // rows of a workgroup: 16 per wave
 constexpr int FS_CHUNK = 64;                            // samples staged at a time
 constexpr int FS_ROW_STRIDE = FS_CHUNK + 2;             // doubles; 16 rows x 2 samples of a half wave fall on 64 banks
@@ -99,14 +99,11 @@ __global__ __launch_bounds__(256) void fs_dft_kernel(const FsCall call, unsigned
     if (lane < 16) {
         const long long r = call.row0 + in_slab0 + lane;
         if (r < call.rows) {
-            my_win = r / call.C;
-            my_c = (int)(r - my_win * call.C);
-            const int s = (int)(my_win % call.S);
-            long long start = call.start[my_win];
-            start = start > FS_INDEX_LIMIT ? FS_INDEX_LIMIT : (start < -FS_INDEX_LIMIT ? -FS_INDEX_LIMIT : start);
-            const bool inside = start >= 0 && start + n <= call.N;
+            const DayRow dr = day_row(call.S, call.C, call.N, call.start, (unsigned)r);
+            my_win = dr.win, my_c = dr.c;
+            const bool inside = day_window_inside(dr.start, n, call.N);
             my_state = inside ? FS_LIVE : FS_OUTSIDE_DAY;
-            if (inside) my_base = ((long long)s * call.C + my_c) * call.N + start;
+            if (inside) my_base = dr.trace + dr.start;
         }
     }
 
@@ -336,17 +333,9 @@ extern "C" int bpmf_fft_spectrum_dev(const float* d_data, size_t S, size_t C, si
 {
     hipStream_t stream = (hipStream_t)stream_;
     if (n_windows == 0) return 0;
-    if (!d_data || !d_starts || !d_taper || !d_twiddles || !d_bins || !d_workspace || !d_out || !d_valid ||
-        (n_targets && (!d_pair || !d_dx || !d_span || !d_flags))) {
-        set_error("bpmf_fft_spectrum_dev: null pointer");
-        return -1;
-    }
-    if (S == 0 || C == 0 || N == 0 || N > (size_t)FS_INDEX_LIMIT || n_windows % S != 0 ||
-        n_windows > 0x7fffffffull / C) {
-        set_error("bpmf_fft_spectrum_dev: bad argument (S=%zu C=%zu N=%zu windows=%zu): need data, a whole number of "
-                  "events and fewer than 2^31 rows", S, C, N, n_windows);
-        return -1;
-    }
+    const bool null_pointer = !d_data || !d_starts || !d_taper || !d_twiddles || !d_bins || !d_workspace || !d_out ||
+                              !d_valid || (n_targets && (!d_pair || !d_dx || !d_span || !d_flags));
+    if (day_rows_refused("bpmf_fft_spectrum_dev", true, null_pointer, S, C, N, n_windows, set_error)) return -1;
     if (!fs_sizes_ok(n_samples, n_bins, n_targets)) {
         set_error("bpmf_fft_spectrum_dev: need %d .. %d samples, 1 .. n_samples / 2 + 1 bins and at most %d targets "
                   "(n_samples=%zu n_bins=%zu n_targets=%zu)", FS_MIN_SAMPLES, FS_MAX_SAMPLES, FS_MAX_TARGETS,

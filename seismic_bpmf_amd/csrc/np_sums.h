@@ -1,10 +1,10 @@
 // NumPy's float32 sums of a row staged in LDS, by one workgroup, bit for bit: np.sum / np.mean / np.std of at most
 // NP_CHUNK float32 -- one pairwise tree.  The order of the additions is np_order.h's, the single definition; what is
-// here is its block layout, shared by templates.hip and picker.hip (resample.hip takes clipped_sample alone).  The
-// shape of the tree depends on the length alone: the host lists its leaves once (list_leaves: np_walk) and
-// passes the list to the kernel by value.  One workgroup of TP_THREADS threads works on one row: each (leaf,
-// accumulator j) is one thread's at most 16 sequential adds out of LDS; one thread per leaf adds the eight partial sums
-// and the tail; thread 0 folds the leaves (NpFold, on SumScratch's LDS array).
+// here is its block layout, shared by templates.hip and picker.hip.  The shape of the tree depends on the length
+// alone: the host lists its leaves once (list_leaves: np_walk) and passes the list to the kernel by value.  One
+// workgroup of TP_THREADS threads works on one row: each (leaf, accumulator j) is one thread's at most 16 sequential
+// adds out of LDS; one thread per leaf adds the eight partial sums and the tail; thread 0 folds the leaves (NpFold, on
+// SumScratch's LDS array).
 #pragma once
 #include "common.h"
 #include "np_order.h"
@@ -94,14 +94,6 @@ __device__ inline float block_std(float* x, int len, const LeafTable& tab, SumSc
     // (sqrtf: the correctly rounded square root, v_sqrt_f32 plus a next-up / next-down fix-up by fma.  __fsqrt_rn
     // compiles to the bare v_sqrt_f32, which is one ulp off NumPy's about once in fifteen windows.)
     return sqrtf(__fdiv_rn(block_pairwise_sum(x, tab, s, tid), count));
-}
-
-// data[i] inside the day, +0.0 outside; the address is clamped, so the load is never predicated (n >= 1)
-__device__ __forceinline__ float clipped_sample(const float* __restrict__ x, long long i, long long n)
-{
-    const long long ic = i < 0 ? 0 : (i >= n ? n - 1 : i);
-    const float v = x[ic];
-    return ic == i ? v : 0.0f;
 }
 
 }  // namespace bpmf

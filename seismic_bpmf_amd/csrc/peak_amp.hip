@@ -8,7 +8,7 @@
 // The slice is a NumPy BASIC slice and the reference does not guard it, so its rule is the contract
 // (slice_bound): each of i1, i2 on its own gets N added when negative and is then clipped to [0, N]; the window is
 // [a, b), empty when b <= a.  Hence a window that straddles sample 0 is EMPTY (a lands near N, b near 0), a window
-// wholly before sample 0 WRAPS to the end of the day, and a window past N is clipped at N.
+// wholly before sample 0 WRAPS to the end of the day, and a window past N is clipped at N (of day_rows.h: the limit).
 //
 // np.max propagates NaN and v_max_f32 drops it: every lane carries a "saw a NaN" flag beside its running maximum, the
 // flags meet in one __ballot, and a window that holds a NaN yields a quiet NaN.  +-Inf are ordinary values.  One
@@ -23,6 +23,7 @@
 // (and the flag) may see a sample twice.  Across lanes: __shfl_xor maxima and one ballot; lane 0 stores the result
 // with a plain vector store.  No LDS, no atomics, and every (q, s, c) is written, the 0.0 of an empty window included.
 #include "common.h"
+#include "day_rows.h"
 #include <cmath>
 #include <vector>
 #include "../../include/bpmf_hip.h"
@@ -30,7 +31,6 @@
 namespace bpmf {
 
 constexpr int PA_UNROLL = 8;                       // loads in flight per lane: 512 samples per round of a wave
-constexpr long long PA_INDEX_LIMIT = 1ll << 40;    // N, |offset|, |duration| of the entry point
 constexpr long long PA_SAMPLE_LIMIT = 1ll << 61;   // |k| the kernel clamps to
 
 // One bound of the Python slice x[i1:i2] of a series of n samples.
@@ -107,8 +107,8 @@ extern "C" int bpmf_peak_amplitudes_dev(const float* d_data, size_t S, size_t C,
         return -1;
     }
     if (S == 0 || C == 0 || S > 0x7fffffffull / C || T == 0 || T > 0x7fffffffull || n_detections > 0x7fffffffull ||
-        N > (size_t)PA_INDEX_LIMIT || offset > PA_INDEX_LIMIT || offset < -PA_INDEX_LIMIT ||
-        duration > PA_INDEX_LIMIT || duration < -PA_INDEX_LIMIT) {
+        N > (size_t)DAY_INDEX_LIMIT || offset > DAY_INDEX_LIMIT || offset < -DAY_INDEX_LIMIT ||
+        duration > DAY_INDEX_LIMIT || duration < -DAY_INDEX_LIMIT) {
         set_error("bpmf_peak_amplitudes_dev: bad argument (S=%zu C=%zu N=%zu T=%zu detections=%zu offset=%lld "
                   "duration=%lld)", S, C, N, T, n_detections, (long long)offset, (long long)duration);
         return -1;

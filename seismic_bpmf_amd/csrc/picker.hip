@@ -2,9 +2,9 @@
 // :2039-2094; the definitions are postprocess.normalize_batch_host and postprocess.find_picks_host, and the device
 // equals them bit for bit).
 //
-// bpmf_normalize_batch_dev -- the running Z-score in front of the model.  Row (r, c) is data[r % S, c, start[r] + i],
-// i in [0, n), +0.0 outside the day (clipped_sample): windows of E events x S stations cut from the day, or, with
-// S = rows, N = n and no starts, an already cut (R, C, n) tensor.  One workgroup of 256 threads per row:
+// bpmf_normalize_batch_dev -- the running Z-score in front of the model.  Row (r, c) is cut by the rule of day_rows.h:
+// windows of E events x S stations of the day, or, with S = rows, N = n and no starts, an already cut (R, C, n) tensor.
+// One workgroup of 256 threads per row:
 //   1. the row, reflect-padded by `shift` on both sides, is staged in LDS once (n + 2 shift floats);
 //   2. window k covers padded[k shift, k shift + W): it is copied to a second LDS buffer (block_std squares its row in
 //      place) and np.mean / np.std come from the NumPy-order float32 sums of np_sums.h.  The reference overwrites the
@@ -30,6 +30,7 @@
 //      np_sum, in one thread) and writes its record.  count is the true number of picks.
 // Plain vector stores, no atomics; every output element is written.
 #include "common.h"
+#include "day_rows.h"
 #include "np_sums.h"
 #include <cmath>
 #include "../../include/bpmf_hip.h"
@@ -38,7 +39,6 @@ namespace bpmf {
 
 constexpr int PK_THREADS = TP_THREADS;
 constexpr size_t PK_NORM_LDS_BYTES = 150 * 1024;       // dynamic; the static SumScratch takes 5 KB of the 160 KB
-constexpr long long PK_INDEX_LIMIT = 1ll << 40;        // N and |start|
 constexpr int PK_MAX_SERIES = 16384;                   // find_picks: 4 (n + n/2 + 1) bytes of LDS
 constexpr int PK_MAX_PICKS = 4096;
 
@@ -56,15 +56,13 @@ __global__ __launch_bounds__(PK_THREADS) void normalize_batch_kernel(
     float* w_std = w_mean + nw;
     const int tid = threadIdx.x;
     const size_t item = blockIdx.x;                                // (r, c) flattened
-    const size_t r = item / (size_t)C, c = item - r * (size_t)C;
-    const float* __restrict__ x = data + ((r % (size_t)S) * (size_t)C + c) * (size_t)N;
-    long long i0 = start ? start[r] : 0;
-    i0 = i0 > PK_INDEX_LIMIT ? PK_INDEX_LIMIT : (i0 < -PK_INDEX_LIMIT ? -PK_INDEX_LIMIT : i0);
+    const DayRow dr = day_row(S, C, N, start, item);
+    const float* __restrict__ x = data + dr.trace;
 
     for (int p = tid; p < n_pad; p += PK_THREADS) {
         int i = p - shift;                                         // np.pad(mode="reflect"), shift <= n - 1
         i = i < 0 ? -i : (i >= n ? 2 * (n - 1) - i : i);
-        row[p] = clipped_sample(x, i0 + i, N);
+        row[p] = clipped_sample(x, dr.start + i, N);
     }
     __syncthreads();
     const int lo = nw > 2 ? 1 : 0, hi = nw > 2 ? nw - 2 : 0;       // the windows whose statistics survive
@@ -272,15 +270,8 @@ extern "C" int bpmf_normalize_batch_dev(const float* d_data, size_t S, size_t C,
 {
     hipStream_t stream = (hipStream_t)stream_;
     if (n_rows == 0) return 0;
-    if (!d_data || !d_nodes || !d_out) {
-        set_error("bpmf_normalize_batch_dev: null pointer");
+    if (day_rows_refused("bpmf_normalize_batch_dev", false, !d_data || !d_nodes || !d_out, S, C, N, n_rows, set_error))
         return -1;
-    }
-    if (S == 0 || C == 0 || N == 0 || N > (size_t)PK_INDEX_LIMIT || n_rows > 0x7fffffffull / C ||
-        S > 0x7fffffffull / C) {
-        set_error("bpmf_normalize_batch_dev: bad argument (S=%zu C=%zu N=%zu rows=%zu)", S, C, N, n_rows);
-        return -1;
-    }
     if (window < 2 || window > (size_t)NP_CHUNK || shift < 1 || n_samples < 2 || shift > n_samples - 1 ||
         n_samples > (1u << 24)) {
         set_error("bpmf_normalize_batch_dev: need 2 <= window <= %d and 1 <= shift <= n_samples - 1 (n_samples=%zu "

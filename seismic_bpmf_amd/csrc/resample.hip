@@ -2,8 +2,8 @@
 // cut windows and the deep-learning picker in Event.pick_PS_phases (BPMF/dataset.py:1801-1804, 5596-5599).  The
 // definition is postprocess.resample_poly_host and the device equals it bit for bit.
 //
-// bpmf_resample_poly_dev -- row (r, c) is data[r % S, c, start[r] + i], i in [0, n_in), +0.0 outside the day
-// (clipped_sample), exactly the rows of bpmf_normalize_batch_dev.  The caller brings the plan of
+// bpmf_resample_poly_dev -- row (r, c) is cut by the rule of day_rows.h, +0.0 outside the day, exactly the rows of
+// bpmf_normalize_batch_dev.  The caller brings the plan of
 // postprocess.resample_poly_plan: the float32 tap table (hp taps for each of the `up` phases: the Kaiser filter times
 // up, with the zeros upfirdn runs it with in front and behind) and n_pre_remove.  Output q of a row has
 //     m = q + n_pre_remove,  j_hi = m down / up,  t = m down % up,
@@ -19,7 +19,8 @@
 // RS_LDS_FLOATS (bpmf_resample_poly_tile).  Index arithmetic in 64 bits.  Plain vector stores, no atomics; every
 // output element is written.
 #include "common.h"
-#include "np_sums.h"
+#include "day_rows.h"
+#include <numeric>
 #include "../../include/bpmf_hip.h"
 
 namespace bpmf {
@@ -29,7 +30,6 @@ constexpr size_t RS_MAX_RATE = 64;                     // max(up, down), reduced
 constexpr size_t RS_MAX_TABLE = 2048;                  // hp * up floats; the plan needs at most 22 * 64 + 64
 constexpr size_t RS_LDS_FLOATS = 12288;                // table + span: 48 KB
 constexpr size_t RS_MAX_TILE = 1024, RS_TILE_STEP = 64;
-constexpr long long RS_INDEX_LIMIT = 1ll << 40;        // n_in * max(up, down), N and |start|
 
 // the input samples a tile of `tile` outputs can span: j_hi(last) - j_hi(first) <= ceil((tile - 1) down / up)
 inline size_t rs_span(size_t tile, size_t up, size_t down, size_t hp)
@@ -44,16 +44,6 @@ inline size_t rs_tile(size_t up, size_t down, size_t hp)
     return tile;
 }
 
-inline size_t rs_gcd(size_t a, size_t b)
-{
-    while (b) {
-        const size_t t = a % b;
-        a = b;
-        b = t;
-    }
-    return a;
-}
-
 __global__ __launch_bounds__(RS_THREADS) void resample_poly_kernel(
     const float* __restrict__ data, int S, int C, long long N, const long long* __restrict__ start, long long n_in,
     int up, int down, const float* __restrict__ table, int hp, long long n_pre_remove, long long n_out, int tile,
@@ -65,10 +55,8 @@ __global__ __launch_bounds__(RS_THREADS) void resample_poly_kernel(
     const int tid = threadIdx.x;
     const size_t item = (size_t)blockIdx.x / (size_t)n_tiles;      // (r, c) flattened
     const long long q0 = (long long)((size_t)blockIdx.x % (size_t)n_tiles) * tile;
-    const size_t r = item / (size_t)C, c = item - r * (size_t)C;
-    const float* __restrict__ x = data + ((r % (size_t)S) * (size_t)C + c) * (size_t)N;
-    long long i0 = start ? start[r] : 0;
-    i0 = i0 > RS_INDEX_LIMIT ? RS_INDEX_LIMIT : (i0 < -RS_INDEX_LIMIT ? -RS_INDEX_LIMIT : i0);
+    const DayRow dr = day_row(S, C, N, start, item);
+    const float* __restrict__ x = data + dr.trace;
     const int nq = n_out - q0 < tile ? (int)(n_out - q0) : tile;   // >= 1: n_tiles = ceil(n_out / tile)
     const long long md0 = (q0 + n_pre_remove) * down;              // the tile's first output, in upsampled samples
     const long long j_first = md0 / up;
@@ -79,7 +67,7 @@ __global__ __launch_bounds__(RS_THREADS) void resample_poly_kernel(
     for (int p = tid; p < hp * up; p += RS_THREADS) tab[p] = table[p];
     for (int p = tid; p < span; p += RS_THREADS) {
         const long long j = j_base + p;
-        xs[p] = j >= 0 && j < n_in ? clipped_sample(x, i0 + j, N) : 0.0f;
+        xs[p] = j >= 0 && j < n_in ? clipped_sample(x, dr.start + j, N) : 0.0f;
     }
     __syncthreads();
 
@@ -118,22 +106,15 @@ extern "C" int bpmf_resample_poly_dev(const float* d_data, size_t S, size_t C, s
 {
     hipStream_t stream = (hipStream_t)stream_;
     if (n_rows == 0) return 0;
-    if (!d_data || !d_table || !d_out) {
-        set_error("bpmf_resample_poly_dev: null pointer");
+    if (day_rows_refused("bpmf_resample_poly_dev", false, !d_data || !d_table || !d_out, S, C, N, n_rows, set_error))
         return -1;
-    }
-    if (S == 0 || C == 0 || N == 0 || N > (size_t)RS_INDEX_LIMIT || n_rows > 0x7fffffffull / C ||
-        S > 0x7fffffffull / C) {
-        set_error("bpmf_resample_poly_dev: bad argument (S=%zu C=%zu N=%zu rows=%zu)", S, C, N, n_rows);
-        return -1;
-    }
-    if (up < 1 || down < 1 || up > RS_MAX_RATE || down > RS_MAX_RATE || rs_gcd(up, down) != 1 || up == down) {
+    if (up < 1 || down < 1 || up > RS_MAX_RATE || down > RS_MAX_RATE || std::gcd(up, down) != 1 || up == down) {
         set_error("bpmf_resample_poly_dev: need 1 <= up, down <= %zu, reduced by their gcd and not both 1 (up=%zu "
                   "down=%zu)", RS_MAX_RATE, up, down);
         return -1;
     }
     const size_t rate = up > down ? up : down;
-    if (n_in < 1 || n_in > ((size_t)RS_INDEX_LIMIT - 1) / rate) {
+    if (n_in < 1 || n_in > ((size_t)DAY_INDEX_LIMIT - 1) / rate) {
         set_error("bpmf_resample_poly_dev: need n_in >= 1 and n_in * max(up, down) below 2^40 (n_in=%zu up=%zu "
                   "down=%zu)", n_in, up, down);
         return -1;

@@ -1,7 +1,7 @@
 // Multi-band displacement spectra of a day's events on the device (BPMF/spectrum.py: Spectrum.compute_multi_band_spectrum
 // :387-505; the definition is postprocess.multiband_spectrum_host).  The day is float32, every operation float64.
 //
-// A row is one window (e, s, c): r = (e S + s) C + c, the n samples data[s, c, start[e S + s] + i].  Rows go through the
+// A row is one window (e, s, c): r = (e S + s) C + c, cut by the rule of day_rows.h.  Rows go through the
 // kernels in slabs of a multiple of 64 that fit the caller's workspace; a slab holds, per row, four scalars, the
 // prepared row and one forward pass per active band, all TIME-MAJOR (element t of row r at [t * slab + r]) so that the
 // 64 lanes of a wave -- 64 consecutive rows -- touch one 512-byte line per sample:
@@ -18,6 +18,7 @@
 // for bit.  A row's arithmetic depends on its own samples only: the same bits in any slab and any batch.  Plain vector
 // stores, no atomics on global memory; every element of every output is written.
 #include "common.h"
+#include "day_rows.h"
 #include "sos_cascade.h"
 #include <cmath>
 #include "../../include/bpmf_hip.h"
@@ -27,7 +28,6 @@ namespace bpmf {
 constexpr int MB_MAX_SAMPLES = 16384;
 constexpr int MB_MAX_BANDS = 64;
 constexpr int MB_ROW_SCALARS = 4;                      // mean, slope, rest, valid
-constexpr long long MB_INDEX_LIMIT = 1ll << 40;
 constexpr size_t MB_MAX_SLAB = 65535 * 64;            // rows: gridDim.y of the prepare kernel is slab / 64
 
 struct MbBands {
@@ -64,19 +64,16 @@ __global__ __launch_bounds__(64) void mb_stats_kernel(const MbCall call, unsigne
     __shared__ double lds[64];
     const int lane = threadIdx.x, n = call.n;
     const long long in_slab = blockIdx.x, r = call.row0 + in_slab;
-    const long long win = r / call.C;
-    const int c = (int)(r - win * call.C), s = (int)(win % call.S);
-    long long start = call.start[win];
-    start = start > MB_INDEX_LIMIT ? MB_INDEX_LIMIT : (start < -MB_INDEX_LIMIT ? -MB_INDEX_LIMIT : start);
-    const bool inside = start >= 0 && start + n <= call.N;
+    const DayRow dr = day_row(call.S, call.C, call.N, call.start, (unsigned)r);
+    const bool inside = day_window_inside(dr.start, n, call.N);
     if (lane < call.B && ((skip_mask >> lane) & 1ull)) out[(size_t)r * call.B + lane] = 0.0;
-    if (lane == 0 && c == 0) valid[win] = inside ? 1 : 0;
+    if (lane == 0 && dr.c == 0) valid[dr.win] = inside ? 1 : 0;
     double* sc = call.scalars + (size_t)in_slab * MB_ROW_SCALARS;
     if (!inside) {
         if (lane < MB_ROW_SCALARS) sc[lane] = 0.0;
         return;
     }
-    const float* __restrict__ x = call.data + ((size_t)s * call.C + c) * (size_t)call.N + (size_t)start;
+    const float* __restrict__ x = call.data + dr.trace + dr.start;
     SvSum s0;
     for (int t = lane; t < n; t += 64) s0.add((double)x[t]);
     const double mean = mb_wave_sum(s0.value(), lds, lane) / (double)n;
@@ -108,10 +105,8 @@ __global__ __launch_bounds__(256) void mb_prepare_kernel(const MbCall call)
         if (r < call.rows && t < n) {
             const double* sc = call.scalars + (size_t)(in_slab0 + local) * MB_ROW_SCALARS;
             if (sc[3] != 0.0) {
-                const long long win = r / call.C;
-                const int c = (int)(r - win * call.C), s = (int)(win % call.S);
-                const float* __restrict__ x = call.data + ((size_t)s * call.C + c) * (size_t)call.N
-                                              + (size_t)call.start[win];
+                const DayRow dr = day_row(call.S, call.C, call.N, call.start, (unsigned)r);    // (valid: inside the day)
+                const float* __restrict__ x = call.data + dr.trace + dr.start;
                 v = ((double)x[t] - sc[0]) - (sc[1] * ((double)t - centre) + sc[2]);
                 const int edge = t < n - 1 - t ? t : n - 1 - t;
                 if (edge < call.taper) v = v * (0.5 * (1.0 - cos(pi * (double)edge / (double)call.taper)));
@@ -200,16 +195,8 @@ extern "C" int bpmf_multiband_spectrum_dev(const float* d_data, size_t S, size_t
 {
     hipStream_t stream = (hipStream_t)stream_;
     if (n_windows == 0) return 0;
-    if (!d_data || !d_start || !d_sos || !bandwidths || !skip || !d_workspace || !d_out || !d_valid) {
-        set_error("bpmf_multiband_spectrum_dev: null pointer");
-        return -1;
-    }
-    if (S == 0 || C == 0 || N == 0 || N > (size_t)MB_INDEX_LIMIT || n_windows % S != 0 ||
-        n_windows > 0x7fffffffull / C) {
-        set_error("bpmf_multiband_spectrum_dev: bad argument (S=%zu C=%zu N=%zu windows=%zu): need data, a whole "
-                  "number of events and fewer than 2^31 rows", S, C, N, n_windows);
-        return -1;
-    }
+    const bool null_pointer = !d_data || !d_start || !d_sos || !bandwidths || !skip || !d_workspace || !d_out || !d_valid;
+    if (day_rows_refused("bpmf_multiband_spectrum_dev", true, null_pointer, S, C, N, n_windows, set_error)) return -1;
     if (n_samples == 0 || n_samples > (size_t)MB_MAX_SAMPLES || buffer == 0 || n_samples <= 2 * buffer ||
         taper > n_samples / 4) {
         set_error("bpmf_multiband_spectrum_dev: need 1 .. %d samples, 1 <= buffer, 2 buffer < n_samples and a taper of "

@@ -1,7 +1,7 @@
 // Matched-filter templates cut from a day's located events (BPMF/dataset.py: Event.read_waveforms(time_shifted=True)
 // :1929-2069, Event.set_availability :2556-2607, Template.moveouts_arr :3451-3475, TemplateGroup.normalize :4152-4166,
 // Event.compute_snr :1441-1475): for event e and channel (s, c), with i0 = origin[e] + moveouts[e, s, c],
-//     window[l]          = data[s, c, i0 + l] where 0 <= i0 + l < N, else +0.0          (l = 0 .. L-1)
+//     window[l]          = data[s, c, i0 + l] where 0 <= i0 + l < N, else +0.0   (l = 0 .. L-1; day_rows.h)
 //     available          = any(window != 0)            (a NaN counts as data)
 //     complete           = 0 <= i0 and i0 + L <= N
 //     norm               = np.std(window) | np.max(np.abs(window)) | 1;   0 -> 1
@@ -23,14 +23,13 @@
 // a "saw a NaN" flag travels beside the maximum, as in peak_amp.hip.  No atomics, plain vector stores, and every
 // output element is written, the zeros of a clipped window included.
 #include "common.h"
+#include "day_rows.h"
 #include "np_sums.h"
 #include <cmath>
 #include <vector>
 #include "../../include/bpmf_hip.h"
 
 namespace bpmf {
-
-constexpr long long TP_INDEX_LIMIT = 1ll << 40;    // N, |origin|, |noise_offset| of the entry point
 
 template <int NU>   // window samples per thread: L <= 256 * NU
 __global__ __launch_bounds__(TP_THREADS) void templates_kernel(
@@ -128,7 +127,7 @@ extern "C" int bpmf_templates_from_events_dev(const float* d_data, size_t S, siz
         return -1;
     }
     if (S == 0 || C == 0 || S > 0x7fffffffull / C || n_events > 0x7fffffffull / (S * C) || N == 0 ||
-        N > (size_t)TP_INDEX_LIMIT || noise_offset > TP_INDEX_LIMIT || noise_offset < -TP_INDEX_LIMIT ||
+        N > (size_t)DAY_INDEX_LIMIT || noise_offset > DAY_INDEX_LIMIT || noise_offset < -DAY_INDEX_LIMIT ||
         normalize < 0 || normalize > 2) {
         set_error("bpmf_templates_from_events_dev: bad argument (S=%zu C=%zu N=%zu events=%zu normalize=%d "
                   "noise_offset=%lld)", S, C, N, n_events, normalize, (long long)noise_offset);
@@ -139,7 +138,7 @@ extern "C" int bpmf_templates_from_events_dev(const float* d_data, size_t S, siz
     BPMF_HIP_CHECK(hipMemcpyAsync(origin.data(), d_origin, n_events * sizeof(int64_t), hipMemcpyDeviceToHost, stream));
     BPMF_HIP_CHECK(hipStreamSynchronize(stream));
     for (size_t e = 0; e < n_events; ++e)
-        if (origin[e] > TP_INDEX_LIMIT || origin[e] < -TP_INDEX_LIMIT) {
+        if (origin[e] > DAY_INDEX_LIMIT || origin[e] < -DAY_INDEX_LIMIT) {
             set_error("bpmf_templates_from_events_dev: event %zu has origin sample %lld, outside +-2^40", e,
                       (long long)origin[e]);
             return -1;

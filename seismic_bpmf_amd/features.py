@@ -85,8 +85,6 @@ def envelope(traces, device=None, channels_per_batch=None, precision="float64"):
     out = torch.empty(x.shape, dtype=torch.float32, device=dev)
     fused = dtype == torch.float64 and x.dtype == torch.float32 and x.is_contiguous()
     if fused:
-        import ctypes as C
-        lib = _lib.lib()
         channels_per_batch = min(channels_per_batch, 65535)
     for i in range(0, x.shape[0], channels_per_batch):
         xb = x[i:i + channels_per_batch].to(dtype)
@@ -95,15 +93,12 @@ def envelope(traces, device=None, channels_per_batch=None, precision="float64"):
             # -i X with the DC (and Nyquist) bin cleared, in place; then sqrt(x^2 + h^2) from the float32 trace and
             # the float64 transform: one pass each (csrc/stats.hip; the tensor expressions below made ten)
             del xb
-            stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
             with torch.cuda.device(dev):
-                _lib.check(lib.bpmf_hilbert_spectrum_dev(C.c_void_p(X.data_ptr()), X.shape[0], X.shape[1], int(n % 2 == 0),
-                                                         stream), "bpmf_hilbert_spectrum_dev")
+                _lib.call("bpmf_hilbert_spectrum_dev", dev, X, X.shape[0], X.shape[1], int(n % 2 == 0), _lib.STREAM)
                 h = torch.fft.irfft(X, n=n, dim=-1)
                 del X
                 xs, os_ = x[i:i + channels_per_batch], out[i:i + channels_per_batch]
-                _lib.check(lib.bpmf_envelope_combine_dev(C.c_void_p(xs.data_ptr()), C.c_void_p(h.data_ptr()), xs.numel(),
-                                                         stream, C.c_void_p(os_.data_ptr())), "bpmf_envelope_combine_dev")
+                _lib.call("bpmf_envelope_combine_dev", dev, xs, h, xs.numel(), _lib.STREAM, os_)
             del h
             continue
         X[:, 0] = 0                      # the DC bin (and, for even n, the Nyquist bin) has no quadrature part
@@ -120,24 +115,18 @@ def row_median_mad(x, skip_zeros=False, device=None):
     samples only when `skip_zeros`), exact order statistics on the device (csrc/stats.hip: long rows
     in two reads by the whole chip, short ones by a radix select).  Returns (median, mad, n_zero) device
     tensors; nothing is synchronised."""
-    import ctypes as C
     torch, dev = _torch_device(device)
     x = x.to(device=dev, dtype=torch.float32).contiguous()
     rows, n = x.shape
     med = torch.empty(rows, dtype=torch.float32, device=dev)
     mad = torch.empty(rows, dtype=torch.float32, device=dev)
     nz = torch.empty(rows, dtype=torch.int64, device=dev)
-    stream = torch.cuda.current_stream(dev).cuda_stream
     lib = _lib.lib()
     # (long rows are read twice by the whole chip instead of seven times by one workgroup each: that path
     # collects the middle of a row in a workspace, about a tenth of the size of the rows)
     ws = torch.empty(lib.bpmf_row_median_mad_workspace_bytes(rows, n), dtype=torch.uint8, device=dev)
-    with torch.cuda.device(dev):
-        rc = lib.bpmf_row_median_mad_ws_dev(C.c_void_p(x.data_ptr()), rows, n, int(bool(skip_zeros)),
-                                            C.c_void_p(ws.data_ptr()), ws.numel(),
-                                            C.c_void_p(stream), C.c_void_p(med.data_ptr()),
-                                            C.c_void_p(mad.data_ptr()), C.c_void_p(nz.data_ptr()))
-    _lib.check(rc, "bpmf_row_median_mad_ws_dev")
+    _lib.call("bpmf_row_median_mad_ws_dev", dev, x, rows, n, int(bool(skip_zeros)), ws, ws.numel(), _lib.STREAM, med,
+              mad, nz)
     ws.record_stream(torch.cuda.current_stream(dev))
     return med, mad, nz
 
@@ -158,18 +147,12 @@ def saturated_envelopes(traces, anomaly_threshold=1.0e-11, max_dynamic_range=1.0
     dead = (n_missing.to(torch.float64) > n_samples / 2) | ~(mad.to(torch.float64) >= anomaly_threshold)
     # (x - median) / MAD in float32 (NumPy's operations), 0 for missing samples and dead channels, capped: one pass,
     # in place over the envelopes (csrc/stats.hip saturate_rows_kernel; it was five element-wise passes of torch)
-    import ctypes as C
     out = rows
     dead_i = dead.to(torch.int32).contiguous()
-    with torch.cuda.device(dev):
-        for r0 in range(0, rows.shape[0], 65535):
-            nr = min(65535, rows.shape[0] - r0)
-            rc = _lib.lib().bpmf_saturate_rows_dev(C.c_void_p(rows[r0:].data_ptr()), C.c_void_p(median[r0:].data_ptr()),
-                                                   C.c_void_p(mad[r0:].data_ptr()), C.c_void_p(dead_i[r0:].data_ptr()),
-                                                   nr, n_samples, float(np.float32(max_dynamic_range)),
-                                                   C.c_void_p(torch.cuda.current_stream(dev).cuda_stream),
-                                                   C.c_void_p(out[r0:].data_ptr()))
-            _lib.check(rc, "bpmf_saturate_rows_dev")
+    for r0 in range(0, rows.shape[0], 65535):
+        nr = min(65535, rows.shape[0] - r0)
+        _lib.call("bpmf_saturate_rows_dev", dev, rows[r0:], median[r0:], mad[r0:], dead_i[r0:], nr, n_samples,
+                  float(np.float32(max_dynamic_range)), _lib.STREAM, out[r0:])
     availability = (~dead).reshape(n_stations, n_components).sum(dim=1).to(torch.int32).cpu().numpy()
     return out.reshape(n_stations, n_components, n_samples), availability
 
@@ -180,20 +163,15 @@ def kurtosis(signal, W, device=None):
     float32 device tensor of the same shape, zero where the reference leaves its zeros.  W is at most 32768 (the
     window and the 256 samples of a workgroup are staged in LDS: include/bpmf_hip.h); any number of channels, handed
     to the library 65535 at a time (its gridDim.y)."""
-    import ctypes as C
     torch, dev = _torch_device(device)
     x = signal if isinstance(signal, torch.Tensor) else torch.as_tensor(np.ascontiguousarray(signal, dtype=np.float32))
     x = x.to(device=dev, dtype=torch.float32).contiguous()
     if x.dim() != 3:
         raise ValueError("signal must be (n_stations, n_components, length)")
     out = torch.zeros_like(x)
-    stream = torch.cuda.current_stream(dev).cuda_stream
     length = x.shape[2]
     rows, out_rows = x.reshape(-1, length), out.reshape(-1, length)
-    with torch.cuda.device(dev):
-        for r0 in range(0, max(rows.shape[0], 1), 65535):         # (no channel at all: the library refuses, as before)
-            nr = min(65535, rows.shape[0] - r0)
-            rc = _lib.lib().bpmf_kurtosis_dev(C.c_void_p(rows[r0:].data_ptr()), int(W), nr, length,
-                                              C.c_void_p(stream), C.c_void_p(out_rows[r0:].data_ptr()))
-            _lib.check(rc, "bpmf_kurtosis_dev")
+    for r0 in range(0, max(rows.shape[0], 1), 65535):             # (no channel at all: the library refuses, as before)
+        nr = min(65535, rows.shape[0] - r0)
+        _lib.call("bpmf_kurtosis_dev", dev, rows[r0:], int(W), nr, length, _lib.STREAM, out_rows[r0:])
     return out

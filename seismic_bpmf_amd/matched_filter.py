@@ -252,13 +252,8 @@ class MatchedFilterGPU:
                _lib.get_option("mf.compat_sequential_csum")[0], _lib.get_option("mf.split16")[0])
         if self._prepared_for == key:
             flags |= FLAG_DATA_PREPARED
-        stream = t.cuda.current_stream(self.device).cuda_stream
-        with t.cuda.device(self.device):
-            rc = self.lib.bpmf_mf_run_dev(tp.data_ptr(), mv.data_ptr(), w.data_ptr(),
-                                          self.data.data_ptr(), int(step), L, N, T, S, Cc, n_corr,
-                                          int(bool(network_sum)), flags, ws.data_ptr(), ws.numel(),
-                                          C.c_void_p(stream), out.data_ptr())
-        _lib.check(rc, "bpmf_mf_run_dev")
+        _lib.call("bpmf_mf_run_dev", self.device, tp, mv, w, self.data, int(step), L, N, T, S, Cc, n_corr,
+                  int(bool(network_sum)), flags, ws, ws.numel(), _lib.STREAM, out)
         self._prepared_for = key
         # keep the inputs alive until the stream has consumed them
         self._keepalive = (tp, mv, w)

@@ -74,6 +74,7 @@ def peak_amplitudes_host(data, rows, samples, moveouts, offset, duration, data_n
     return out
 
 
+DAY_INDEX_LIMIT = 2**40          # N and |start|, |origin|, |offset| of the device entry points (csrc/day_rows.h)
 TEMPLATE_MAX_SAMPLES = 8192      # np.std sums a longer row in buffers of 8192 samples: another summation tree
 
 
@@ -177,7 +178,7 @@ def template_arguments(S, C, origin_samples, moveouts, n_samples, normalize, noi
     if n_noise and noise_offset is None:
         raise ValueError("templates_from_events: noise_samples needs noise_offset (samples before the origin)")
     offset = 0 if noise_offset is None else int(noise_offset)
-    if np.any(np.abs(origin) > 2**40) or abs(offset) > 2**40:
+    if np.any(np.abs(origin) > DAY_INDEX_LIMIT) or abs(offset) > DAY_INDEX_LIMIT:
         raise ValueError("templates_from_events: origin_samples and noise_offset must lie within +-2^40")
     return origin, mv, L, n_noise, offset
 
@@ -269,13 +270,13 @@ def picker_starts(starts, S):
     if st.ndim not in (1, 2) or (st.ndim == 2 and st.shape[1] != S) or (st.size and st.dtype.kind not in "iu"):
         raise ValueError(f"picker_batch: starts must be (E,) or (E, {S}) integers (samples); got {st.dtype} {st.shape}")
     st = st.astype(np.int64)
-    if np.any(np.abs(st) > 2**40):
+    if np.any(np.abs(st) > DAY_INDEX_LIMIT):
         raise ValueError("picker_batch: starts must lie within +-2^40")
     return np.array(np.broadcast_to(st[:, None] if st.ndim == 1 else st, (len(st), S)), dtype=np.int64, order="C")
 
 
 RESAMPLE_MAX_RATE = 64                       # max(up, down) after the reduction by their gcd
-RESAMPLE_INDEX_LIMIT = 2**40                 # n_in * max(up, down) stays below it
+RESAMPLE_INDEX_LIMIT = DAY_INDEX_LIMIT        # n_in * max(up, down) stays below it
 
 
 def resample_poly_factors(up, down):

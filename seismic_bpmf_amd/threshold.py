@@ -7,8 +7,6 @@ BPMF/libc.c:516-673) for every row of a CC matrix that is already in HBM (the ou
 records come back to the host, where :func:`seismic_bpmf_amd.postprocess.select_cc_indexes`-style
 merging runs on a few thousand entries instead of millions of samples.
 """
-import ctypes as C
-
 import numpy as np
 
 from . import _lib
@@ -41,9 +39,6 @@ class ThresholdGPU:
         self._ws = None
         self.mad_workspace_limit = 4 << 30      # bytes of workspace per call of the MAD threshold (the rank tables: n / 32 bytes per row)
 
-    def _stream(self):
-        return C.c_void_p(self.torch.cuda.current_stream(self.device).cuda_stream)
-
     def time_dependent_threshold(self, cc, sliding_window_samp, num_dev, overlap=0.66,
                                  white_noise=None, expand=False):
         """cc: (rows, n) float32 device tensor.  Returns (thr_windows (rows, n_win), full or None)."""
@@ -65,12 +60,8 @@ class ThresholdGPU:
             self._ws = t.empty(nbytes, dtype=t.uint8, device=self.device)
         thr_win = t.empty((rows, n_win), dtype=t.float32, device=self.device)
         full = t.empty((rows, n), dtype=t.float32, device=self.device) if expand else None
-        with t.cuda.device(self.device):
-            rc = self.lib.bpmf_tdt_rms_dev(cc.data_ptr(), g.data_ptr(), float(num_dev), rows, n, half,
-                                           shift, self._ws.data_ptr(), self._ws.numel(),
-                                           self._stream(), thr_win.data_ptr(),
-                                           full.data_ptr() if expand else None)
-        _lib.check(rc, "bpmf_tdt_rms_dev")
+        _lib.call("bpmf_tdt_rms_dev", self.device, cc, g, float(num_dev), rows, n, half, shift, self._ws,
+                  self._ws.numel(), _lib.STREAM, thr_win, full)
         self._keep = (cc, g)
         return thr_win, full
 
@@ -112,14 +103,11 @@ class ThresholdGPU:
             self._ws = t.empty(nbytes, dtype=t.uint8, device=self.device)
         thr_win = t.empty((rows, n_win), dtype=t.float32, device=self.device)
         full = t.empty((rows, n), dtype=t.float32, device=self.device) if (expand or single) else None
-        with t.cuda.device(self.device):
-            for r0 in range(0, rows, chunk):
-                nr = min(chunk, rows - r0)
-                rc = self.lib.bpmf_tdt_mad_dev(x[r0:].data_ptr(), wn.data_ptr() if wn.numel() else None, wn.numel(),
-                                               float(num_dev), nr, n, W, shift, self._ws.data_ptr(),
-                                               self._ws.numel(), self._stream(), thr_win[r0:].data_ptr(),
-                                               full[r0:].data_ptr() if full is not None else None, None)
-                _lib.check(rc, "bpmf_tdt_mad_dev")
+        for r0 in range(0, rows, chunk):
+            nr = min(chunk, rows - r0)
+            _lib.call("bpmf_tdt_mad_dev", self.device, x[r0:], wn if wn.numel() else None, wn.numel(), float(num_dev),
+                      nr, n, W, shift, self._ws, self._ws.numel(), _lib.STREAM, thr_win[r0:],
+                      None if full is None else full[r0:], None)
         self._keep = (x, wn)
         return full[0] if single else (thr_win, full)
 
@@ -142,19 +130,14 @@ class ThresholdGPU:
         while True:
             count = t.zeros(1, dtype=t.int32, device=self.device)
             rec = t.empty((capacity, 4), dtype=t.int32, device=self.device)
-            with t.cuda.device(self.device):
-                if kind == "rms":
-                    rc = self.lib.bpmf_extract_candidates_dev(
-                        cc.data_ptr(), thr_windows.data_ptr(), cap.data_ptr() if cap is not None else None,
-                        rows, n, half, shift, capacity, self._stream(), count.data_ptr(), rec.data_ptr())
-                elif kind == "mad":
-                    rc = self.lib.bpmf_extract_candidates_mad_dev(
-                        cc.data_ptr(), thr_windows.data_ptr(), cap.data_ptr() if cap is not None else None,
-                        rows, n, int(sliding_window_samp), shift, capacity, self._stream(), count.data_ptr(),
-                        rec.data_ptr())
-                else:
-                    raise ValueError("kind must be 'rms' or 'mad'")
-            _lib.check(rc, "bpmf_extract_candidates_dev")
+            if kind == "rms":
+                _lib.call("bpmf_extract_candidates_dev", self.device, cc, thr_windows, cap, rows, n, half, shift,
+                          capacity, _lib.STREAM, count, rec)
+            elif kind == "mad":
+                _lib.call("bpmf_extract_candidates_mad_dev", self.device, cc, thr_windows, cap, rows, n,
+                          int(sliding_window_samp), shift, capacity, _lib.STREAM, count, rec)
+            else:
+                raise ValueError("kind must be 'rms' or 'mad'")
             n_found = int(count.item())
             if n_found <= capacity:
                 break
@@ -181,9 +164,6 @@ class BeamDetectorGPU:
         self.device = torch.device("cuda", torch.cuda.current_device() if device is None else device)
         self.lib = _lib.lib()
 
-    def _stream(self):
-        return C.c_void_p(self.torch.cuda.current_stream(self.device).cuda_stream)
-
     def window_stats(self, beam, window, overlap=0.75):
         """(median, mad) float32 arrays of n_windows + 2 entries; entries 1 .. n_windows hold
         np.median / MAD of the windows [q*shift, min(n, q*shift + window)), the two end entries
@@ -198,10 +178,7 @@ class BeamDetectorGPU:
             raise ValueError("series shorter than the sliding window")
         med = t.zeros(nw + 2, dtype=t.float32, device=self.device)
         mad = t.zeros(nw + 2, dtype=t.float32, device=self.device)
-        with t.cuda.device(self.device):
-            rc = self.lib.bpmf_bp_window_stats_dev(x.data_ptr(), n, window, shift, self._stream(),
-                                                   med.data_ptr(), mad.data_ptr())
-        _lib.check(rc, "bpmf_bp_window_stats_dev")
+        _lib.call("bpmf_bp_window_stats_dev", self.device, x, n, window, shift, _lib.STREAM, med, mad)
         return med.cpu().numpy(), mad.cpu().numpy()
 
     def extract_peaks(self, beam, sources, floor, capacity=1 << 18):
@@ -214,11 +191,8 @@ class BeamDetectorGPU:
         while True:
             count = t.zeros(1, dtype=t.int32, device=self.device)
             rec = t.empty((capacity, 4), dtype=t.int32, device=self.device)
-            with t.cuda.device(self.device):
-                rc = self.lib.bpmf_bp_extract_peaks_dev(
-                    x.data_ptr(), src.data_ptr() if src is not None else None, n, float(floor),
-                    capacity, self._stream(), count.data_ptr(), rec.data_ptr())
-            _lib.check(rc, "bpmf_bp_extract_peaks_dev")
+            _lib.call("bpmf_bp_extract_peaks_dev", self.device, x, src, n, float(floor), capacity, _lib.STREAM, count,
+                      rec)
             found = int(count.item())
             if found <= capacity:
                 break

@@ -25,6 +25,39 @@ from .matched_filter import MatchedFilterGPU
 from .threshold import ThresholdGPU
 
 
+def _gpu_tensor(name, what, t, definition):
+    """The refusal every wrapper of a device entry point opens with; `definition` names what to use on the host."""
+    import torch
+    if not isinstance(t, torch.Tensor) or not t.is_cuda:
+        raise ValueError(f"{name}: {what} must be a tensor on the GPU (there is no CPU path; {definition})")
+
+
+def _day(name, data_dev, definition):
+    """The refusals of a wrapper that takes the (S, C, N) day in HBM; returns (S, C, N, device)."""
+    _gpu_tensor(name, "data_dev", data_dev, definition)
+    if data_dev.dim() != 3:
+        raise ValueError(f"{name}: data_dev must be (S, C, N)")
+    S, Cc, N = (int(v) for v in data_dev.shape)
+    return S, Cc, N, data_dev.device
+
+
+def _window_starts(starts, S):
+    """`starts` of a batch of day windows, a tensor or an array, as (E, S) int64 on the host (pp.picker_starts)."""
+    import torch
+    if isinstance(starts, torch.Tensor):
+        starts = starts.detach().cpu().numpy()
+    return pp.picker_starts(starts, S)
+
+
+def _slab_workspace_bytes(need, rows, workspace_bytes, refusal):
+    """Bytes of the workspace of an entry point that takes its rows in slabs of a multiple of 64: min(the caller's
+    `workspace_bytes`, need(rows)).  ValueError(refusal(workspace_bytes, need(64))) where 64 rows do not fit."""
+    workspace_bytes, least = int(workspace_bytes), int(need(64))
+    if workspace_bytes < least:
+        raise ValueError(refusal(workspace_bytes, least))
+    return min(workspace_bytes, int(need(rows)))
+
+
 def search_window(moveouts_t, minimum_interevent_samp, step):
     """Merge distance between detections of one template, BPMF/similarity_search.py:651-659:
     the median over stations of the moveout spread between components, bounded by 1-10x the
@@ -64,7 +97,6 @@ def row_excess_kurtosis(cc):
     (BPMF/similarity_search.py:633-642): float32 moments in NumPy's summation order
     (csrc/stats.hip, bpmf_row_kurtosis_parts_dev; host mirror postprocess.excess_kurtosis_f32).  Returns a
     float32 NumPy array; NaN for a constant row, like SciPy."""
-    import ctypes as C
     import torch
     from . import _lib
     x = cc if cc.dim() == 2 else cc.reshape(1, -1)
@@ -76,13 +108,9 @@ def row_excess_kurtosis(cc):
     parts = torch.empty((rows, 3), dtype=torch.float32, device=x.device)
     chunk = min(rows, 65535)                   # rows per call of the library (its gridDim.y)
     ws = torch.empty(lib.bpmf_row_kurtosis_workspace_bytes(chunk, n), dtype=torch.uint8, device=x.device)
-    with torch.cuda.device(x.device):
-        for r0 in range(0, rows, chunk):
-            rc = lib.bpmf_row_kurtosis_parts_dev(C.c_void_p(x[r0:].data_ptr()), min(chunk, rows - r0), n,
-                                                 C.c_void_p(ws.data_ptr()), ws.numel(),
-                                                 C.c_void_p(torch.cuda.current_stream(x.device).cuda_stream),
-                                                 None, C.c_void_p(parts[r0:].data_ptr()))
-            _lib.check(rc, "bpmf_row_kurtosis_parts_dev")
+    for r0 in range(0, rows, chunk):
+        _lib.call("bpmf_row_kurtosis_parts_dev", x.device, x[r0:], min(chunk, rows - r0), n, ws, ws.numel(),
+                  _lib.STREAM, None, parts[r0:])
     # (mean, m2, m4) per row from the device; the last expression on NumPy scalars, as SciPy evaluates it on one
     # series -- postprocess.kurtosis_from_moments_f32 says why that is not the same as finishing on the device
     from .postprocess import kurtosis_from_moments_rows
@@ -107,7 +135,6 @@ def validate_detections(cc, merged, bounds, c_index, c_thr, *, n_dev, threshold_
     `c_index` / `c_thr` / `bounds`: the candidate arrays of cc_detections (the threshold AT a detection is the
     candidate record's).  Level and fractions as the reference computes them: float32 threshold / n_dev (x 1.48),
     float32 compares, count / float(len) in float64."""
-    import ctypes as C
     import torch
     from . import _lib
     n = int(cc.shape[-1])
@@ -138,14 +165,8 @@ def validate_detections(cc, merged, bounds, c_index, c_thr, *, n_dev, threshold_
     d_lvl = torch.as_tensor(lvl, device=dev)
     below = torch.empty((len(rows), 2), dtype=torch.int32, device=dev)
     x = cc if cc.is_contiguous() else cc.contiguous()
-    with torch.cuda.device(dev):
-        rc = _lib.lib().bpmf_count_below_dev(C.c_void_p(x.data_ptr()), int(x.shape[0]), n, len(rows),
-                                             C.c_void_p(d_rows.data_ptr()), C.c_void_p(d_start.data_ptr()),
-                                             C.c_void_p(d_nl.data_ptr()), C.c_void_p(d_nr.data_ptr()),
-                                             C.c_void_p(d_lvl.data_ptr()),
-                                             C.c_void_p(torch.cuda.current_stream(dev).cuda_stream),
-                                             C.c_void_p(below.data_ptr()))
-    _lib.check(rc, "bpmf_count_below_dev")
+    _lib.call("bpmf_count_below_dev", dev, x, int(x.shape[0]), n, len(rows), d_rows, d_start, d_nl, d_nr, d_lvl,
+              _lib.STREAM, below)
     below = below.cpu().numpy().astype(np.float64)
     frac = np.minimum(below[:, 0] / float(n_left), below[:, 1] / float(n_right))
     keep = ~(frac < cut)
@@ -168,17 +189,10 @@ def peak_amplitudes(data_dev, rows, samples, moveouts, *, offset, duration, data
     the moveout of the phase the reference's `phase_on_comp_peak_amp` names; `offset` / `duration` in samples;
     `data_norm` (S, C) or None.  Uploads the detection records and the moveout table, downloads D * S * C floats.
     Returns a (D, S, C) float32 NumPy array."""
-    import ctypes as C
     import torch
     from . import _lib
-    if not isinstance(data_dev, torch.Tensor) or not data_dev.is_cuda:
-        raise ValueError("peak_amplitudes: data_dev must be a tensor on the GPU (there is no CPU path; the host mirror "
-                         "is postprocess.peak_amplitudes_host)")
-    if data_dev.dim() != 3:
-        raise ValueError("peak_amplitudes: data_dev must be (S, C, N)")
-    dev = data_dev.device
+    S, Cc, N, dev = _day("peak_amplitudes", data_dev, "the host mirror is postprocess.peak_amplitudes_host")
     x = data_dev.to(dtype=torch.float32).contiguous()
-    S, Cc, N = (int(v) for v in x.shape)
     rows = np.ascontiguousarray(np.asarray(rows).reshape(-1), dtype=np.int32)
     samples = np.ascontiguousarray(np.asarray(samples).reshape(-1), dtype=np.int64)
     if rows.shape != samples.shape:
@@ -201,13 +215,8 @@ def peak_amplitudes(data_dev, rows, samples, moveouts, *, offset, duration, data
     d_mv = torch.as_tensor(mv, device=dev)
     d_norm = None if norm is None else torch.as_tensor(norm, device=dev)
     out = torch.empty((D, S, Cc), dtype=torch.float32, device=dev)
-    with torch.cuda.device(dev):
-        rc = _lib.lib().bpmf_peak_amplitudes_dev(
-            C.c_void_p(x.data_ptr()), S, Cc, N, D, C.c_void_p(d_rows.data_ptr()), C.c_void_p(d_samples.data_ptr()),
-            C.c_void_p(d_mv.data_ptr()), T, int(offset), int(duration),
-            None if d_norm is None else C.c_void_p(d_norm.data_ptr()),
-            C.c_void_p(torch.cuda.current_stream(dev).cuda_stream), C.c_void_p(out.data_ptr()))
-    _lib.check(rc, "bpmf_peak_amplitudes_dev")
+    _lib.call("bpmf_peak_amplitudes_dev", dev, x, S, Cc, N, D, d_rows, d_samples, d_mv, T, int(offset), int(duration),
+              d_norm, _lib.STREAM, out)
     return out.cpu().numpy()
 
 
@@ -229,15 +238,10 @@ def templates_from_events(data_dev, origin_samples, moveouts, n_samples, *, norm
     normalize_weights(weights_channels_simple(available [& complete when `require_complete`], min_channels,
     min_stations)).  On the host: `available`, `complete` (E, S, C) bool, `norm` (E, S, C) float32, `snr` (E, S, C)
     float32 or None."""
-    import ctypes as C
     import torch
     from . import _lib
-    if not isinstance(data_dev, torch.Tensor) or not data_dev.is_cuda:
-        raise ValueError("templates_from_events: data_dev must be a tensor on the GPU (there is no CPU path; the "
-                         "definition on the host is postprocess.templates_from_events_host)")
-    if data_dev.dim() != 3:
-        raise ValueError("templates_from_events: data_dev must be (S, C, N)")
-    S, Cc, N = (int(v) for v in data_dev.shape)
+    S, Cc, N, dev = _day("templates_from_events", data_dev,
+                         "the definition on the host is postprocess.templates_from_events_host")
     if isinstance(moveouts, torch.Tensor):
         moveouts = moveouts.detach().cpu().numpy()
     if isinstance(origin_samples, torch.Tensor):
@@ -246,7 +250,6 @@ def templates_from_events(data_dev, origin_samples, moveouts, n_samples, *, norm
                                                            noise_offset, noise_samples)
     if N == 0:
         raise ValueError("templates_from_events: the day is empty")
-    dev = data_dev.device
     E = len(origin)
     with torch.cuda.device(dev):
         x = data_dev.to(dtype=torch.float32).contiguous()
@@ -257,13 +260,8 @@ def templates_from_events(data_dev, origin_samples, moveouts, n_samples, *, norm
         snr = torch.empty((E, S, Cc), dtype=torch.float32, device=dev) if n_noise else None
         if E:
             d_origin = torch.as_tensor(origin, device=dev)
-            rc = _lib.lib().bpmf_templates_from_events_dev(
-                C.c_void_p(x.data_ptr()), S, Cc, N, E, C.c_void_p(d_origin.data_ptr()), C.c_void_p(d_mv.data_ptr()),
-                L, {None: 0, "rms": 1, "max": 2}[normalize], offset, n_noise,
-                C.c_void_p(torch.cuda.current_stream(dev).cuda_stream), C.c_void_p(templates.data_ptr()),
-                C.c_void_p(norm.data_ptr()), C.c_void_p(flags.data_ptr()),
-                None if snr is None else C.c_void_p(snr.data_ptr()))
-            _lib.check(rc, "bpmf_templates_from_events_dev")
+            _lib.call("bpmf_templates_from_events_dev", dev, x, S, Cc, N, E, d_origin, d_mv, L,
+                      {None: 0, "rms": 1, "max": 2}[normalize], offset, n_noise, _lib.STREAM, templates, norm, flags, snr)
         flags_host = flags.cpu().numpy()
         available, complete = (flags_host & 1) != 0, (flags_host & 2) != 0
         present = available & complete if require_complete else available
@@ -300,7 +298,6 @@ def _normalize_checks(what, shape, n_rows, n, W, overlap, dtype):
 def _normalize_rows(what, x, n_rows, d_start, n, W, overlap, dtype, out_shape):
     """Checks on the host, then one bpmf_normalize_batch_dev launch on the current stream of x's device: rows
     (r, c) = x[r % S, c, start[r] + i] of the contiguous float32 (S, C, N) tensor `x`."""
-    import ctypes as C
     import torch
     from . import _lib
     S, Cc, N = (int(v) for v in x.shape)
@@ -311,11 +308,8 @@ def _normalize_rows(what, x, n_rows, d_start, n, W, overlap, dtype, out_shape):
         if n_rows == 0:
             return out
         nodes = torch.as_tensor(pp.normalize_batch_nodes(n, shift, n_windows), device=dev)
-        rc = _lib.lib().bpmf_normalize_batch_dev(
-            C.c_void_p(x.data_ptr()), S, Cc, N, n_rows, None if d_start is None else C.c_void_p(d_start.data_ptr()),
-            n, int(W), shift, C.c_void_p(nodes.data_ptr()), n_windows, int(dtype == torch.float64),
-            C.c_void_p(torch.cuda.current_stream(dev).cuda_stream), C.c_void_p(out.data_ptr()))
-        _lib.check(rc, "bpmf_normalize_batch_dev")
+        _lib.call("bpmf_normalize_batch_dev", dev, x, S, Cc, N, n_rows, d_start, n, int(W), shift, nodes, n_windows,
+                  int(dtype == torch.float64), _lib.STREAM, out)
     return out
 
 
@@ -333,9 +327,7 @@ def normalize_batch(x_dev, normalization_window_sample=3000, overlap=0.5, dtype=
     picker_batch(upsampling=, downsampling=) runs both on the windows of a day).  Out of scope: the model itself; the
     power-of-two reflect padding of tutorial/notebooks/6_relocate.ipynb cell 54; infinite samples."""
     import torch
-    if not isinstance(x_dev, torch.Tensor) or not x_dev.is_cuda:
-        raise ValueError("normalize_batch: x_dev must be a tensor on the GPU (there is no CPU path; the definition on "
-                         "the host is postprocess.normalize_batch_host)")
+    _gpu_tensor("normalize_batch", "x_dev", x_dev, "the definition on the host is postprocess.normalize_batch_host")
     if x_dev.dim() != 3:
         raise ValueError("normalize_batch: x_dev must be (R, C, n)")
     R, Cc, n = (int(v) for v in x_dev.shape)
@@ -365,7 +357,6 @@ def _resample_rows(what, x, n_rows, d_start, n_in, up, down):
     """Checks on the host, then one bpmf_resample_poly_dev launch on the current stream of x's device: rows
     (r, c) = x[r % S, c, start[r] + i], i < n_in, of the contiguous float32 (S, C, N) tensor `x`, resampled by the
     reduced up / down (not both 1).  Returns (n_rows, C, n_out) float32."""
-    import ctypes as C
     import torch
     from . import _lib
     S, Cc, N = (int(v) for v in x.shape)
@@ -376,11 +367,8 @@ def _resample_rows(what, x, n_rows, d_start, n_in, up, down):
         if n_rows == 0:
             return out
         d_table = torch.as_tensor(table, device=dev)
-        rc = _lib.lib().bpmf_resample_poly_dev(
-            C.c_void_p(x.data_ptr()), S, Cc, N, n_rows, None if d_start is None else C.c_void_p(d_start.data_ptr()),
-            n_in, up, down, C.c_void_p(d_table.data_ptr()), hp, n_pre_remove, n_out,
-            C.c_void_p(torch.cuda.current_stream(dev).cuda_stream), C.c_void_p(out.data_ptr()))
-        _lib.check(rc, "bpmf_resample_poly_dev")
+        _lib.call("bpmf_resample_poly_dev", dev, x, S, Cc, N, n_rows, d_start, n_in, up, down, d_table, hp,
+                  n_pre_remove, n_out, _lib.STREAM, out)
     return out
 
 
@@ -406,9 +394,7 @@ def resample_poly(x_dev, up, down):
 
     Out of scope: the other `padtype` and `window` arguments; float64 and complex input."""
     import torch
-    if not isinstance(x_dev, torch.Tensor) or not x_dev.is_cuda:
-        raise ValueError("resample_poly: x_dev must be a tensor on the GPU (there is no CPU path; the definition on "
-                         "the host is postprocess.resample_poly_host)")
+    _gpu_tensor("resample_poly", "x_dev", x_dev, "the definition on the host is postprocess.resample_poly_host")
     if x_dev.dim() < 1 or x_dev.dtype != torch.float32:
         raise ValueError(f"resample_poly: x_dev must be (..., n) float32; got {x_dev.dtype} {tuple(x_dev.shape)}")
     up, down = pp.resample_poly_factors(up, down)
@@ -452,15 +438,9 @@ def picker_batch(data_dev, starts, n_samples, *, normalization_window_sample=300
 
     Refusals (every one before any device call) and what is out of scope: see normalize_batch and resample_poly."""
     import torch
-    if not isinstance(data_dev, torch.Tensor) or not data_dev.is_cuda:
-        raise ValueError("picker_batch: data_dev must be a tensor on the GPU (there is no CPU path; the definition on "
-                         "the host is postprocess.normalize_batch_host of postprocess.picker_windows_host)")
-    if data_dev.dim() != 3:
-        raise ValueError("picker_batch: data_dev must be (S, C, N)")
-    S, Cc, N = (int(v) for v in data_dev.shape)
-    if isinstance(starts, torch.Tensor):
-        starts = starts.detach().cpu().numpy()
-    st = pp.picker_starts(starts, S)
+    S, Cc, N, dev = _day("picker_batch", data_dev, "the definition on the host is postprocess.normalize_batch_host of "
+                                                   "postprocess.picker_windows_host")
+    st = _window_starts(starts, S)
     n = int(n_samples)
     up, down = pp.resample_poly_factors(upsampling, downsampling)
     dtype = torch.float32 if dtype is None else dtype
@@ -469,7 +449,6 @@ def picker_batch(data_dev, starts, n_samples, *, normalization_window_sample=300
     if up != down:
         n_out = _resample_checks("picker_batch", (S, Cc, N), st.size, n, up, down)[0]
         _normalize_checks("picker_batch", (S, Cc, N), st.size, n_out, W, overlap, dtype)
-    dev = data_dev.device
     with torch.cuda.device(dev):
         x = data_dev.to(dtype=torch.float32).contiguous()
         d_start = torch.as_tensor(st.reshape(-1), device=dev) if st.size else None
@@ -493,12 +472,9 @@ def find_picks(proba_dev, threshold_P=0.6, threshold_S=0.6, max_picks=32, trunca
     RuntimeError, unless `truncate`: then its first max_picks picks are kept and `count` tells how many there were.
 
     Out of scope: find_peaks keywords other than the reference's defaults; infinite samples."""
-    import ctypes as C
     import torch
     from . import _lib
-    if not isinstance(proba_dev, torch.Tensor) or not proba_dev.is_cuda:
-        raise ValueError("find_picks: proba_dev must be a tensor on the GPU (there is no CPU path; the definition on "
-                         "the host is postprocess.find_picks_host)")
+    _gpu_tensor("find_picks", "proba_dev", proba_dev, "the definition on the host is postprocess.find_picks_host")
     if proba_dev.dim() < 2 or proba_dev.shape[-2] != 2:
         raise ValueError(f"find_picks: proba_dev must be (..., 2, n); got {tuple(proba_dev.shape)}")
     n, max_picks = int(proba_dev.shape[-1]), int(max_picks)
@@ -522,12 +498,8 @@ def find_picks(proba_dev, threshold_P=0.6, threshold_S=0.6, max_picks=32, trunca
         std = torch.empty(lead + (max_picks,), dtype=torch.float64, device=dev)
         index = torch.empty(lead + (max_picks,), dtype=torch.int32, device=dev)
         if T:
-            rc = _lib.lib().bpmf_find_picks_dev(
-                C.c_void_p(x.data_ptr()), T, n, thresholds[0], thresholds[1], max_picks,
-                C.c_void_p(torch.cuda.current_stream(dev).cuda_stream), C.c_void_p(count.data_ptr()),
-                C.c_void_p(value.data_ptr()), C.c_void_p(mean.data_ptr()), C.c_void_p(std.data_ptr()),
-                C.c_void_p(index.data_ptr()))
-            _lib.check(rc, "bpmf_find_picks_dev")
+            _lib.call("bpmf_find_picks_dev", dev, x, T, n, thresholds[0], thresholds[1], max_picks, _lib.STREAM, count,
+                      value, mean, std, index)
         out = {"count": count.cpu().numpy(), "value": value.cpu().numpy(), "mean": mean.cpu().numpy(),
                "std": std.cpu().numpy(), "index": index.cpu().numpy()}
     if not truncate and T and out["count"].max() > max_picks:
@@ -549,10 +521,8 @@ def pick_events(proba_dev, *, threshold_P, threshold_S, buffer_length, prior=Non
     sr * upsampling / downsampling, as BPMF/dataset.py:1807 sets it, and so are buffer_length, prior and search_win_samp.
 
     Out of scope: absolute pick times and the pandas table; see find_picks and normalize_batch for the rest."""
-    import torch
-    if not isinstance(proba_dev, torch.Tensor) or not proba_dev.is_cuda:
-        raise ValueError("pick_events: proba_dev must be a tensor on the GPU (there is no CPU path; the definitions on "
-                         "the host are postprocess.find_picks_host and postprocess.get_picks_host)")
+    _gpu_tensor("pick_events", "proba_dev", proba_dev,
+                "the definitions on the host are postprocess.find_picks_host and postprocess.get_picks_host")
     if proba_dev.dim() != 4 or proba_dev.shape[2] != 2:
         raise ValueError(f"pick_events: proba_dev must be (E, S, 2, n); got {tuple(proba_dev.shape)}")
     E, S = int(proba_dev.shape[0]), int(proba_dev.shape[1])
@@ -586,12 +556,9 @@ def bandpass_filter(x_dev, sos=None, *, freqmin=None, freqmax=None, f_Nyq=None, 
     float64 by default as the reference returns it, or `dtype` torch.float32.  The definition is
     postprocess.bandpass_filter_host; without detrend and taper the float64 result equals it (and SciPy's sosfilt) bit
     for bit."""
-    import ctypes as C
     import torch
     from . import _lib
-    if not isinstance(x_dev, torch.Tensor) or not x_dev.is_cuda:
-        raise ValueError("bandpass_filter: x_dev must be a tensor on the GPU (there is no CPU path; the definition on "
-                         "the host is postprocess.bandpass_filter_host)")
+    _gpu_tensor("bandpass_filter", "x_dev", x_dev, "the definition on the host is postprocess.bandpass_filter_host")
     if x_dev.dim() < 1 or x_dev.dtype not in (torch.float32, torch.float64):
         raise ValueError("bandpass_filter: x_dev must be a float32 or float64 tensor (..., m)")
     dtype = torch.float64 if dtype is None else dtype
@@ -615,11 +582,8 @@ def bandpass_filter(x_dev, sos=None, *, freqmin=None, freqmax=None, f_Nyq=None, 
         out_f64, zp = int(dtype == torch.float64), int(bool(zerophase))
         need = _lib.lib().bpmf_bandpass_rows_workspace_bytes(rows, m, zp, out_f64)
         ws = torch.empty((need,), dtype=torch.uint8, device=dev) if need else None
-        rc = _lib.lib().bpmf_bandpass_rows_dev(
-            C.c_void_p(x.data_ptr()), int(x.dtype == torch.float64), rows, m, C.c_void_p(d_sos.data_ptr()),
-            table.shape[0], int(bool(detrend)), alpha, zp, out_f64, None if ws is None else C.c_void_p(ws.data_ptr()),
-            need, C.c_void_p(torch.cuda.current_stream(dev).cuda_stream), C.c_void_p(out.data_ptr()))
-        _lib.check(rc, "bpmf_bandpass_rows_dev")
+        _lib.call("bpmf_bandpass_rows_dev", dev, x, int(x.dtype == torch.float64), rows, m, d_sos, table.shape[0],
+                  int(bool(detrend)), alpha, zp, out_f64, ws, need, _lib.STREAM, out)
     return out
 
 
@@ -650,9 +614,7 @@ def svdwf_stack(x_dev, offsets=None, *, expl_var=0.4, max_singular_values=5, wie
     import ctypes as C
     import torch
     from . import _lib
-    if not isinstance(x_dev, torch.Tensor) or not x_dev.is_cuda:
-        raise ValueError("svdwf_stack: x_dev must be a tensor on the GPU (there is no CPU path; the definition on the "
-                         "host is postprocess.svdwf_stack_host)")
+    _gpu_tensor("svdwf_stack", "x_dev", x_dev, "the definition on the host is postprocess.svdwf_stack_host")
     if x_dev.dim() != 4:
         raise ValueError("svdwf_stack: x_dev must be (N, S, C, m)")
     N, S, Cc, m = (int(v) for v in x_dev.shape)
@@ -695,14 +657,9 @@ def svdwf_stack(x_dev, offsets=None, *, expl_var=0.4, max_singular_values=5, wie
                       and workspace.is_contiguous() and workspace.data_ptr() % 256 == 0):
                 raise ValueError("svdwf_stack: workspace must be a contiguous uint8 tensor on the GPU, aligned to 256")
             d_sos = None if table is None else torch.as_tensor(table, device=dev)
-            rc = lib.bpmf_svdwf_stack_dev(
-                C.c_void_p(x.data_ptr()), off.ctypes.data_as(C.POINTER(C.c_int64)), G, S, Cc, m, expl_var, kmax,
-                0 if w is None else w, None if d_sos is None else C.c_void_p(d_sos.data_ptr()),
-                0 if table is None else table.shape[0], alpha, C.c_void_p(workspace.data_ptr()),
-                int(workspace.numel()), C.c_void_p(torch.cuda.current_stream(dev).cuda_stream),
-                None if filtered is None else C.c_void_p(filtered.data_ptr()), C.c_void_p(stack.data_ptr()),
-                C.c_void_p(n_singular.data_ptr()), C.c_void_p(status.data_ptr()))
-            _lib.check(rc, "bpmf_svdwf_stack_dev")
+            _lib.call("bpmf_svdwf_stack_dev", dev, x, off.ctypes.data_as(C.POINTER(C.c_int64)), G, S, Cc, m, expl_var,
+                      kmax, 0 if w is None else w, d_sos, 0 if table is None else table.shape[0], alpha, workspace,
+                      int(workspace.numel()), _lib.STREAM, filtered, stack, n_singular, status)
         n_singular, status = n_singular.cpu().numpy(), status.cpu().numpy()
     if strict and status.any():
         bad = np.argwhere(status != 0)[0]
@@ -750,19 +707,13 @@ def multiband_spectra(data_dev, starts, n_samples, frequency_bands, *, sr, buffe
     import ctypes as C
     import torch
     from . import _lib
-    if not isinstance(data_dev, torch.Tensor) or not data_dev.is_cuda:
-        raise ValueError("multiband_spectra: data_dev must be a tensor on the GPU (there is no CPU path; the definition "
-                         "on the host is postprocess.multiband_spectrum_host of postprocess.multiband_windows_host)")
-    if data_dev.dim() != 3:
-        raise ValueError("multiband_spectra: data_dev must be (S, C, N)")
-    S, Cc, N = (int(v) for v in data_dev.shape)
+    S, Cc, N, dev = _day("multiband_spectra", data_dev, "the definition on the host is "
+                         "postprocess.multiband_spectrum_host of postprocess.multiband_windows_host")
     n = int(n_samples)
     if not 1 <= n <= MULTIBAND_MAX_SAMPLES:
         raise ValueError(f"multiband_spectra: windows of 1 .. {MULTIBAND_MAX_SAMPLES} samples; got {n}")
     plan = pp.multiband_plan(n, frequency_bands, sr, buffer_seconds, corners)
-    if isinstance(starts, torch.Tensor):
-        starts = starts.detach().cpu().numpy()
-    st = pp.picker_starts(starts, S)
+    st = _window_starts(starts, S)
     E, B = len(st), len(plan["bands"])
     if S * Cc == 0 or N == 0:
         raise ValueError("multiband_spectra: the data are empty")
@@ -770,32 +721,24 @@ def multiband_spectra(data_dev, starts, n_samples, frequency_bands, *, sr, buffe
     if rows * B >= 2**31:
         raise ValueError(f"multiband_spectra: {rows} rows x {B} bands in one call; fewer than 2^31 values fit")
     n_active = int((~plan["skip"]).sum())
-    least = int(_lib.lib().bpmf_multiband_workspace_bytes(64, n, n_active))
-    workspace_bytes = int(workspace_bytes)
-    if workspace_bytes < least:
-        raise ValueError(f"multiband_spectra: workspace_bytes = {workspace_bytes}; 64 rows of {n} samples and "
-                         f"{n_active} active bands take {least}")
-    dev = data_dev.device
+    n_bytes = _slab_workspace_bytes(
+        lambda r: _lib.lib().bpmf_multiband_workspace_bytes(r, n, n_active), rows, workspace_bytes,
+        lambda given, least: f"multiband_spectra: workspace_bytes = {given}; 64 rows of {n} samples and {n_active} "
+                             f"active bands take {least}")
     with torch.cuda.device(dev):
         freq = torch.as_tensor(plan["freq"], device=dev)
         spectra = torch.empty((E, S, Cc, B), dtype=torch.float64, device=dev)
         valid = torch.empty((E, S), dtype=torch.uint8, device=dev)
         if E:
-            lib = _lib.lib()
             x = data_dev.to(dtype=torch.float32).contiguous()
             d_start = torch.as_tensor(st.reshape(-1), device=dev)
             d_sos = torch.as_tensor(np.ascontiguousarray(plan["sos"]), device=dev)
-            n_bytes = min(workspace_bytes, int(lib.bpmf_multiband_workspace_bytes(rows, n, n_active)))
             ws = torch.empty((n_bytes,), dtype=torch.uint8, device=dev)
             bandwidth = np.ascontiguousarray(plan["bandwidth"], dtype=np.float64)
             skip = np.ascontiguousarray(plan["skip"], dtype=np.uint8)
-            rc = lib.bpmf_multiband_spectrum_dev(
-                C.c_void_p(x.data_ptr()), S, Cc, N, st.size, C.c_void_p(d_start.data_ptr()), n, plan["taper"],
-                plan["buffer"], C.c_void_p(d_sos.data_ptr()), B, int(plan["sos"].shape[1]),
-                bandwidth.ctypes.data_as(C.POINTER(C.c_double)), skip.ctypes.data_as(C.POINTER(C.c_uint8)),
-                C.c_void_p(ws.data_ptr()), n_bytes, C.c_void_p(torch.cuda.current_stream(dev).cuda_stream),
-                C.c_void_p(spectra.data_ptr()), C.c_void_p(valid.data_ptr()))
-            _lib.check(rc, "bpmf_multiband_spectrum_dev")
+            _lib.call("bpmf_multiband_spectrum_dev", dev, x, S, Cc, N, st.size, d_start, n, plan["taper"], plan["buffer"],
+                      d_sos, B, int(plan["sos"].shape[1]), bandwidth.ctypes.data_as(C.POINTER(C.c_double)),
+                      skip.ctypes.data_as(C.POINTER(C.c_uint8)), ws, n_bytes, _lib.STREAM, spectra, valid)
         if multi_component:
             total = torch.zeros((E, S, B), dtype=torch.float64, device=dev)
             for c in range(Cc):                                        # in component order, as the reference adds
@@ -868,20 +811,13 @@ def fft_spectra(data_dev, starts, n_samples, *, sr, frequencies=None, alpha=0.05
     approximate_moment_magnitudes (source_spectra runs both); `integrate` / `differentiate` are integrate_spectra and
     differentiate_spectra.  Out of scope: response removal, float64 days, a `spectrum_func` callable, and the model
     fit (fit_average_spectrum: see network_average_spectra)."""
-    import ctypes as C
     import torch
     from . import _lib
-    if not isinstance(data_dev, torch.Tensor) or not data_dev.is_cuda:
-        raise ValueError("fft_spectra: data_dev must be a tensor on the GPU (there is no CPU path; the definition on "
-                         "the host is postprocess.fft_spectrum_host of postprocess.fft_windows_host)")
-    if data_dev.dim() != 3:
-        raise ValueError("fft_spectra: data_dev must be (S, C, N)")
-    S, Cc, N = (int(v) for v in data_dev.shape)
+    S, Cc, N, dev = _day("fft_spectra", data_dev, "the definition on the host is postprocess.fft_spectrum_host of "
+                                                  "postprocess.fft_windows_host")
     n = int(n_samples)
     plan = pp.fft_spectrum_plan(n, sr, frequencies, alpha, taper)
-    if isinstance(starts, torch.Tensor):
-        starts = starts.detach().cpu().numpy()
-    st = pp.picker_starts(starts, S)
+    st = _window_starts(starts, S)
     E, K_b = len(st), len(plan["bins"])
     F = 0 if frequencies is None else len(plan["frequencies"])
     if S * Cc == 0 or N == 0:
@@ -892,12 +828,10 @@ def fft_spectra(data_dev, starts, n_samples, *, sr, frequencies=None, alpha=0.05
     rows = st.size * Cc
     if rows * max(2 * K_b, F) >= 2**31:
         raise ValueError(f"fft_spectra: {rows} rows x {max(2 * K_b, F)} values in one call; fewer than 2^31 values fit")
-    least = int(_lib.lib().bpmf_fft_spectrum_workspace_size(64, n, K_b, F))
-    workspace_bytes = int(workspace_bytes)
-    if workspace_bytes < least:
-        raise ValueError(f"fft_spectra: workspace_bytes = {workspace_bytes}; 64 rows of {n} samples and {K_b} bins "
-                         f"take {least}")
-    dev = data_dev.device
+    n_bytes = _slab_workspace_bytes(
+        lambda r: _lib.lib().bpmf_fft_spectrum_workspace_size(r, n, K_b, F), rows, workspace_bytes,
+        lambda given, least: f"fft_spectra: workspace_bytes = {given}; 64 rows of {n} samples and {K_b} bins take "
+                             f"{least}")
     with torch.cuda.device(dev):
         freq = torch.as_tensor(plan["frequencies"] if F else plan["freq"], device=dev)
         lead = (E, S) if multi else (E, S, Cc)
@@ -907,7 +841,6 @@ def fft_spectra(data_dev, starts, n_samples, *, sr, frequencies=None, alpha=0.05
             spectra = torch.empty(lead + (K_b,), dtype=torch.float64 if multi else torch.complex128, device=dev)
         valid = torch.empty((E, S), dtype=torch.uint8, device=dev)
         if E:
-            lib = _lib.lib()
             x = data_dev.to(dtype=torch.float32).contiguous()
             up = {k: torch.as_tensor(np.ascontiguousarray(v), device=dev) for k, v in (
                 ("starts", st.reshape(-1)), ("taper", plan["taper"]), ("twiddles", np.array(pp.dft_twiddles(n))),
@@ -915,15 +848,10 @@ def fft_spectra(data_dev, starts, n_samples, *, sr, frequencies=None, alpha=0.05
             if F:
                 up.update({k: torch.as_tensor(np.ascontiguousarray(plan[k]), device=dev)
                            for k in ("pair", "dx", "span", "flags")})
-            ptr = {k: C.c_void_p(v.data_ptr()) for k, v in up.items()}
-            n_bytes = min(workspace_bytes, int(lib.bpmf_fft_spectrum_workspace_size(rows, n, K_b, F)))
             ws = torch.empty((n_bytes,), dtype=torch.uint8, device=dev)
-            rc = lib.bpmf_fft_spectrum_dev(
-                C.c_void_p(x.data_ptr()), S, Cc, N, st.size, ptr["starts"], n, ptr["taper"], ptr["twiddles"],
-                plan["delta"], ptr["bins"], K_b, ptr.get("pair"), ptr.get("dx"), ptr.get("span"), ptr.get("flags"), F,
-                int(multi), C.c_void_p(ws.data_ptr()), n_bytes, C.c_void_p(torch.cuda.current_stream(dev).cuda_stream),
-                C.c_void_p(spectra.data_ptr()), C.c_void_p(valid.data_ptr()))
-            _lib.check(rc, "bpmf_fft_spectrum_dev")
+            _lib.call("bpmf_fft_spectrum_dev", dev, x, S, Cc, N, st.size, up["starts"], n, up["taper"], up["twiddles"],
+                      plan["delta"], up["bins"], K_b, up.get("pair"), up.get("dx"), up.get("span"), up.get("flags"), F,
+                      int(multi), ws, n_bytes, _lib.STREAM, spectra, valid)
         return spectra, freq, valid.to(torch.bool)
 
 
@@ -994,7 +922,6 @@ def network_average_spectra(signal, noise, *, phase, valid, noise_valid=None, di
     Refusals (ValueError, before any device call): spectra that are no float64 tensors of equal shape (E, S, F) or
     (E, S, C, F) on one GPU; S * C above 256; F above 1024; E S C F >= 2^31; a per-station table that is not (E, S);
     a phase, reduce or attenuation that is not one of the two; frequencies that are not (F,) finite numbers."""
-    import ctypes as C
     import torch
     from . import _lib
     name = "network_average_spectra"
@@ -1029,15 +956,13 @@ def network_average_spectra(signal, noise, *, phase, valid, noise_valid=None, di
                "num_valid": torch.empty((E, F), dtype=torch.int32, device=dev),
                "used": torch.empty((E, S), dtype=torch.uint8, device=dev)}
         if E:
-            p = {key: C.c_void_p(t.data_ptr()) for key, t in list(tab.items()) + list(out.items())}
-            rc = _lib.lib().bpmf_source_spectra_dev(
-                C.c_void_p(x.data_ptr()), C.c_void_p(z.data_ptr()), p["valid"], p["noise_valid"], p["dist"], None,
-                p["tt"], p["err"], p["f"], p["q"], E, S, Cc, F, SS_SNR | SS_CORRECT | SS_AVERAGE, constant, radiation,
-                float(snr_threshold), float(max_relative_distance_err_pct), int(min_num_valid_channels_per_freq_bin),
-                int(bool(average_log)), int(reduce == "median"), 1, 0, 0.0, 0.0, 0,
-                C.c_void_p(torch.cuda.current_stream(dev).cuda_stream), p["corrected"], p["snr"], p["average"],
-                p["mask"], p["std"], p["num_valid"], p["used"], None, None, None, None, None)
-            _lib.check(rc, "bpmf_source_spectra_dev")
+            p = {**tab, **out}
+            _lib.call("bpmf_source_spectra_dev", dev, x, z, p["valid"], p["noise_valid"], p["dist"], None, p["tt"],
+                      p["err"], p["f"], p["q"], E, S, Cc, F, SS_SNR | SS_CORRECT | SS_AVERAGE, constant, radiation,
+                      float(snr_threshold), float(max_relative_distance_err_pct),
+                      int(min_num_valid_channels_per_freq_bin), int(bool(average_log)), int(reduce == "median"), 1, 0,
+                      0.0, 0.0, 0, _lib.STREAM, p["corrected"], p["snr"], p["average"], p["mask"], p["std"],
+                      p["num_valid"], p["used"], None, None, None, None, None)
         out["mask"], out["used"] = out["mask"].to(torch.bool), out["used"].to(torch.bool)
         return out
 
@@ -1056,7 +981,6 @@ def approximate_moment_magnitudes(corrected, snr, *, valid, frequencies, epicent
     float32.  The definition is postprocess.approximate_moment_magnitude_host; bounds in DESIGN.md section 4.
     Refusals (ValueError, before any device call): as network_average_spectra; num_averaging_bands outside 1 .. 8;
     frequencies that do not ascend; max_num_bad_measurements < 0."""
-    import ctypes as C
     import torch
     from . import _lib
     name = "approximate_moment_magnitudes"
@@ -1084,15 +1008,11 @@ def approximate_moment_magnitudes(corrected, snr, *, valid, frequencies, epicent
                "weights": torch.empty((E, S * Cc), dtype=torch.float32, device=dev),
                "measurement_snr": torch.empty((E, S * Cc), dtype=torch.float32, device=dev)}
         if E:
-            p = {key: C.c_void_p(t.data_ptr()) for key, t in out.items()}
-            rc = _lib.lib().bpmf_source_spectra_dev(
-                None, None, C.c_void_p(v.data_ptr()), None, None, C.c_void_p(epi.data_ptr()), None, None, None, None,
-                E, S, Cc, F, SS_MW, 0.0, 1.0, float(snr_threshold), 0.0, 0, 0, 0, nab, first_high,
-                float(magnitude_log_moment_scaling), float(weight_max), int(max_num_bad_measurements),
-                C.c_void_p(torch.cuda.current_stream(dev).cuda_stream), C.c_void_p(x.data_ptr()),
-                C.c_void_p(r.data_ptr()), None, None, None, None, None, p["Mw_star"], p["log10_M0"],
-                p["measured_disp"], p["weights"], p["measurement_snr"])
-            _lib.check(rc, "bpmf_source_spectra_dev")
+            _lib.call("bpmf_source_spectra_dev", dev, None, None, v, None, None, epi, None, None, None, None, E, S, Cc,
+                      F, SS_MW, 0.0, 1.0, float(snr_threshold), 0.0, 0, 0, 0, nab, first_high,
+                      float(magnitude_log_moment_scaling), float(weight_max), int(max_num_bad_measurements),
+                      _lib.STREAM, x, r, None, None, None, None, None, out["Mw_star"], out["log10_M0"],
+                      out["measured_disp"], out["weights"], out["measurement_snr"])
         return out
 
 
@@ -1362,7 +1282,6 @@ def flag_multiples(origin_time_sec, template_rows, cc, pair_ok, dt_criterion=4.0
     which synchronises once, then the flags are scattered back to the input order.  `device`: the GPU (default: the
     current one); `out`: an optional uint8 tensor of length n on that GPU that receives the flags IN SORTED ORDER (the
     library's own output buffer, every element written)."""
-    import ctypes as C
     import torch
     from . import _lib
     d_ok = None
@@ -1376,11 +1295,7 @@ def flag_multiples(origin_time_sec, template_rows, cc, pair_ok, dt_criterion=4.0
     else:
         t, rows, c, ok = pp.multiples_arguments(origin_time_sec, template_rows, cc, pair_ok)
         n, T = t.shape[0], ok.shape[0]
-    dev = torch.device("cuda" if device is None else device)
-    if dev.type != "cuda":
-        raise ValueError("flag_multiples: no CPU implementation here (the host mirror is postprocess.flag_multiples)")
-    if dev.index is None:
-        dev = torch.device("cuda", torch.cuda.current_device())
+    dev = _cuda_device("flag_multiples", device, "postprocess.flag_multiples")
     if out is not None and (not isinstance(out, torch.Tensor) or out.dtype != torch.uint8 or out.shape != (n,) or
                             out.device != dev or not out.is_contiguous()):
         raise ValueError(f"flag_multiples: out must be a contiguous uint8 tensor of length {n} on {dev}")
@@ -1389,21 +1304,15 @@ def flag_multiples(origin_time_sec, template_rows, cc, pair_ok, dt_criterion=4.0
     if T == 0:
         raise ValueError("flag_multiples: pair_ok is empty")
     order = np.argsort(t, kind="stable")
-    lib = _lib.lib()
     d_t = torch.as_tensor(t[order], device=dev)
     d_rows = torch.as_tensor(rows[order], device=dev)
     d_cc = torch.as_tensor(c[order], device=dev)
     if d_ok is None:
         d_ok = torch.as_tensor(ok.view(np.uint8), device=dev)
-    ws = torch.empty(lib.bpmf_flag_multiples_workspace_bytes(n), dtype=torch.uint8, device=dev)
+    ws = torch.empty(_lib.lib().bpmf_flag_multiples_workspace_bytes(n), dtype=torch.uint8, device=dev)
     flags = torch.empty(n, dtype=torch.uint8, device=dev) if out is None else out
-    with torch.cuda.device(dev):
-        rc = lib.bpmf_flag_multiples_dev(C.c_void_p(d_t.data_ptr()), C.c_void_p(d_rows.data_ptr()),
-                                         C.c_void_p(d_cc.data_ptr()), n, C.c_void_p(d_ok.data_ptr()), T,
-                                         float(dt_criterion), C.c_void_p(ws.data_ptr()), ws.numel(),
-                                         C.c_void_p(torch.cuda.current_stream(dev).cuda_stream),
-                                         C.c_void_p(flags.data_ptr()))
-    _lib.check(rc, "bpmf_flag_multiples_dev")
+    _lib.call("bpmf_flag_multiples_dev", dev, d_t, d_rows, d_cc, n, d_ok, T, float(dt_criterion), ws, ws.numel(),
+              _lib.STREAM, flags)
     unique = np.empty(n, dtype=bool)
     unique[order] = flags.cpu().numpy().astype(bool)
     return unique
@@ -1449,7 +1358,6 @@ def compute_distances(src_lon, src_lat, src_dep, rcv_lon, rcv_lat, rcv_dep, retu
     nonconverged="raise" reads the 4-byte count of pairs the iteration gave up on (nearly antipodal points) and raises
     ValueError if there is any; "antipodal" gives them pi (a + b) / 2 and does not synchronise.  `count_out`: an
     optional int32 tensor of one element on the GPU that receives the count."""
-    import ctypes as C
     import torch
     from . import _lib
     slon, slat, sdep, rlon, rlat, rdep, depth_f64 = pp.distances_arguments(src_lon, src_lat, src_dep, rcv_lon,
@@ -1468,13 +1376,8 @@ def compute_distances(src_lon, src_lat, src_dep, rcv_lon, rcv_lat, rcv_dep, retu
         d_src = torch.as_tensor(_geo_table(slon, slat, sdep), device=dev)
         d_rcv = torch.as_tensor(_geo_table(rlon, rlat, rdep), device=dev)
         count = torch.empty(1, dtype=torch.int32, device=dev) if count_out is None else count_out
-        with torch.cuda.device(dev):
-            rc = _lib.lib().bpmf_geo_distances_dev(
-                C.c_void_p(d_src.data_ptr()), K, C.c_void_p(d_rcv.data_ptr()), R, 1 if depth_f64 else 0,
-                C.c_void_p(torch.cuda.current_stream(dev).cuda_stream), C.c_void_p(hypo.data_ptr()),
-                C.c_void_p(epi.data_ptr() if epi is not None else None),
-                C.c_void_p(metres.data_ptr() if metres is not None else None), C.c_void_p(count.data_ptr()))
-        _lib.check(rc, "bpmf_geo_distances_dev")
+        _lib.call("bpmf_geo_distances_dev", dev, d_src, K, d_rcv, R, 1 if depth_f64 else 0, _lib.STREAM, hypo, epi,
+                  metres, count)
         if nonconverged == "raise":
             n_bad = int(count.item())
             if n_bad:
@@ -1494,7 +1397,6 @@ def template_geometry(longitude, latitude, depth, cov_mat=None, has_cov=None, de
     points and uploads them; the T^2 pairs are the kernel's.  dir_errors equals the definition bit for bit, the
     distances are its roundings of the device's own geodesic, and ellipsoid_dist is the float32
     (dist - dir_errors) - dir_errors.T of the device's matrices.  No synchronisation."""
-    import ctypes as C
     import torch
     from . import _lib
     lon, lat, dep, xyz, cov, has = pp.template_geometry_arguments(longitude, latitude, depth, cov_mat, has_cov,
@@ -1510,14 +1412,8 @@ def template_geometry(longitude, latitude, depth, cov_mat=None, has_cov=None, de
         d_has = torch.as_tensor(has.view(np.uint8), device=dev)
     out = {k: torch.empty((T, T), dtype=torch.float32, device=dev)
            for k in ("intertemplate_dist", "dir_errors", "ellipsoid_dist")}
-    with torch.cuda.device(dev):
-        rc = _lib.lib().bpmf_template_geometry_dev(
-            C.c_void_p(d_geo.data_ptr()), C.c_void_p(d_xyz.data_ptr()),
-            C.c_void_p(d_cov.data_ptr() if d_cov is not None else None),
-            C.c_void_p(d_has.data_ptr() if d_has is not None else None), T,
-            C.c_void_p(torch.cuda.current_stream(dev).cuda_stream), C.c_void_p(out["intertemplate_dist"].data_ptr()),
-            C.c_void_p(out["dir_errors"].data_ptr()), C.c_void_p(out["ellipsoid_dist"].data_ptr()), C.c_void_p(None))
-    _lib.check(rc, "bpmf_template_geometry_dev")
+    _lib.call("bpmf_template_geometry_dev", dev, d_geo, d_xyz, d_cov, d_has, T, _lib.STREAM, out["intertemplate_dist"],
+              out["dir_errors"], out["ellipsoid_dist"], None)
     return out
 
 
@@ -1542,7 +1438,6 @@ def template_pair_masks(ellipsoid_dist, *, distance_criterion=None, intertemplat
     `ellipsoid_dist` (and `intertemplate_cc`): (T, T) float32, the GPU tensor of template_geometry as it is, or a host
     array, which is uploaded.  The comparisons are NumPy's on float32 matrices (a NaN fails both: 0 in pair_ok, 1 in
     pair_mask).  No synchronisation."""
-    import ctypes as C
     import torch
     from . import _lib
     if distance_criterion is None and distance_threshold is None:
@@ -1582,12 +1477,8 @@ def template_pair_masks(ellipsoid_dist, *, distance_criterion=None, intertemplat
     out = {}
     for key, mode, criterion, cc, similarity in jobs:
         mask = torch.empty((T, T), dtype=torch.uint8, device=dev)
-        with torch.cuda.device(dev):
-            rc = _lib.lib().bpmf_pair_mask_dev(
-                C.c_void_p(d_ell.data_ptr()), C.c_void_p(cc.data_ptr() if cc is not None else None), T, mode,
-                _float32_comparand(criterion), _float32_comparand(similarity),
-                C.c_void_p(torch.cuda.current_stream(dev).cuda_stream), C.c_void_p(mask.data_ptr()))
-        _lib.check(rc, "bpmf_pair_mask_dev")
+        _lib.call("bpmf_pair_mask_dev", dev, d_ell, cc, T, mode, _float32_comparand(criterion),
+                  _float32_comparand(similarity), _lib.STREAM, mask)
         out[key] = mask
     return out
 
@@ -2344,18 +2235,12 @@ def intertemplate_cc(waveforms_arr, weights, max_lag=10, device=None, pair_mask=
                 mask_d = d_mask
             else:
                 mask_d = torch.as_tensor(np.ascontiguousarray(mask, dtype=np.uint8), device=wf.device)
-            lib = mf.lib
-            ws = torch.empty(lib.bpmf_intertemplate_workspace_bytes(T, S, Cc, max_lag), dtype=torch.uint8,
+            ws = torch.empty(mf.lib.bpmf_intertemplate_workspace_bytes(T, S, Cc, max_lag), dtype=torch.uint8,
                              device=wf.device)
             out = torch.empty((T, T), dtype=torch.float32, device=wf.device)
-            import ctypes as C
             from . import _lib
-            with torch.cuda.device(wf.device):
-                rc = lib.bpmf_intertemplate_cc_dev(wf.data_ptr(), base_d.data_ptr(), mask_d.data_ptr(), T, S, Cc,
-                                                   Lw, int(max_lag), ws.data_ptr(), ws.numel(),
-                                                   C.c_void_p(torch.cuda.current_stream(wf.device).cuda_stream),
-                                                   out.data_ptr())
-            _lib.check(rc, "bpmf_intertemplate_cc_dev")
+            _lib.call("bpmf_intertemplate_cc_dev", wf.device, wf, base_d, mask_d, T, S, Cc, Lw, int(max_lag), ws,
+                      ws.numel(), _lib.STREAM, out)
             o = out.cpu().numpy()
             return (o + o.T) / 2.0 if symmetrise else o
     if isinstance(pair_mask, torch.Tensor):                  # (the loop below is driven from the host)

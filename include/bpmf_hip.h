@@ -936,6 +936,45 @@ int bpmf_source_spectra_dev(const double *d_signal, const double *d_noise, const
                             double *d_mw_star, double *d_log10_m0, double *d_measured_disp, float *d_weights,
                             float *d_measurement_snr);
 
+/* ------------------------------- Brune / Boatwright fits of the network-average spectra --- */
+/*
+ * Spectrum.fit_average_spectrum (BPMF/spectrum.py:729-849, log=True) with the below-fc gate and the stress drop, for ONE
+ * phase of E events in one call (spectral_fit.hip; called by workflow.fit_source_spectra).  The inputs are what stage
+ * 4 of bpmf_source_spectra_dev leaves.  The answer is DEFINED as the exact weighted least-squares minimum
+ * (seismic_bpmf_amd.postprocess.fit_source_spectra_host), not as the point where SciPy's curve_fit stops: over the M
+ * unmasked bins, y = log10(d_average), x = d_frequencies, w = 1 or, weighted, sigmoid((d_num_valid - mean) / mean) with
+ * the mean over all F bins; the model is a - g(x / fc) with a = log10 Omega_0 and g = log10(1 + r^2) (model 0, Brune)
+ * or 0.5 log10(1 + r^4) (model 1, Boatwright); with u = ln fc the profile cost is
+ *   P(u) = 1/2 sum w^2 (y + g - a(u))^2,   a(u) = sum w^2 (y + g) / sum w^2,   sums in bin order,
+ * and u* = argmin P on the closed interval [ln(fc0 / BPMF_FIT_BOUND_FACTOR), ln(fc0 * BPMF_FIT_BOUND_FACTOR)], fc0 =
+ * fc_circular_crack(moment_to_magnitude(first unmasked value)) with the reference's defaults, found with fixed trip
+ * counts: BPMF_FIT_SCAN_POINTS evenly spaced u, the lowest cost (ties to the lowest index, a NaN as +inf),
+ * BPMF_FIT_ZOOM_ROUNDS rounds of BPMF_FIT_ZOOM_POINTS points on the bracket of the lowest point's two neighbours, then
+ * BPMF_FIT_NEWTON_STEPS Newton steps u - P' / P'' (taken where P'' > 0 and the step is finite), clamped to the bracket.
+ * Outputs per event: d_m0 = 10^a(u*), d_fc = exp(u*), d_mw = 2/3 (log10 M0 - 9.1), d_cost = P(u*), d_stress_drop (Pa,
+ * stress_drop_circular_crack for `phase`: 0 P, 1 S), d_m0_err and d_fc_err the roots of the diagonal of
+ * (2 P / (M - 2)) (J^T J)^-1 in closed form (inf for M <= 2), d_n_valid = M, d_at_bound (u* at either end), d_reason:
+ *   0 fitted (d_success = 1); 1 no unmasked bin; 2 M / F < min_fraction_valid_points; 3 fewer than
+ *   min_fraction_valid_points_below_fc * F unmasked bins with x < fc; 4 at a bound; 5 a y, w, M0, fc, cost, Mw or stress
+ *   drop that is not finite.  The seven f64 outputs are NaN for reasons 1, 2 and 5, and reported for 3 and 4.
+ *   d_average (E, F) f64; d_mask (E, F) u8; d_num_valid (E, F) i32; d_frequencies (F) f64, positive and ascending (the
+ *   caller's to check); seven (E) f64, d_n_valid (E) i32, three (E) u8.  All on the device; every element is written.
+ * One wave per event, no workspace: an event gives the same bits alone and in any batch.  Asynchronous on `stream`.
+ * Returns -1 for a null pointer, F outside 1 .. 1024, E * F >= 2^31, a model or phase that is not 0 or 1.  E == 0
+ * launches nothing and returns 0.
+ */
+#define BPMF_FIT_SCAN_POINTS 1024
+#define BPMF_FIT_ZOOM_ROUNDS 2
+#define BPMF_FIT_ZOOM_POINTS 64
+#define BPMF_FIT_NEWTON_STEPS 4
+#define BPMF_FIT_BOUND_FACTOR 1.0e3
+int bpmf_fit_spectra_dev(const double *d_average, const unsigned char *d_mask, const int *d_num_valid,
+                         const double *d_frequencies, size_t E, size_t F, int model, int phase, int weighted,
+                         double min_fraction_valid_points, double min_fraction_valid_points_below_fc,
+                         bpmf_stream_t stream, double *d_m0, double *d_fc, double *d_mw, double *d_m0_err,
+                         double *d_fc_err, double *d_cost, double *d_stress_drop, int *d_n_valid,
+                         unsigned char *d_success, unsigned char *d_at_bound, unsigned char *d_reason);
+
 /* ------------------------------------------- events detected by several templates --- */
 /*
  * The loop of TemplateGroup.remove_multiples (BPMF/dataset.py:5214-5282) on a catalog that is ALREADY in the

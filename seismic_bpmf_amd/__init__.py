@@ -16,8 +16,9 @@ from ._lib import (BpmfHipError, device_count, device_info, device_memory_held, 
 from .beampower import BeamformerGPU, beamform  # noqa: F401
 from .matched_filter import MatchedFilterGPU, accept_cpu_arch, matched_filter, matched_filter_full  # noqa: F401
 from .workflow import (approximate_moment_magnitudes, bandpass_filter, differentiate_spectra,  # noqa: F401
-                       fft_spectra, find_picks, integrate_spectra, multiband_snr, multiband_spectra,
-                       network_average_spectra, normalize_batch, pick_events, picker_batch, source_spectra,
+                       fft_spectra, find_picks, fit_source_spectra, integrate_spectra, moment_magnitudes,
+                       multiband_snr, multiband_spectra, network_average_spectra, normalize_batch, pick_events,
+                       picker_batch, resample_spectra, source_spectra,
                        spectral_snr, svdwf_stack, target_frequencies, templates_from_events)
 
 __version__ = "0.1.0"

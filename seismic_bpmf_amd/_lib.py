@@ -109,6 +109,8 @@ SIGNATURES = {
     "bpmf_source_spectra_dev": (C.c_int, [_vp] * 10 + [_sz, _sz, _sz, _sz, C.c_uint, C.c_double, C.c_double, C.c_double,
                                           C.c_double, C.c_int, C.c_int, C.c_int, C.c_int, _sz, C.c_double, C.c_double,
                                           C.c_int, _vp] + [_vp] * 12),
+    "bpmf_fit_spectra_dev": (C.c_int, [_vp] * 4 + [_sz, _sz, C.c_int, C.c_int, C.c_int, C.c_double, C.c_double, _vp] +
+                             [_vp] * 11),
     "bpmf_flag_multiples_workspace_bytes": (_sz, [_sz]),
     "bpmf_flag_multiples_dev": (C.c_int, [_vp, _vp, _vp, _sz, _vp, _sz, C.c_double, _vp, _sz, _vp, _vp]),
     "bpmf_geo_distances_dev": (C.c_int, [_vp, _sz, _vp, _sz, C.c_int, _vp, _vp, _vp, _vp, _vp]),

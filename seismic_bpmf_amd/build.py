@@ -12,7 +12,7 @@ CSRC = os.path.join(_HERE, "csrc")
 LIBDIR = os.path.join(_HERE, "lib")
 LIBPATH = os.path.join(LIBDIR, "libbpmf_hip.so")
 OBJDIR = os.path.join(LIBDIR, "obj")
-SOURCES = ["mf.hip", "mf_split.hip", "mf_full.hip", "bp.hip", "bp_plan.hip", "bp_fast.hip", "bp_direct.hip", "bp_relocate.hip", "bp_uncertainty.hip", "bp_detect.hip", "stats.hip", "intertp.hip", "post.hip", "peak_amp.hip", "templates.hip", "picker.hip", "resample.hip", "svdwf.hip", "spectrum.hip", "fft_spectrum.hip", "source_spectra.hip", "multiples.hip", "geometry.hip", "decimate.hip", "util.hip", "multi.hip", "context.hip", "host_call.hip", "bp_plan_cache.hip"]
+SOURCES = ["mf.hip", "mf_split.hip", "mf_full.hip", "bp.hip", "bp_plan.hip", "bp_fast.hip", "bp_direct.hip", "bp_relocate.hip", "bp_uncertainty.hip", "bp_detect.hip", "stats.hip", "intertp.hip", "post.hip", "peak_amp.hip", "templates.hip", "picker.hip", "resample.hip", "svdwf.hip", "spectrum.hip", "fft_spectrum.hip", "source_spectra.hip", "spectral_fit.hip", "multiples.hip", "geometry.hip", "decimate.hip", "util.hip", "multi.hip", "context.hip", "host_call.hip", "bp_plan_cache.hip"]
 ARCH = "gfx950"
 # -ffp-contract=off: the kernels spell out every fmaf; the compiler must not fuse more.
 FLAGS = ["-O3", "-std=c++17", "-ffp-contract=off", "-fPIC", "-shared", "-Wall",

@@ -2337,3 +2337,269 @@ def source_spectra_host(signal, noise, present, noise_present, dist_km, tt_sec, 
     out = network_average_spectrum_host(corrected, snr, present, err_pct, **average_options)
     out.update(corrected=corrected, snr=snr)
     return out
+
+
+# ---- Spectrum.fit_average_spectrum :729-849 (log=True), the gates and the P-S average of compute_moment_magnitude
+# :1895-1990, Spectrum.resample :851-887 ----
+# The constants of the fit's operational definition; include/bpmf_hip.h holds the same numbers as BPMF_FIT_*
+# (tests/test_spectral_fit_definition.py compares the two).
+FIT_SCAN_POINTS = 1024                     # G: log-spaced corner frequencies over the closed interval
+FIT_ZOOM_ROUNDS = 2
+FIT_ZOOM_POINTS = 64                       # one per lane
+FIT_NEWTON_STEPS = 4
+FIT_BOUND_FACTOR = 1.0e3                   # fc0 / 1e3 .. fc0 * 1e3
+FIT_MODELS = {"brune": 2.0, "boatwright": 4.0}          # n of g = (2 / n) log10(1 + (f / fc)^n)
+FIT_REASONS = ("fitted", "all bins masked", "too few valid bins", "too few valid bins below fc", "fc at a bound",
+               "a value that is not finite")
+FIT_KEYS = ("M0", "fc", "Mw", "M0_err", "fc_err", "cost", "stress_drop_pa")
+FIT_LOG_OF_10 = 2.302585092994046          # np.log(10.0)
+CRACK_CONSTANT = {"p": 2.23, "s": 1.47}
+CRACK_VR_M_PER_S = 0.9 * 3500.0            # vr_vs_ratio * vs_m_per_s, the reference's defaults
+
+
+def moment_to_magnitude(M0):
+    """BPMF/spectrum.py:1201-1203."""
+    return 2.0 / 3.0 * (np.log10(M0) - 9.1)
+
+
+def magnitude_to_moment(Mw):
+    """BPMF/spectrum.py:1196-1198."""
+    return 10.0 ** (3.0 / 2.0 * Mw + 9.1)
+
+
+def fc_circular_crack(Mw, stress_drop_Pa=1.0e6, phase="p"):
+    """BPMF/spectrum.py:1206-1246 with the reference's velocity defaults."""
+    crack_radius = np.power((7.0 / 16.0) * (magnitude_to_moment(Mw) / stress_drop_Pa), 1.0 / 3.0)
+    return (CRACK_CONSTANT[phase] * CRACK_VR_M_PER_S) / (2.0 * np.pi * crack_radius)
+
+
+def stress_drop_circular_crack(Mw, fc, phase="p"):
+    """BPMF/spectrum.py:1249-1287 with the reference's velocity defaults."""
+    crack_radius = CRACK_CONSTANT[phase] * CRACK_VR_M_PER_S / (2.0 * np.pi * fc)
+    return 7.0 / 16.0 * magnitude_to_moment(Mw) / crack_radius**3
+
+
+def _ordered_sum(terms):
+    """The sum of the last axis, one term after the other from the first (what a plain loop on the device does)."""
+    return np.add.accumulate(terms, axis=-1)[..., -1]
+
+
+def fit_profile_cost(u, ln_x, y, w2, n):
+    """The profile cost P(u) = 1/2 sum w^2 (y + g - a)^2 and a(u) = sum w^2 (y + g) / sum w^2 at every u of a (K,)
+    array, with g = (2 / n) log10(1 + exp(n (ln x - u))) and every sum in bin order.  Returns (P, a), each (K,)."""
+    u = np.atleast_1d(np.asarray(u, dtype=np.float64))
+    with np.errstate(all="ignore"):
+        g = (2.0 / n) * np.log10(1.0 + np.exp(n * (ln_x[None, :] - u[:, None])))
+        z = y[None, :] + g
+        a = _ordered_sum(w2[None, :] * z) / _ordered_sum(w2)
+        rho = z - a[:, None]
+        return 0.5 * _ordered_sum(w2[None, :] * rho * rho), a
+
+
+def fit_profile_derivatives(u, ln_x, y, w2, n):
+    """At one u: P'(u) = sum w^2 rho (g' - a'), P''(u) = sum w^2 (g' - a')^2 + sum w^2 rho g'', the centred second
+    moment D = sum w^2 (g' - a')^2 and the plain one sum w^2 g'^2, with t = 1 / (1 + exp(-n (ln x - u))),
+    g' = dg/du = -(2 / ln 10) t and g'' = (2 n / ln 10) t (1 - t).  Sums in bin order."""
+    with np.errstate(all="ignore"):
+        d = ln_x - u
+        g = (2.0 / n) * np.log10(1.0 + np.exp(n * d))
+        t = 1.0 / (1.0 + np.exp(-(n * d)))
+        g1 = -(2.0 / FIT_LOG_OF_10) * t
+        g2 = (2.0 * n / FIT_LOG_OF_10) * (t * (1.0 - t))
+        sw = _ordered_sum(w2)
+        z = y + g
+        rho = z - _ordered_sum(w2 * z) / sw
+        c1 = g1 - _ordered_sum(w2 * g1) / sw
+        centred = _ordered_sum(w2 * c1 * c1)
+        return (_ordered_sum(w2 * rho * c1), centred + _ordered_sum(w2 * rho * g2), centred,
+                _ordered_sum(w2 * g1 * g1))
+
+
+def _fit_lowest(cost):
+    """The index of the lowest cost, ties to the lowest index; a NaN counts as +inf."""
+    return int(np.argmin(np.where(np.isnan(cost), np.inf, cost)))
+
+
+def _fit_grid(lo, hi, count):
+    """`count` points from lo to hi, both ends exact: lo + i ((hi - lo) / (count - 1)), the last one hi itself."""
+    u = lo + np.arange(count, dtype=np.float64) * ((hi - lo) / (count - 1))
+    u[-1] = hi
+    return u
+
+
+def fit_minimise(ln_x, y, w2, n, lo, hi):
+    """argmin of the profile cost on the closed interval [lo, hi] as the kernel finds it: FIT_SCAN_POINTS evenly spaced
+    u, the lowest cost (ties to the lowest index), FIT_ZOOM_ROUNDS rounds of FIT_ZOOM_POINTS points on the bracket of
+    its two neighbours, then FIT_NEWTON_STEPS Newton steps u - P' / P'' (taken where P'' > 0 and the step is finite)
+    clamped to the last bracket.  Returns u*."""
+    a, b, count = lo, hi, FIT_SCAN_POINTS
+    for _ in range(1 + FIT_ZOOM_ROUNDS):
+        u = _fit_grid(a, b, count)
+        i = _fit_lowest(fit_profile_cost(u, ln_x, y, w2, n)[0])
+        a, b, best = u[max(i - 1, 0)], u[min(i + 1, count - 1)], u[i]
+        count = FIT_ZOOM_POINTS
+    u = best
+    for _ in range(FIT_NEWTON_STEPS):
+        p1, p2 = fit_profile_derivatives(u, ln_x, y, w2, n)[:2]
+        with np.errstate(all="ignore"):
+            step = p1 / p2
+        if p2 > 0.0 and step - step == 0.0:
+            u = min(max(u - step, a), b)
+    return u
+
+
+def fit_weights(num_valid, weighted):
+    """(E, F) weights of the fit: sigmoid((num_valid - mean) / mean) with the mean over ALL F bins of the event
+    (BPMF/spectrum.py:796-799), or 1.  curve_fit's sigma = 1 / w multiplies the residuals by w."""
+    nv = np.asarray(num_valid, dtype=np.float64)
+    if not weighted:
+        return np.ones_like(nv)
+    with np.errstate(all="ignore"):
+        mean = _ordered_sum(nv) / nv.shape[-1]
+        return 1.0 / (1.0 + np.exp(-((nv - mean[..., None]) / mean[..., None])))
+
+
+def fit_source_spectra_host(average, mask, num_valid, frequencies, phase, *, model="brune", weighted=False,
+                            min_fraction_valid_points=0.5, min_fraction_valid_points_below_fc=0.1):
+    """Spectrum.fit_average_spectrum (BPMF/spectrum.py:729-849, log=True) for E events, by DEFINITION the exact weighted
+    least-squares minimum rather than where SciPy's curve_fit stops: `average`, `mask`, `num_valid` (E, F) as
+    network_average_spectrum_host returns them, `frequencies` (F,) positive and ascending, `phase` "p" or "s" (it
+    enters the stress drop only: the reference's first guess of fc is the P one for both phases).
+
+    Per event: no unmasked bin -> reason 1; valid / F < min_fraction_valid_points -> reason 2.  Else y = log10(average),
+    x = frequencies at the M unmasked bins, w = fit_weights; Omega_0's first guess is the first unmasked value,
+    fc0 = fc_circular_crack(moment_to_magnitude(Omega_0)).  The model is m(f) = a - g(f / fc), a = log10 Omega_0,
+    g = log10(1 + r^2) (Brune) or 0.5 log10(1 + r^4) (Boatwright).  a is linear, so with u = ln fc the problem is
+    u* = argmin P(u) (fit_profile_cost) on [ln(fc0 / 1e3), ln(fc0 1e3)], found by fit_minimise.  The upper end is the
+    reference's bound; the reference's lower bound is fc = 0, where P tends to a constant and no minimum is attained,
+    so the symmetric lower end is a departure.  u* at either end -> at_bound, reason 4 (values reported).
+
+    Covariance, exact (not SciPy's SVD cut, which in one fit of six drops the Omega_0 column and leaves
+    M0_err ~ 1e-31 M0: that artefact is not reproduced): J = w [1 / (Omega_0 ln 10), -dg/dfc], pcov = (2 P / (M - 2))
+    (J^T J)^-1, in the coordinates (a, u) where J = w [1, -g'], so that pcov_00 = (Omega_0 ln 10)^2 s^2 sum w^2 g'^2 /
+    (sum w^2 D) and pcov_11 = fc^2 s^2 / D with D the centred moment of g'.  M <= 2: inf, SciPy's rule.
+    sum(x < fc) / F < min_fraction_valid_points_below_fc -> reason 3 (values reported).  A y, w, M0, fc, cost, Mw or
+    stress drop that is not finite -> reason 5, NaN outputs (the two errors may be inf).  Precedence 1, 2, 5, 4, 3.
+
+    Returns a dict of (E,) arrays: FIT_KEYS float64 (NaN where nothing was fitted), `n_valid` int32, `success`
+    (reason 0), `at_bound` bool, `reason` uint8 (FIT_REASONS)."""
+    if model not in FIT_MODELS:
+        raise ValueError(f"fit_source_spectra_host: model must be one of {sorted(FIT_MODELS)}; got {model!r}")
+    if phase not in CRACK_CONSTANT:
+        raise ValueError(f"fit_source_spectra_host: phase must be 'p' or 's'; got {phase!r}")
+    n = FIT_MODELS[model]
+    average, mask = np.asarray(average, dtype=np.float64), np.asarray(mask, dtype=bool)
+    f = np.asarray(frequencies, dtype=np.float64)
+    E, F = average.shape
+    weights = fit_weights(num_valid, weighted)
+    out = {k: np.full(E, np.nan) for k in FIT_KEYS}
+    out.update(n_valid=np.zeros(E, np.int32), success=np.zeros(E, bool), at_bound=np.zeros(E, bool),
+               reason=np.zeros(E, np.uint8))
+    with np.errstate(all="ignore"):
+        for e in range(E):
+            keep = ~mask[e]
+            M = int(keep.sum())
+            out["n_valid"][e] = M
+            if M == 0:
+                out["reason"][e] = 1
+                continue
+            if M / float(F) < min_fraction_valid_points:
+                out["reason"][e] = 2
+                continue
+            y, x, w = np.log10(average[e][keep]), f[keep], weights[e][keep]
+            if not (np.isfinite(y).all() and np.isfinite(w).all()):
+                out["reason"][e] = 5
+                continue
+            w2, ln_x = w * w, np.log(x)
+            fc0 = fc_circular_crack(moment_to_magnitude(average[e][keep][0]))
+            lo, hi = np.log(fc0 / FIT_BOUND_FACTOR), np.log(fc0 * FIT_BOUND_FACTOR)
+            if not (np.isfinite(lo) and np.isfinite(hi)):
+                out["reason"][e] = 5
+                continue
+            u = fit_minimise(ln_x, y, w2, n, lo, hi)
+            cost, a = (v[0] for v in fit_profile_cost(u, ln_x, y, w2, n))
+            _, _, centred, plain = fit_profile_derivatives(u, ln_x, y, w2, n)
+            M0, fc = 10.0 ** a, np.exp(u)
+            Mw = moment_to_magnitude(M0)
+            stress = stress_drop_circular_crack(Mw, fc, phase)
+            if not np.isfinite([M0, fc, cost, Mw, stress]).all():
+                out["reason"][e] = 5
+                continue
+            if M > 2:
+                s2 = 2.0 * cost / (M - 2)
+                cov_a, cov_u = s2 * plain / (_ordered_sum(w2) * centred), s2 / centred
+            else:
+                cov_a = cov_u = np.inf
+            out["M0"][e], out["fc"][e], out["Mw"][e], out["cost"][e], out["stress_drop_pa"][e] = M0, fc, Mw, cost, stress
+            out["M0_err"][e] = (M0 * FIT_LOG_OF_10) * np.sqrt(cov_a)
+            out["fc_err"][e] = fc * np.sqrt(cov_u)
+            out["at_bound"][e] = u == lo or u == hi
+            if out["at_bound"][e]:
+                out["reason"][e] = 4
+            elif int((x < fc).sum()) / float(F) < min_fraction_valid_points_below_fc:
+                out["reason"][e] = 3
+    out["success"] = out["reason"] == 0
+    return out
+
+
+def moment_magnitudes_host(fit_p=None, fit_s=None, *, max_rel_m0_err_pct=33.0, max_rel_fc_err_pct=33.0):
+    """The acceptance tests and the P-S average of compute_moment_magnitude (BPMF/spectrum.py:1907-1946, :1965-1990)
+    on the dicts of fit_source_spectra_host: a phase is accepted where its fit succeeded and NOT (100 M0_err / M0 >
+    max_rel_m0_err_pct or fc < 0 or 100 fc_err / fc > max_rel_fc_err_pct); Mw is the sum of the accepted phases' Mw
+    (P first) divided by their number, Mw_err that of 2 / 3 * M0_err / M0; NaN where no phase was accepted.  The
+    reference computes a stress-drop gate and then overrides it to True (:1937-1940); it stays overridden here.
+    Returns {"Mw", "Mw_err" (E,) float64, "accepted": {phase: (E,) bool}}."""
+    given = [(ph, fit) for ph, fit in (("p", fit_p), ("s", fit_s)) if fit is not None]
+    if not given:
+        raise ValueError("moment_magnitudes_host: give the fit of at least one phase")
+    E = len(given[0][1]["M0"])
+    total, total_err, norm, accepted = np.zeros(E), np.zeros(E), np.zeros(E), {}
+    with np.errstate(all="ignore"):
+        for ph, fit in given:
+            M0, fc = np.asarray(fit["M0"], dtype=np.float64), np.asarray(fit["fc"], dtype=np.float64)
+            rel_m0 = 100.0 * np.asarray(fit["M0_err"], dtype=np.float64) / M0
+            rel_fc = 100.0 * np.asarray(fit["fc_err"], dtype=np.float64) / fc
+            ok = np.asarray(fit["success"], dtype=bool) & ~((rel_m0 > max_rel_m0_err_pct) | (fc < 0.0) |
+                                                             (rel_fc > max_rel_fc_err_pct))
+            accepted[ph] = ok
+            total = total + np.where(ok, np.asarray(fit["Mw"], dtype=np.float64), 0.0)
+            total_err = total_err + np.where(ok, 2.0 / 3.0 * np.asarray(fit["M0_err"], dtype=np.float64) / M0, 0.0)
+            norm = norm + ok
+        some = norm > 0
+        return {"Mw": np.where(some, total / norm, np.nan), "Mw_err": np.where(some, total_err / norm, np.nan),
+                "accepted": accepted}
+
+
+def resample_plan(frequencies_in, frequencies_out):
+    """What np.interp needs per target of Spectrum.resample (BPMF/spectrum.py:851-887), from the frequencies alone:
+    `pair` j with xp[j] <= x < xp[j + 1] (clipped to 0 .. B - 2), `below` (x < xp[0]: fp[0]), `above` (x >= xp[-1]:
+    fp[-1], before the zeroing), `on` (x == xp[j]: fp[j]) and `outside` (x >= 0.99 max(xp): 0)."""
+    xp = np.asarray(frequencies_in, dtype=np.float64)
+    x = np.asarray(frequencies_out, dtype=np.float64)
+    if xp.ndim != 1 or x.ndim != 1 or len(xp) < 2 or not np.isfinite(xp).all() or not np.isfinite(x).all() or \
+            np.any(np.diff(xp) <= 0):
+        raise ValueError("resample_plan: frequencies_in must be (B >= 2,) finite and ascending, frequencies_out (T,) "
+                         "finite")
+    pair = np.clip(np.searchsorted(xp, x, side="right") - 1, 0, len(xp) - 2)
+    return {"pair": pair, "below": x < xp[0], "above": x >= xp[-1], "on": x == xp[pair],
+            "outside": x >= 0.99 * np.max(xp), "dx": x - xp[pair], "span": xp[pair + 1] - xp[pair]}
+
+
+def resample_spectra_host(spectra, frequencies_in, frequencies_out):
+    """Spectrum.resample (BPMF/spectrum.py:851-887) of (..., B) spectra onto (T,) targets: np.interp of |spectra| --
+    ((fp[j + 1] - fp[j]) / (xp[j + 1] - xp[j])) (x - xp[j]) + fp[j], one rounded operation each, fp[j] itself on a
+    band's frequency, the end values outside the bands -- and +0 at and beyond 0.99 max(frequencies_in)."""
+    plan = resample_plan(frequencies_in, frequencies_out)
+    fp = np.abs(np.asarray(spectra, dtype=np.float64))
+    j = plan["pair"]
+    with np.errstate(all="ignore"):
+        lo, hi = fp[..., j], fp[..., j + 1]
+        slope = (hi - lo) / plan["span"]
+        out = slope * plan["dx"] + lo
+        # np.interp's own second thoughts on a NaN: from the pair's other end, then equal ends
+        out = np.where(np.isnan(out), slope * (plan["dx"] - plan["span"]) + hi, out)
+        out = np.where(np.isnan(out) & (lo == hi), lo, out)
+    out = np.where(plan["on"], lo, out)
+    out = np.where(plan["below"], fp[..., :1], out)
+    out = np.where(plan["above"], fp[..., -1:], out)
+    return np.where(plan["outside"], 0.0, out)

@@ -918,6 +918,8 @@ def network_average_spectra(signal, noise, *, phase, valid, noise_valid=None, di
     with a 2-point Jacobian on parameters of scale 1e11 .. 1e15 and 1 .. 30 with x_scale = 1) is not offered: its
     answer is a property of SciPy's termination rules, not a definition.  The definition is
     postprocess.source_spectra_host; bounds in DESIGN.md section 4.  An event gives the same bits alone and in any batch.
+    Since then the fit is offered as the exact least-squares minimum: fit_source_spectra; and resample_spectra puts
+    multi-band spectra onto other targets.
 
     Refusals (ValueError, before any device call): spectra that are no float64 tensors of equal shape (E, S, F) or
     (E, S, C, F) on one GPU; S * C above 256; F above 1024; E S C F >= 2^31; a per-station table that is not (E, S);
@@ -1021,12 +1023,20 @@ def source_spectra(*, p=None, s=None, noise, valid_p=None, valid_s=None, noise_v
                    q_phase_prefactor=None, attenuation="reference", average_log=True,
                    min_num_valid_channels_per_freq_bin=0, max_relative_distance_err_pct=25.0, reduce="mean",
                    num_averaging_bands=1, low_snr_freq_min_hz=2.0, magnitude_log_moment_scaling=2.0 / 3.0,
-                   weight_max=3.0, max_num_bad_measurements=6):
+                   weight_max=3.0, max_num_bad_measurements=6, fit=None, fit_weighted=True, fit_on="average",
+                   min_fraction_valid_points=0.5, min_fraction_valid_points_below_fc=0.1):
     """network_average_spectra, then approximate_moment_magnitudes, for each phase given (`p`, `s`: the phase's
     spectra; `valid_p`, `valid_s`: their `valid`): a day's events go from the spectra in HBM to (E, F) network-average
     source spectra and a per-event Mw* in two calls per phase.  Returns {"p": {...}, "s": {...}} for the phases given,
     each the two functions' dicts in one.  The phases are NOT combined: the reference's combined Mw* is, through a
-    misplaced `if` (BPMF/spectrum.py:1879-1880), the last phase's value alone; the caller averages as they see fit."""
+    misplaced `if` (BPMF/spectrum.py:1879-1880), the last phase's value alone; the caller averages as they see fit.
+    With fit="brune" or "boatwright" each phase's dict gains the keys of fit_source_spectra (weighted=fit_weighted and
+    the two fractions), run on the returned `average` or, with fit_on="integrated", on integrate_spectra of it;
+    moment_magnitudes combines the two phases.  fit=None (the default) adds nothing."""
+    if fit is not None and fit not in pp.FIT_MODELS:
+        raise ValueError(f"source_spectra: fit must be None or one of {sorted(pp.FIT_MODELS)}; got {fit!r}")
+    if fit_on not in ("average", "integrated"):
+        raise ValueError(f"source_spectra: fit_on must be 'average' or 'integrated'; got {fit_on!r}")
     given = [(ph, x, v) for ph, x, v in (("p", p, valid_p), ("s", s, valid_s)) if x is not None]
     if not given:
         raise ValueError("source_spectra: give the spectra of at least one phase (p=, s=)")
@@ -1046,7 +1056,131 @@ def source_spectra(*, p=None, s=None, noise, valid_p=None, valid_s=None, noise_v
             num_averaging_bands=num_averaging_bands, low_snr_freq_min_hz=low_snr_freq_min_hz,
             magnitude_log_moment_scaling=magnitude_log_moment_scaling, weight_max=weight_max,
             max_num_bad_measurements=max_num_bad_measurements))
+        if fit is not None:
+            spectrum = out[ph]["average"]
+            if fit_on == "integrated":
+                spectrum = integrate_spectra(spectrum, frequencies)
+            out[ph].update(fit_source_spectra(
+                spectrum, out[ph]["mask"], out[ph]["num_valid"], frequencies=frequencies, phase=ph, model=fit,
+                weighted=fit_weighted, min_fraction_valid_points=min_fraction_valid_points,
+                min_fraction_valid_points_below_fc=min_fraction_valid_points_below_fc))
     return out
+
+
+def fit_source_spectra(average, mask, num_valid, *, frequencies, phase, model="brune", weighted=False,
+                       min_fraction_valid_points=0.5, min_fraction_valid_points_below_fc=0.1):
+    """Spectrum.fit_average_spectrum (BPMF/spectrum.py:729-849, log=True), the below-fc gate and the stress drop for
+    one phase of E events in one call on the device (bpmf_fit_spectra_dev, csrc/spectral_fit.hip): `average` (E, F)
+    float64, `mask` (E, F) bool and `num_valid` (E, F) int32 as network_average_spectra returns them (or
+    integrate_spectra of the average), `frequencies` (F,).  The fit is defined as the exact weighted least-squares
+    minimum, found by profiling over ln fc with log10 Omega_0 in closed form -- not as the point where SciPy's
+    curve_fit stops (its cost is never below this one's); the definition, its bounds, its covariance and its
+    departures from the reference are postprocess.fit_source_spectra_host's, DESIGN.md section 4.
+
+    Returns a dict of (E,) tensors on the inputs' device and the current stream: `M0`, `fc`, `Mw`, `M0_err`, `fc_err`,
+    `cost`, `stress_drop_pa` float64 (NaN where nothing was fitted), `n_valid` int32, `success`, `at_bound` bool and
+    `reason` uint8 (postprocess.FIT_REASONS).  An event gives the same bits alone and in any batch.
+
+    Refusals (ValueError, before any device call): average, mask, num_valid that are not (E, F) tensors of float64,
+    bool (or uint8) and int32 on one GPU; F outside 1 .. 1024; E F >= 2^31; a model that is not "brune" or
+    "boatwright"; a phase that is not "p" or "s"; frequencies that are not (F,) finite, positive and ascending."""
+    import torch
+    from . import _lib
+    name = "fit_source_spectra"
+    if model not in pp.FIT_MODELS:
+        raise ValueError(f"{name}: model must be one of {sorted(pp.FIT_MODELS)}; got {model!r}")
+    if phase not in ("p", "s"):
+        raise ValueError(f"{name}: phase must be 'p' or 's'; got {phase!r}")
+    f = np.array(frequencies.detach().cpu().numpy() if isinstance(frequencies, torch.Tensor) else frequencies,
+                 dtype=np.float64)
+    if f.ndim != 1 or not np.isfinite(f).all() or np.any(f <= 0) or np.any(np.diff(f) <= 0):
+        raise ValueError(f"{name}: frequencies must be (F,) finite, positive, ascending numbers")
+    for what, t, dtypes in (("average", average, (torch.float64,)), ("mask", mask, (torch.bool, torch.uint8)),
+                            ("num_valid", num_valid, (torch.int32,))):
+        if not isinstance(t, torch.Tensor) or t.dtype not in dtypes or t.dim() != 2:
+            raise ValueError(f"{name}: {what} must be an (E, F) tensor of {' or '.join(str(d) for d in dtypes)}")
+    if average.shape != mask.shape or average.shape != num_valid.shape or average.shape[1] != len(f):
+        raise ValueError(f"{name}: average, mask and num_valid must be (E, F) with F = {len(f)} frequencies; got "
+                         f"{tuple(average.shape)}, {tuple(mask.shape)}, {tuple(num_valid.shape)}")
+    E, F = int(average.shape[0]), int(average.shape[1])
+    if not 1 <= F <= pp.SOURCE_SPECTRA_MAX_FREQUENCIES:
+        raise ValueError(f"{name}: 1 .. {pp.SOURCE_SPECTRA_MAX_FREQUENCIES} frequencies; got {F}")
+    if E * F >= 2**31:
+        raise ValueError(f"{name}: {E} events x {F} frequencies; fewer than 2^31 values fit")
+    if not average.is_cuda or mask.device != average.device or num_valid.device != average.device:
+        raise ValueError(f"{name}: average, mask and num_valid must be tensors on one GPU (there is no CPU path; the "
+                         "definition on the host is postprocess.fit_source_spectra_host)")
+    dev = average.device
+    with torch.cuda.device(dev):
+        out = {k: torch.empty((E,), dtype=torch.float64, device=dev) for k in pp.FIT_KEYS}
+        out["n_valid"] = torch.empty((E,), dtype=torch.int32, device=dev)
+        flags = {k: torch.empty((E,), dtype=torch.uint8, device=dev) for k in ("success", "at_bound", "reason")}
+        if E:
+            _lib.call("bpmf_fit_spectra_dev", dev, average.contiguous(), mask.to(torch.uint8).contiguous(),
+                      num_valid.contiguous(), torch.as_tensor(f, device=dev), E, F, ("brune", "boatwright").index(model),
+                      ("p", "s").index(phase), int(bool(weighted)), float(min_fraction_valid_points),
+                      float(min_fraction_valid_points_below_fc), _lib.STREAM, *(out[k] for k in pp.FIT_KEYS),
+                      out["n_valid"], flags["success"], flags["at_bound"], flags["reason"])
+        out.update(success=flags["success"].to(torch.bool), at_bound=flags["at_bound"].to(torch.bool),
+                   reason=flags["reason"])
+        return out
+
+
+def moment_magnitudes(fit_p=None, fit_s=None, *, max_rel_m0_err_pct=33.0, max_rel_fc_err_pct=33.0):
+    """The acceptance tests and the P-S average of compute_moment_magnitude (BPMF/spectrum.py:1907-1946, :1965-1990) on
+    the dicts of fit_source_spectra, as torch operations on their (E,) tensors: a phase is accepted where its fit
+    succeeded and not (100 M0_err / M0 > max_rel_m0_err_pct or fc < 0 or 100 fc_err / fc > max_rel_fc_err_pct); `Mw`
+    and `Mw_err` (of 2 / 3 * M0_err / M0) are the accepted phases' sums, P first, divided by their number, NaN where no
+    phase was accepted.  The stress-drop gate that the reference overrides to True stays overridden.  Returns
+    {"Mw", "Mw_err": (E,) float64, "accepted": {phase: (E,) bool}}; the definition is
+    postprocess.moment_magnitudes_host."""
+    import torch
+    given = [(ph, fit) for ph, fit in (("p", fit_p), ("s", fit_s)) if fit is not None]
+    if not given:
+        raise ValueError("moment_magnitudes: give the fit of at least one phase (fit_p=, fit_s=)")
+    like = given[0][1]["M0"]
+    total, total_err, norm, accepted = torch.zeros_like(like), torch.zeros_like(like), torch.zeros_like(like), {}
+    zero = torch.zeros_like(like)
+    for ph, fit in given:
+        rel_m0 = 100.0 * fit["M0_err"] / fit["M0"]
+        rel_fc = 100.0 * fit["fc_err"] / fit["fc"]
+        ok = fit["success"] & ~((rel_m0 > max_rel_m0_err_pct) | (fit["fc"] < 0.0) | (rel_fc > max_rel_fc_err_pct))
+        accepted[ph] = ok
+        total = total + torch.where(ok, fit["Mw"], zero)
+        total_err = total_err + torch.where(ok, 2.0 / 3.0 * fit["M0_err"] / fit["M0"], zero)
+        norm = norm + ok.to(like.dtype)
+    nan = torch.full_like(like, float("nan"))
+    return {"Mw": torch.where(norm > 0, total / norm, nan), "Mw_err": torch.where(norm > 0, total_err / norm, nan),
+            "accepted": accepted}
+
+
+def resample_spectra(spectra, frequencies_in, frequencies_out):
+    """Spectrum.resample (BPMF/spectrum.py:851-887) for multi-band spectra on the device: (..., B) spectra on the bands'
+    `frequencies_in` (B,) onto `frequencies_out` (T,), by np.interp's formula with one rounded operation each --
+    ((fp[j + 1] - fp[j]) / (xp[j + 1] - xp[j])) (x - xp[j]) + fp[j] of |spectra|, fp[j] itself on a band's frequency,
+    the end values outside the bands -- and +0 at and beyond 0.99 max(frequencies_in).  Returns (..., T) on the
+    spectra's device, bit for bit what postprocess.resample_spectra_host gives (no product is fused with a sum: each
+    is a torch operation of its own).  ValueError for spectra that are no floating-point tensor on the GPU with B as
+    their last axis, and for frequencies that postprocess.resample_plan refuses."""
+    import torch
+    name = "resample_spectra"
+    f_in = _spectra_and_frequencies(name, spectra, frequencies_in)
+    plan = pp.resample_plan(f_in.detach().cpu().numpy(), frequencies_out.detach().cpu().numpy()
+                            if isinstance(frequencies_out, torch.Tensor) else frequencies_out)
+    dev = spectra.device
+    t = {k: torch.as_tensor(np.ascontiguousarray(v), device=dev) for k, v in plan.items()}
+    dx, span = t["dx"].to(spectra.dtype), t["span"].to(spectra.dtype)
+    fp = spectra.abs()
+    lo, hi = fp[..., t["pair"]], fp[..., t["pair"] + 1]
+    slope = (hi - lo) / span
+    out = slope * dx + lo
+    # np.interp's own second thoughts on a NaN: from the pair's other end, then equal ends
+    out = torch.where(out.isnan(), slope * (dx - span) + hi, out)
+    out = torch.where(out.isnan() & (lo == hi), lo, out)
+    out = torch.where(t["on"], lo, out)
+    out = torch.where(t["below"], fp[..., :1], out)
+    out = torch.where(t["above"], fp[..., -1:], out)
+    return torch.where(t["outside"], torch.zeros_like(out), out)
 
 
 def _spectra_and_frequencies(name, spectra, frequencies):

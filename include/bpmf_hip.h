@@ -482,8 +482,10 @@ int bpmf_intertemplate_cc_dev(const float *d_waveforms, const float *d_base_weig
  * caller.  n_windows = bpmf_bp_num_windows(n, window, shift) = (n - window) / shift + 1.
  *
  * bpmf_bp_extract_peaks_dev: every rising-edge local maximum of the max-beam (the peak rule of
- * utils._detect_peaks, BPMF/utils.py:2292-2301: x[t] > x[t-1] and x[t+1] <= x[t], first and last
- * sample excluded, samples next to a NaN excluded) whose value exceeds `floor_value`, as
+ * utils._detect_peaks, BPMF/utils.py:2292-2301: x[t] - x[t-1] > 0 and x[t+1] - x[t] <= 0 in float64
+ * -- x[t] > x[t-1] and x[t+1] <= x[t] on finite values; an isolated +Inf is a peak, a run of equal
+ * infinities is none -- first and last sample excluded, samples next to a NaN excluded) whose value
+ * exceeds `floor_value` (-Inf: every local maximum; NaN: none), as
  * (sample, beam, source) records in arbitrary order.  *d_count receives the number found (may
  * exceed `capacity`; only the first `capacity` are stored).  d_sources may be NULL (source = 0).
  */

@@ -11,9 +11,10 @@
 //                              order-preserving keys through an LDS histogram; windows are read from
 //                              L2 (a window of 90 000 samples is 360 KB), so the kernel is bound by
 //                              LDS atomics, not HBM: 4 B per sample per pass.
-//   bpmf_bp_extract_peaks_dev  rising-edge local maxima (x[t] > x[t-1] and x[t+1] <= x[t], the
-//                              `edge="rising"` rule of _detect_peaks :2292-2301) above a scalar floor,
-//                              compacted as (sample, beam, source) records.
+//   bpmf_bp_extract_peaks_dev  rising-edge local maxima (x[t] - x[t-1] > 0 and x[t+1] - x[t] <= 0 in
+//                              float64, the `edge="rising"` rule of _detect_peaks :2292-2301: on finite
+//                              values x[t] > x[t-1] and x[t+1] <= x[t]; a run of equal infinities is no
+//                              peak) above a scalar floor, compacted as (sample, beam, source) records.
 //
 // The floor is the smallest node of the interpolated threshold: a lower bound of threshold(t) for
 // every t, so the compacted list is a superset of the peaks above the threshold, and every peak it
@@ -53,7 +54,8 @@ __global__ __launch_bounds__(SEL_THREADS) void bp_window_stats_kernel(
         if (threadIdx.x == 0) { med[q] = __uint_as_float(0x7fc00000u); mad[q] = __uint_as_float(0x7fc00000u); }
         return;
     }
-    const float m = window_median<false>(x, len, len, 0.0f, hist, sel);
+    // (+ 0.0f: np.median ends in np.mean, whose sum starts from +0 -- a median of -0.0 comes out as +0.0 there)
+    const float m = window_median<false>(x, len, len, 0.0f, hist, sel) + 0.0f;
     const float d = window_median<true>(x, len, len, m, hist, sel);
     if (threadIdx.x == 0) { med[q] = m; mad[q] = d; }
 }
@@ -70,9 +72,13 @@ __global__ __launch_bounds__(256) void bp_extract_peaks_kernel(
     if (t >= 1 && t < n - 1) {
         const float x0 = beam[t - 1], x2 = beam[t + 1];
         x1 = beam[t];
+        // the reference tests DIFFERENCES (dx = x[1:] - x[:-1] in float64, dx > 0 and dx <= 0): the sign of a
+        // difference of two finite float32 is exact in float64, so on finite input this is x1 > x0 && x2 <= x1;
+        // Inf - Inf is NaN and fails both tests, so a run of equal infinities is no peak (an isolated +Inf is).
         // NaN neighbours: the reference turns NaNs into +inf and then drops every peak next to one;
         // comparisons with NaN are false, which excludes the same samples here
-        hit = x1 > x0 && x2 <= x1 && (double)x1 > floor_;
+        const double d0 = (double)x1 - (double)x0, d1 = (double)x2 - (double)x1;
+        hit = d0 > 0.0 && d1 <= 0.0 && (double)x1 > floor_;
     }
     const unsigned long long mask = __ballot(hit);
     if (mask == 0) return;
@@ -125,7 +131,7 @@ extern "C" int bpmf_bp_extract_peaks_dev(const float* d_beam, const int32_t* d_s
                                          bpmf_bp_peak* d_records)
 {
     hipStream_t stream = (hipStream_t)stream_;
-    if (!d_beam || !d_count || (!d_records && capacity)) {
+    if ((!d_beam && n) || !d_count || (!d_records && capacity)) {     // (an empty series has no address)
         set_error("bpmf_bp_extract_peaks_dev: null pointer");
         return -1;
     }

@@ -150,6 +150,22 @@ peak_dtype = np.dtype([("index", np.int32), ("beam", np.float32), ("source", np.
                        ("pad", np.int32)])
 
 
+def bp_window_plan(n, window, overlap=0.75):
+    """(window, shift, n_windows) of the sliding statistics behind the backprojection threshold
+    (BPMF/template_search.py:1452), or ValueError where the reference itself cannot run: a shift of 0
+    samples (it divides by it) or a series shorter than the window (it would index node -1)."""
+    n, window = int(n), int(window)
+    shift = int((1.0 - overlap) * window)
+    if window < 1:
+        raise ValueError(f"sliding window of {window} samples")
+    if shift < 1:
+        raise ValueError(f"shift of {shift} samples between windows: int((1 - overlap) * window) with overlap "
+                         f"{overlap!r} and window {window}")
+    if n < window:
+        raise ValueError(f"series shorter than the sliding window ({n} < {window} samples)")
+    return window, shift, (n - window) // shift + 1
+
+
 class BeamDetectorGPU:
     """Device side of ``Beamformer.find_detections`` (BPMF/template_search.py:574-627): the sliding
     median/MAD statistics of its threshold (:1418-1487) and the extraction of the rising-edge local
@@ -171,11 +187,7 @@ class BeamDetectorGPU:
         t = self.torch
         x = beam.reshape(-1).contiguous()
         n = x.numel()
-        window = int(window)
-        shift = int((1.0 - overlap) * window)
-        nw = self.lib.bpmf_bp_num_windows(n, window, shift)
-        if nw == 0:
-            raise ValueError("series shorter than the sliding window")
+        window, shift, nw = bp_window_plan(n, window, overlap)         # (= bpmf_bp_num_windows(n, window, shift))
         med = t.zeros(nw + 2, dtype=t.float32, device=self.device)
         mad = t.zeros(nw + 2, dtype=t.float32, device=self.device)
         _lib.call("bpmf_bp_window_stats_dev", self.device, x, n, window, shift, _lib.STREAM, med, mad)

@@ -1811,7 +1811,7 @@ def sharded_backprojection_detections(features, moveouts, weights_phases, weight
 
 
 def beam_detections_device(beam, arg, *, mpd, threshold=None, window=None, n_dev=15.0, overlap=0.75,
-                           device=None):
+                           device=None, detector=None):
     """``Beamformer.find_detections`` (BPMF/template_search.py:574-627) on a max-beam that lives
     on the device: `beam` (N,) float32 and `arg` (N,) int32 device tensors (the output of
     BeamformerGPU.run).  Nothing of length N is downloaded:
@@ -1823,10 +1823,19 @@ def beam_detections_device(beam, arg, *, mpd, threshold=None, window=None, n_dev
          survivors, the +-mpd/2 snap (on windows of the beam gathered in one small transfer) and
          np.unique -- the reference's own index logic (postprocess.find_beam_detections_from_candidates).
 
+    The result is postprocess.find_beam_detections on the downloaded series for every float32 series, +-Inf
+    included (DESIGN.md s4 "Non-finite features", rule 3), and for every form of the threshold.
+
+    `detector`: an object with ``window_stats(beam, window, overlap)`` and ``extract_peaks(beam, sources, floor)``
+    in place of a threshold.BeamDetectorGPU -- the CPU stand-in of the host tests; everything else here works
+    on CPU tensors as well.
+
     Returns (peak samples int64, source indices int32, threshold nodes (centre, values) or None)."""
     import torch
-    from .threshold import BeamDetectorGPU
-    det = BeamDetectorGPU(device=device if device is not None else beam.device.index)
+    if detector is None:
+        from .threshold import BeamDetectorGPU
+        detector = BeamDetectorGPU(device=device if device is not None else beam.device.index)
+    det = detector
     n = beam.numel()
     nodes = None
     if threshold is None:
@@ -1836,12 +1845,12 @@ def beam_detections_device(beam, arg, *, mpd, threshold=None, window=None, n_dev
         # a NaN node (a window that holds a NaN, or the reference's empty last window when the
         # series is a whole number of non-overlapping windows) makes the interpolated threshold
         # NaN around it, where the reference then keeps no peak (`>` is false); the floor is the
-        # smallest finite node
-        # smallest finite node -- less one float32 ulp: the interpolation (SciPy's order of operations,
+        # smallest node that is not NaN (a +Inf node -- a finite median under an Inf MAD -- lets nothing pass around
+        # it either) -- less one float32 ulp: the interpolation (SciPy's order of operations,
         # pp.interp_threshold) can land an ulp of float64 below two equal nodes, and a peak exactly as high
         # as the node would then pass the reference's `>` but not the floor
-        finite = thr[np.isfinite(thr)]
-        floor = float(np.nextafter(np.float32(finite.min()), np.float32(-np.inf))) if finite.size else float("nan")
+        real = thr[~np.isnan(thr)]
+        floor = float(np.nextafter(np.float32(real.min()), np.float32(-np.inf))) if real.size else float("nan")
 
         def threshold_at(samples):
             return pp.interp_threshold(samples, centre, thr)
@@ -1852,11 +1861,14 @@ def beam_detections_device(beam, arg, *, mpd, threshold=None, window=None, n_dev
             return np.full(len(samples), float(threshold))
     else:
         thr_arr = np.asarray(threshold)
-        floor = float(np.nanmin(thr_arr)) if np.isfinite(thr_arr).any() else float("nan")
+        real = thr_arr[~np.isnan(thr_arr)]
+        floor = float(real.min()) if real.size else float("nan")
 
         def threshold_at(samples):
             return thr_arr[samples]
-    if not np.isfinite(floor):               # no finite threshold anywhere: nothing can exceed it
+    # a NaN floor (no threshold value that is not NaN) or a +Inf one: nothing can exceed it.  A -Inf floor is a
+    # threshold like any other: every peak is above it, as in the reference (`x > -inf`)
+    if np.isnan(floor) or floor == np.inf:
         return np.zeros(0, dtype=np.int64), np.zeros(0, dtype=np.int32), nodes
     rec = det.extract_peaks(beam, arg, floor)
     if mpd > 1 and pp.has_close_ties(rec["index"], rec["beam"], mpd):
